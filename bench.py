@@ -17,7 +17,10 @@ steps; lr only scales the update, the work per step is identical, and the run mu
 gradient all-reduce + optimizer (one `sess.run(train_ops)` of train.py:228) on synthetic inputs
 already resident in HBM.  Strong scaling: rank r works on rows [r*512/N, (r+1)*512/N).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step, and the run's config and losses); its timed steps
+carry no launch records.  --dump-outputs DIR then also writes what the last timed step computed (see dump_outputs()).
+With --full the line carries, besides, the legs below (the timed steps then take the launch records of `roofline`):
   roofline     : the dominant kernel symbol (most device time among the MFMA launches; since round 6 the Winograd product of the
                  conv3x3 forward pass, wino_mm_kernel<0,2>; with FTE_CONV_ALGO=direct an igemm_kernel<...> instantiation).  Its
                  launches inside the recorded steps (two of the timed steps at 512 images, every 4th where the net walks one
@@ -283,13 +286,41 @@ def time_other_configs(dev, steps0=10, warmup0=3):
     return out
 
 
+DUMP_SAMPLE = 1 << 20                            # values kept of a larger variable (the whole dump stays near 42 MB)
+
+
+def dump_outputs(d, net, losses):
+    """--dump-outputs: what a caller of the timed step receives after the last one, as float32 .npy files in `d` --
+    the losses (losses.npy, in the order of the line's `losses`) and every variable after the optimizer update in its reference
+    layout (<name with '/' as '.'>.npy).  A variable of more than DUMP_SAMPLE values is reduced to a fixed sample: flat indices
+    drawn without replacement by a generator seeded with the CRC-32 of its name, in increasing order -- the same positions in
+    every run and every build."""
+    import zlib
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'losses.npy'), np.array([float(l) for l in losses], dtype=np.float32))
+    for name in sorted(net.variables):
+        v = net.get_variable(name).float().cpu().numpy()
+        if v.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(v.size, DUMP_SAMPLE, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(d, name.replace('/', '.') + '.npy'), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)      # SURVEY.md 8d: mean over >= 50 timed steps after >= 10 warm-up
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the `other_configs` leg (N = 1 only, ~15 s)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the launch records (roofline, per-shape table, conv_algo launch counts), the CPU baseline + parity, '
+                         '`other_configs` and, N > 1, the all-reduce figures; without it only the contract fields')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs())')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline and parity')
+    ap.add_argument('--no-other-configs', action='store_true', help='--full: skip the `other_configs` leg (N = 1 only, ~15 s)')
     ap.add_argument('--one-stream', action='store_true',
                     help='profiling only: EVERY step runs as the launch-record steps do (one chain of kernels, no second stream), so that '
                          'rocprofv3 kernel durations and PMC bytes are each launch\'s own (scripts/collect_profiles.sh); the value printed is '
@@ -300,6 +331,8 @@ def main():
                     help="operand precision of the MFMA products (fte_set_mfma_dtype).  The metric (BASELINE.json configs[1]) is "
                          "fp32 = the default; bf16 = bf16 operands, fp32 accumulate, fp32 storage (exploration, configs[2]'s precision)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         self_launch(args.gpus, sys.argv[1:])     # does not return
@@ -363,14 +396,15 @@ def main():
     barrier()
     # Launch records (event pairs around every MFMA-kernel launch, for the roofline leg) are taken on every PROF_EVERY-th
     # timed step: an event pair costs a queue barrier per launch -- recording all steps lowers the measured rate by 4.6 %
-    # at 64 images per GPU (7.57 k -> 7.24 k images/s), by 0.5 % at 512.  FTE_BENCH_NO_PROF=1 turns them off (exploration).
+    # at 64 images per GPU (7.57 k -> 7.24 k images/s), by 0.5 % at 512.  Only --full takes them; FTE_BENCH_NO_PROF=1 turns
+    # them off there too (exploration).
     PROF_EVERY = 4
     two_streams = getattr(net, '_side_stream', None) is not None and net._side_stream(shard) is not None
     if two_streams:
         # small shards / bf16 mode: the backward walk uses two streams and a recorded step does not (below) -- two recorded steps
         # (the first and the middle one) are enough for the per-shape table and cost the timed region < 1 %
         PROF_EVERY = max(4, (args.steps + 1) // 2)
-    prof = os.environ.get('FTE_BENCH_NO_PROF') != '1'
+    prof = args.full and os.environ.get('FTE_BENCH_NO_PROF') != '1'
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]     # per-step device times (no host sync)
     net.one_stream = args.one_stream
     first = True
@@ -390,8 +424,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    _lib.query('fte_prof_enable', 0)
-    records = _lib.prof_records(shapes=True) if rank == 0 else []
+    records = []
+    if prof:
+        _lib.query('fte_prof_enable', 0)
+        records = _lib.prof_records(shapes=True) if rank == 0 else []
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -400,10 +436,12 @@ def main():
     import math
     if not all(math.isfinite(v) for v in loss_vals):
         raise SystemExit('non-finite losses %s: the timed run is invalid' % loss_vals)
+    if args.dump_outputs and rank == 0:           # before anything below runs more steps on these weights
+        dump_outputs(args.dump_outputs, net, losses)
 
     # ---- N > 1: what the collective costs (outside the timed region) ----
     allreduce = None
-    if world > 1:
+    if world > 1 and args.full:
         buckets = net.grad_buckets()
         alone = []
         for a, b in buckets:
@@ -452,46 +490,47 @@ def main():
 
     if rank == 0:
         ms = 1000.0 * elapsed / args.steps
-        if not records:                      # FTE_BENCH_NO_PROF=1: throughput only
+        if args.full and not records:                   # FTE_BENCH_NO_PROF=1: throughput only
             print(json.dumps({'value': round(gb * args.steps / elapsed, 2), 'ms_per_step': round(ms, 3), 'n_gpus': world, 'note': 'launch records off'}))
             return
-        sampled = (args.steps + PROF_EVERY - 1) // PROF_EVERY
-        # per-symbol table: key = the kernel symbol the launch was dispatched to, as the library recorded it
-        # (fte_prof_get_name: the template arguments rocprofv3 prints) -> [launches, flops, ms, alg bytes]; kinds: its op
-        table, shapes, kinds = {}, {}, {}
-        for sig, fl, ms_, mnk, by, sym in records:
-            t = table.setdefault(sym, [0, 0.0, 0.0, 0.0])
-            kinds[sym] = op_kind(sig, sym)
-            t[0] += 1; t[1] += fl; t[2] += ms_; t[3] += by
-            s = shapes.setdefault((op_kind(sig, sym),) + tuple(mnk) + (sig[3], sig[4]), [0, 0.0, 0.0, 0.0])
-            s[0] += 1; s[1] += fl; s[2] += ms_; s[3] += by
-        DOM = max(table, key=lambda k: table[k][2])              # the symbol with the most device time
-        cnt, dom_flops, dom_ms, dom_bytes = table[DOM]
-        avg_ms = dom_ms / cnt
-        achieved = dom_flops / (dom_ms * 1e-3) / 1e12
-        all_ms = sum(v[2] for v in table.values())
-        all_flops = sum(v[1] for v in table.values())
-        # PMC traffic: cannot be collected inside this process; measured by rocprofv3 --pmc on this same command and kept
-        # under profiles/, stamped with the kernel sources it was measured on (stale figures are nulled, not reported)
-        traffic, tsrc, tnote = None, None, None
-        tpath = latest_traffic_file(args.mfma_dtype)
-        if world == 1 and tpath and gb == GLOBAL_BATCH:
-            tinfo = json.load(open(tpath))
-            ent = (tinfo.get('symbols') or {}).get(DOM)
-            if tinfo.get('kernel_src_sha') != library_src_sha():
-                tnote = 'profiles/%s was measured on other kernel sources (%s != library %s): traffic nulled' % (
-                    os.path.basename(tpath), tinfo.get('kernel_src_sha'), library_src_sha())
-            elif ent and tinfo.get('mfma_dtype', 'f32') == args.mfma_dtype:
-                traffic = ent['hbm_bytes_per_launch']
-                tsrc = 'profiles/' + os.path.basename(tpath)
-        per_shape = []
-        for key in sorted(shapes, key=lambda k: -shapes[k][2]):
-            c_, fl_, ms_, by_ = shapes[key]
-            tf_ = fl_ / (ms_ * 1e-3) / 1e12
-            per_shape.append({'op': key[0], 'rows': key[1], 'N': key[2], 'K': key[3], 'tile': TILES.get(key[4], '?'), 'splits': key[5],
-                              'launches_per_step': round(c_ / sampled, 2), 'ms': round(ms_ / c_, 4),
-                              'tflops': round(tf_, 1), 'frac': round(tf_ / peak, 3),
-                              'alg_GBps': round(by_ / (ms_ * 1e-3) / 1e9, 0)})
+        if args.full:
+            sampled = (args.steps + PROF_EVERY - 1) // PROF_EVERY
+            # per-symbol table: key = the kernel symbol the launch was dispatched to, as the library recorded it
+            # (fte_prof_get_name: the template arguments rocprofv3 prints) -> [launches, flops, ms, alg bytes]; kinds: its op
+            table, shapes, kinds = {}, {}, {}
+            for sig, fl, ms_, mnk, by, sym in records:
+                t = table.setdefault(sym, [0, 0.0, 0.0, 0.0])
+                kinds[sym] = op_kind(sig, sym)
+                t[0] += 1; t[1] += fl; t[2] += ms_; t[3] += by
+                s = shapes.setdefault((op_kind(sig, sym),) + tuple(mnk) + (sig[3], sig[4]), [0, 0.0, 0.0, 0.0])
+                s[0] += 1; s[1] += fl; s[2] += ms_; s[3] += by
+            DOM = max(table, key=lambda k: table[k][2])              # the symbol with the most device time
+            cnt, dom_flops, dom_ms, dom_bytes = table[DOM]
+            avg_ms = dom_ms / cnt
+            achieved = dom_flops / (dom_ms * 1e-3) / 1e12
+            all_ms = sum(v[2] for v in table.values())
+            all_flops = sum(v[1] for v in table.values())
+            # PMC traffic: cannot be collected inside this process; measured by rocprofv3 --pmc on this same command and kept
+            # under profiles/, stamped with the kernel sources it was measured on (stale figures are nulled, not reported)
+            traffic, tsrc, tnote = None, None, None
+            tpath = latest_traffic_file(args.mfma_dtype)
+            if world == 1 and tpath and gb == GLOBAL_BATCH:
+                tinfo = json.load(open(tpath))
+                ent = (tinfo.get('symbols') or {}).get(DOM)
+                if tinfo.get('kernel_src_sha') != library_src_sha():
+                    tnote = 'profiles/%s was measured on other kernel sources (%s != library %s): traffic nulled' % (
+                        os.path.basename(tpath), tinfo.get('kernel_src_sha'), library_src_sha())
+                elif ent and tinfo.get('mfma_dtype', 'f32') == args.mfma_dtype:
+                    traffic = ent['hbm_bytes_per_launch']
+                    tsrc = 'profiles/' + os.path.basename(tpath)
+            per_shape = []
+            for key in sorted(shapes, key=lambda k: -shapes[k][2]):
+                c_, fl_, ms_, by_ = shapes[key]
+                tf_ = fl_ / (ms_ * 1e-3) / 1e12
+                per_shape.append({'op': key[0], 'rows': key[1], 'N': key[2], 'K': key[3], 'tile': TILES.get(key[4], '?'), 'splits': key[5],
+                                  'launches_per_step': round(c_ / sampled, 2), 'ms': round(ms_ / c_, 4),
+                                  'tflops': round(tf_, 1), 'frac': round(tf_ / peak, 3),
+                                  'alg_GBps': round(by_ / (ms_ * 1e-3) / 1e9, 0)})
         out = {
             'metric': 'images/sec (whole node), SphereFaceNet-20 112x112 bs512',
             'value': round(gb * args.steps / elapsed, 2),
@@ -507,54 +546,57 @@ def main():
             'config': {'workload': 'SphereFaceNet-20 + A-softmax training step, 112x112x3, global batch %d, 10575 classes, Momentum, %s' % (gb, {'f32': 'fp32', 'bf16': 'bf16 MFMA operands / fp32 accumulate + storage', 'bf16s': 'bf16 MFMA operands + bf16 storage of activations and inter-layer gradients / fp32 accumulate, sums, master weights'}[args.mfma_dtype]),
                        'global_batch': gb, 'per_gpu_batch': shard, 'lr': LR, 'parallelism': 'dp%d' % world,
                        'train_gflop_per_image': 12.2698},
-            # the algorithm of the stride-1 3x3 layers (fte.h FTE_CONV_*; the reference runs Winograd: train.py:260) and how many launches of
-            # a recorded step took it
-            'conv_algo': {'setting': CONV_ALGOS.get(_lib.query('fte_get_conv_algo'), '?'),
-                          'winograd_launches_per_step': round(sum(v[0] for k, v in table.items() if k.startswith('wino_')) / sampled, 2),
-                          'direct_mfma_launches_per_step': round(sum(v[0] for k, v in table.items() if not k.startswith('wino_')) / sampled, 2),
-                          'note': 'Winograd F(2x2,3x3) forward / data gradient and F(3x3,2x2) filter gradient on the stride-1 3x3 layers of '
-                                  '>= 128 channels, forward + filter gradient of the 64-channel stage; direct implicit GEMM elsewhere',
-                          # how the timed steps walk the net (the launch-record steps behind `roofline` run one chain of kernels instead)
-                          'forward_walk': ('two half shards on two streams' if getattr(net, '_fwd_halves', None) is not None and not args.one_stream
-                                           and net._fwd_halves(shard, _lib.get_mfma_dtype() == 'bf16') else 'one chain'),
-                          'backward_walk': 'filter gradients on a second stream' if two_streams and not args.one_stream else 'one chain'},
-            # step_mfma_frac: DIRECT-CONVOLUTION-EQUIVALENT FLOPs of the step (12.27 GFLOP per image) / time / peak -- the
-            # metric's own FLOP count; under Winograd the kernels execute fewer FLOPs, so this figure is not bounded by 1.
-            # step_mfma_frac_executed: the FLOPs the MFMA launches of a recorded step actually execute / the step time / peak (<= 1)
-            'step_mfma_frac': round(gb * args.steps / elapsed * 12.2698e9 / (peak * 1e12) / world, 4),
-            'step_mfma_frac_basis': 'direct-convolution-equivalent FLOPs (12.27 GFLOP per image)',
-            'step_mfma_frac_executed': round(all_flops / sampled / (elapsed / args.steps) / (peak * 1e12), 4),
-            'losses': dict(zip(losses_name, [round(v, 6) for v in loss_vals])),
-            'roofline': {'bound': 'mfma',
-                         'kernel': '%s = %s (%s)' % (DOM, {'fwd': 'conv3x3 forward + bias/PReLU/residual', 'dgrad': 'conv3x3 data gradient + PReLU gradient', 'wgrad': 'conv3x3 filter gradient'}[kinds[DOM]],
-                                                       'Winograd: 16 plane products on the fp32 MFMA; FLOPs = those the launch EXECUTES' if DOM.startswith('wino_') else 'MFMA implicit GEMM'),
-                         'achieved': round(achieved, 2), 'peak': peak,
-                         'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4),
-                         'launches_timed': cnt, 'avg_launch_ms': round(avg_ms, 4),
-                         'flops_per_launch_avg': dom_flops / cnt,
-                         'traffic': traffic, 'traffic_source': tsrc, 'traffic_note': tnote,
-                         'algorithmic_bytes_per_launch': round(dom_bytes / cnt),
-                         'algorithmic_GBps': round(dom_bytes / (dom_ms * 1e-3) / 1e9, 1),
-                         'all_mfma_kernels': {'launches': len(records), 'steps_sampled': sampled,
-                                              'ms_per_step': round(all_ms / sampled, 3),
-                                              'achieved': round(all_flops / (all_ms * 1e-3) / 1e12, 2),
-                                              'frac': round(all_flops / (all_ms * 1e-3) / 1e12 / peak, 4)},
-                         'per_symbol': {k: {'op': kinds[k], 'launches_per_step': round(v[0] / sampled, 2), 'ms_per_step': round(v[2] / sampled, 3),
-                                                             'tflops': round(v[1] / (v[2] * 1e-3) / 1e12, 1),
-                                                             'frac': round(v[1] / (v[2] * 1e-3) / 1e12 / peak, 3),
-                                                             'algorithmic_bytes_per_launch': round(v[3] / v[0])}
-                                        for k, v in sorted(table.items(), key=lambda kv: -kv[1][2])},
-                         'per_shape': per_shape},
-            'kernel_src_sha': library_src_sha(),          # the LIBRARY's stamp (= the sources': check_library_stamp())
         }
+        if args.full:
+            out.update({
+                # the algorithm of the stride-1 3x3 layers (fte.h FTE_CONV_*; the reference runs Winograd: train.py:260) and how many launches of
+                # a recorded step took it
+                'conv_algo': {'setting': CONV_ALGOS.get(_lib.query('fte_get_conv_algo'), '?'),
+                              'winograd_launches_per_step': round(sum(v[0] for k, v in table.items() if k.startswith('wino_')) / sampled, 2),
+                              'direct_mfma_launches_per_step': round(sum(v[0] for k, v in table.items() if not k.startswith('wino_')) / sampled, 2),
+                              'note': 'Winograd F(2x2,3x3) forward / data gradient and F(3x3,2x2) filter gradient on the stride-1 3x3 layers of '
+                                      '>= 128 channels, forward + filter gradient of the 64-channel stage; direct implicit GEMM elsewhere',
+                              # how the timed steps walk the net (the launch-record steps behind `roofline` run one chain of kernels instead)
+                              'forward_walk': ('two half shards on two streams' if getattr(net, '_fwd_halves', None) is not None and not args.one_stream
+                                               and net._fwd_halves(shard, _lib.get_mfma_dtype() == 'bf16') else 'one chain'),
+                              'backward_walk': 'filter gradients on a second stream' if two_streams and not args.one_stream else 'one chain'},
+                # step_mfma_frac: DIRECT-CONVOLUTION-EQUIVALENT FLOPs of the step (12.27 GFLOP per image) / time / peak -- the
+                # metric's own FLOP count; under Winograd the kernels execute fewer FLOPs, so this figure is not bounded by 1.
+                # step_mfma_frac_executed: the FLOPs the MFMA launches of a recorded step actually execute / the step time / peak (<= 1)
+                'step_mfma_frac': round(gb * args.steps / elapsed * 12.2698e9 / (peak * 1e12) / world, 4),
+                'step_mfma_frac_basis': 'direct-convolution-equivalent FLOPs (12.27 GFLOP per image)',
+                'step_mfma_frac_executed': round(all_flops / sampled / (elapsed / args.steps) / (peak * 1e12), 4)})
+        out['losses'] = dict(zip(losses_name, [round(v, 6) for v in loss_vals]))
+        if args.full:
+            out['roofline'] = {'bound': 'mfma',
+                               'kernel': '%s = %s (%s)' % (DOM, {'fwd': 'conv3x3 forward + bias/PReLU/residual', 'dgrad': 'conv3x3 data gradient + PReLU gradient', 'wgrad': 'conv3x3 filter gradient'}[kinds[DOM]],
+                                                             'Winograd: 16 plane products on the fp32 MFMA; FLOPs = those the launch EXECUTES' if DOM.startswith('wino_') else 'MFMA implicit GEMM'),
+                               'achieved': round(achieved, 2), 'peak': peak,
+                               'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4),
+                               'launches_timed': cnt, 'avg_launch_ms': round(avg_ms, 4),
+                               'flops_per_launch_avg': dom_flops / cnt,
+                               'traffic': traffic, 'traffic_source': tsrc, 'traffic_note': tnote,
+                               'algorithmic_bytes_per_launch': round(dom_bytes / cnt),
+                               'algorithmic_GBps': round(dom_bytes / (dom_ms * 1e-3) / 1e9, 1),
+                               'all_mfma_kernels': {'launches': len(records), 'steps_sampled': sampled,
+                                                    'ms_per_step': round(all_ms / sampled, 3),
+                                                    'achieved': round(all_flops / (all_ms * 1e-3) / 1e12, 2),
+                                                    'frac': round(all_flops / (all_ms * 1e-3) / 1e12 / peak, 4)},
+                               'per_symbol': {k: {'op': kinds[k], 'launches_per_step': round(v[0] / sampled, 2), 'ms_per_step': round(v[2] / sampled, 3),
+                                                                   'tflops': round(v[1] / (v[2] * 1e-3) / 1e12, 1),
+                                                                   'frac': round(v[1] / (v[2] * 1e-3) / 1e12 / peak, 3),
+                                                                   'algorithmic_bytes_per_launch': round(v[3] / v[0])}
+                                              for k, v in sorted(table.items(), key=lambda kv: -kv[1][2])},
+                               'per_shape': per_shape}
+        out['kernel_src_sha'] = library_src_sha()          # the LIBRARY's stamp (= the sources': check_library_stamp())
         if allreduce is not None:
             out['allreduce'] = allreduce
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del train_ops, model
             out['cpu_baseline'], out['parity'] = cpu_baseline_and_parity(dev, args.mfma_dtype)
-        else:
+        elif args.full:
             out['cpu_baseline'] = None
-        if world == 1 and not args.no_other_configs and gb == GLOBAL_BATCH and args.mfma_dtype == 'f32':
+        if args.full and world == 1 and not args.no_other_configs and gb == GLOBAL_BATCH and args.mfma_dtype == 'f32':
             train_ops = model = None
             del net, images, labels, inputs
             torch.cuda.empty_cache()

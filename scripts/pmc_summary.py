@@ -2,7 +2,7 @@
 
     python scripts/pmc_summary.py FETCH_DIR WRITE_DIR MFMA_DIR BENCH_JSON OUT_CSV OUT_JSON
 
-Each pass is `rocprofv3 --pmc <counters> --kernel-trace --output-format csv -- python3 bench.py --steps 2 --warmup 1
+Each pass is `rocprofv3 --pmc <counters> --kernel-trace --output-format csv -- python3 bench.py --full --steps 2 --warmup 1
 --no-cpu-baseline` (counters in separate passes, as MI355X_MICROARCH.md's HBM section prescribes).  Corrections from the
 same section: FETCH_SIZE / WRITE_SIZE are in KiB; gfx950 reports HALF the bytes of wide (16 B / lane) coalesced reads, so
 HBM bytes = 2 * FETCH_SIZE + WRITE_SIZE.  MFMA pipe busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs * GRBM_GUI_ACTIVE / 8);
@@ -77,6 +77,6 @@ with open(out_csv, 'w') as f:
 json.dump({'kernel_src_sha': bench.kernel_src_sha(), 'mfma_dtype': bline.get('dtype', 'f32'), 'symbols': symbols,
            'correction': 'FETCH_SIZE doubled (gfx950 reports half the bytes of wide coalesced 16-B/lane reads; MI355X_MICROARCH.md, HBM section); WRITE_SIZE exact; units KiB',
            'algorithmic_bytes': 'per launch, from the launch records of %s (every operand and result tensor of the launch once)' % os.path.basename(bench_json),
-           'collected_with': 'rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE (separate passes) --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline; summarised by scripts/pmc_summary.py',
+           'collected_with': 'rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE (separate passes) --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline; summarised by scripts/pmc_summary.py',
            'summary_file': out_csv}, open(out_json, 'w'), indent=1)
 print(open(out_csv).read()[:3000])

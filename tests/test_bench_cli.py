@@ -70,3 +70,14 @@ def test_other_configs_is_the_last_key_of_the_line():
     from tf_face_toolbox_amd.nets.net_base import net_select      # every name is a factory name
     for n, _, _ in names:
         assert net_select(n, 'NCHW', 5e-4) is not None
+
+
+def test_plain_run_options_are_offered():
+    """--full (the legs besides the headline figure) and --dump-outputs DIR are options of the command line; --steps below 1
+    is refused (it is the number of timed steps the result line divides by)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], env=_env(), stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout, r.stdout + r.stderr
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], env=_env(), stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode != 0 and '--steps must be at least 1' in r.stderr

@@ -119,7 +119,7 @@ def test_bench_py_runs_with_eight_ranks(tmp_path):
         env['FTE_BENCH_SHARED_GPU'] = '1'
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--global-batch', '64'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--global-batch', '64', '--full'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500, cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -162,7 +162,7 @@ def test_bench_py_runs_with_two_ranks(tmp_path, launcher):
         env['FTE_BENCH_SHARED_GPU'] = '1'
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--global-batch', '16']
+    tail = [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--global-batch', '16', '--full']
     if launcher == 'self':
         cmd = [sys.executable] + tail
     else:
