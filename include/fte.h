@@ -562,8 +562,33 @@ int fte_focal_loss_fwd_bwd(const float* logits, const int32_t* labels, float* lo
 int fte_asoftmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels,
                          float lambda, float* f, float* loss_rows, float* G, float* rowcoef,
                          int n, int c, int ld, float grad_scale, void* stream);
+/* colcoef_j = -sum_i G[i,j] * s[i,j] / wn_j^2 (columns c..ld-1 get 0): the norm-correction term of a head on the
+ * normalised weight columns, dw[:,j] += colcoef_j * w[:,j].  Serves both the A-softmax head and the additive-margin
+ * head below (whatever the loss, G = dLoss/ds and s = x @ w). */
 int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* colcoef,
                          int n, int c, int ld, void* stream);
+/* Additive-margin softmax: ArcFace (angular margin m, cos(theta + m)) and CosFace (cosine margin m3, cos(theta) - m3),
+ * InsightFace's combined margin with m1 = 1.  Scale S = `scale`.  For row i with label y, column j < c, eps = 1e-12:
+ *   c_ij = clamp(s_ij / (max(xn_i, eps) * wn_j), -1, 1)      (the clamp only absorbs rounding: identity in the derivative)
+ *   z_ij = S * c_ij (j != y);  z_iy = S * t(c_iy) with
+ *     m == 0:                      t = c - m3,                                 t' = 1                          (CosFace)
+ *     m > 0, c > cos(pi - m):      t = c cos m - sin_t sin m - m3,            t' = cos m + sin m * c / max(sin_t, 1e-6),
+ *                                  sin_t = sqrt(max((1 - c)(1 + c), 0))                                        (ArcFace)
+ *     m > 0, otherwise:            t = c - m sin m - m3,                       t' = 1       (theta + m > pi, easy_margin = False)
+ *   loss_rows[i] = logsumexp_j z_ij - z_iy
+ *   dL/dc_ij = grad_scale * S * (p_ij - [j = y]) * (j = y ? t' : 1),  p = softmax(z_i)
+ *   G_ij = dL/dc_ij / (max(xn_i, eps) * wn_j)                  (dLoss/ds: feeds the two classifier GEMMs)
+ *   rowcoef_i = xn_i > eps ? -sum_j G_ij s_ij / xn_i^2 : 0
+ *   f (optional, may be NULL) = z, the margin logits.
+ * With colcoef from fte_asoftmax_colcoef, dx = G W^T + rowcoef (.) x and dW = x^T G + colcoef (.) W: the exact gradient through
+ * both normalisations (not the straight-through variant that applies the margin under no_grad).  s / f / G are [n, ld],
+ * ld >= c; columns c..ld-1 get G = 0 and f = 0 and wn[j] is never read for j >= c.  An out-of-range label gives a NaN row
+ * (loss, rowcoef, G and f below c), never an out-of-bounds access.  Zero-norm weight columns are outside the contract.
+ * Presets: ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35.
+ * FTE_EINVAL: a null pointer (f excepted), n < 1, c < 1, ld < c, scale <= 0 or m < 0 (or either NaN). */
+int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels,
+                               float scale, float m, float m3, float* f, float* loss_rows, float* G, float* rowcoef,
+                               int n, int c, int ld, float grad_scale, void* stream);
 /* out[i] = sqrt(sum_j a[i,j]^2) over rows of [rows, ld] (cols used) */
 int fte_row_norms(const float* a, float* out, int rows, int cols, int ld, void* stream);
 /* out[j] = sqrt(sum_i a[i,j]^2) over columns */

@@ -1205,6 +1205,12 @@ int fte_asoftmax_fwd_bwd(const float* s, const float* xn, const float* wn, const
     if (!s || !xn || !wn || !labels || !loss_rows || !G || !rowcoef || n <= 0 || c <= 0 || ld < c) return FTE_EINVAL;
     return rc(k_asoftmax(s, xn, wn, labels, lambda, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
 }
+int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m, float m3,
+                               float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float grad_scale, void* stream) {
+    if (!s || !xn || !wn || !labels || !loss_rows || !G || !rowcoef || n <= 0 || c <= 0 || ld < c || !(scale > 0.f) || !(m >= 0.f))
+        return FTE_EINVAL;
+    return rc(k_margin_softmax(s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
+}
 int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int n, int c, int ld, void* stream) {
     if (!G || !s || !wn || !colcoef) return FTE_EINVAL;
     return rc(k_asoftmax_colcoef(G, s, wn, colcoef, n, c, ld, (hipStream_t)stream));

@@ -548,6 +548,163 @@ __global__ __launch_bounds__(256) void asoftmax_colcoef_kernel(const float* __re
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Additive-margin softmax (ArcFace m, CosFace m3; fte.h states the contract).  One block per row, s = raw x.W row.
+// Pass 1: one online max / sum-of-exp over the row (a thread rescales its partial sum only when its running max grows, so
+// the steady state costs one exp per element); the partials merge through block_max / block_sum in a fixed order.
+// Pass 2 re-reads s, writes G (and f) and sums G*s for rowcoef.  The target logit is computed once per row; the streams
+// select it with one compare.  VEC: s / G / f / wn 16-byte aligned and ld % 4 == 0 -- dwordx4 over columns 4q..4q+3
+// (a chunk starting below c lies wholly below ld; wn is read as a vector only where the chunk lies wholly below c).
+// c = s * (1/max(xn, eps)) * rcp(wn): v_rcp_f32 (1 ulp) instead of a division; exp is __expf: its error, |x| * 2^-24
+// relative for exp(x), is below 1e-6 on every term that is more than 2e-9 of the row's sum.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ float clamp1(float v) { return v > 1.f ? 1.f : (v < -1.f ? -1.f : v); }     // NaN stays NaN
+struct MarginRow {
+    float ix, S, zy;
+    int y;
+    __device__ __forceinline__ float z(float sv, float wv, int j, float& r) const {
+        r = ix * __builtin_amdgcn_rcpf(wv);
+        return j == y ? zy : S * clamp1(sv * r);
+    }
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                             const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                             float S, float m, float m3, float* __restrict__ f,
+                                                             float* __restrict__ loss_rows, float* __restrict__ G,
+                                                             float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    constexpr int U = 4;                                        // chunks in flight per thread and trip
+    constexpr float EPS = 1e-12f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * ld;
+    float* gr = G + (long)row * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const int yl = labels[row];
+    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
+    const int y = bad ? 0 : yl;
+    const float xr = xn[row];
+    MarginRow R;
+    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
+    R.S = S;
+    R.y = y;
+    // target term, once per row
+    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
+    float ty = cy - m3, tp = 1.f;
+    if (m > 0.f) {
+        const float cm = cosf(m), sm = sinf(m);
+        if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
+            const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+            ty = cy * cm - st * sm - m3;
+            tp = cm + sm * cy / fmaxf(st, 1e-6f);
+        } else {
+            ty = cy - m * sm - m3;                              // easy_margin = False fallback
+        }
+    }
+    R.zy = S * ty;
+
+    // pass 1: online max / sum of exp
+    float mx = -INFINITY, se = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < c; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    float z[4], r;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
+                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
+                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < c; j += 256) {
+            float r;
+            const float z = R.z(sr[j], wn[j], j, r);
+            if (z > mx) { se *= __expf(mx - z); mx = z; }
+            se += __expf(z - mx);
+        }
+    }
+    const float M = block_max(mx, sh);
+    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
+    const float inv = 1.f / se;
+    const float gS = gscale * S, gT = gscale * S * tp;
+
+    // pass 2: G (and f), sum of G * s
+    float acc = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < ld; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < ld) {
+                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
+                    if (j < c) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (j + k < c) {
+                                float r;
+                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
+                                const float p = __expf(z - M) * inv;
+                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
+                                acc += g * sv[u][k];
+                                gv[k] = g;
+                                fv[k] = z;
+                            }
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(gr + j) = gv;
+                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < ld; j += 256) {
+            float g = 0.f, fv = 0.f;
+            if (j < c) {
+                float r;
+                const float sv = sr[j];
+                const float z = R.z(sv, wn[j], j, r);
+                const float p = __expf(z - M) * inv;
+                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
+                acc += g * sv;
+                fv = z;
+            }
+            gr[j] = g;
+            if (fr) fr[j] = fv;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (t == 0) {
+        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
+        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
+    }
+}
+
 __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict__ a, float* __restrict__ out, int cols, int ld) {
     __shared__ float sh[4];
     const float* r = a + (long)blockIdx.x * ld;
@@ -1037,6 +1194,13 @@ hipError_t k_focal_loss(const float* logits, const int32_t* labels, float* loss_
 hipError_t k_asoftmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float lam, float* f, float* loss_rows,
                       float* G, float* rowcoef, int n, int c, int ld, float gs, hipStream_t st) {
     hipLaunchKernelGGL(asoftmax_kernel, dim3(n), dim3(256), 0, st, s, xn, wn, labels, lam, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m, float m3,
+                            float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs, hipStream_t st) {
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    if (vec) hipLaunchKernelGGL(margin_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
+    else hipLaunchKernelGGL(margin_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
     return hipGetLastError();
 }
 hipError_t k_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* cc, int n, int c, int ld, hipStream_t st) {

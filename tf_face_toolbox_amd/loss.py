@@ -1,5 +1,5 @@
 """Host-side mirror of the reference's loss.py: focal_loss (:18-27), center_loss (:29-45), batch_hard_triplet_loss
-(:47-78) on libfte.so.  Same names, argument meaning and defaults.  There is no autograd here, so every function
+(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference).  Same names, argument meaning and defaults.  There is no autograd here, so every function
 also returns the gradient of ITS OWN loss value with respect to its first argument (what tf.gradients would have
 produced for that term); the graph nets wire them as heads (nets/graph.py), a caller can combine them freely.
 
@@ -69,3 +69,44 @@ def batch_hard_triplet_loss(features, labels, margin=None, metric='euclidean'):
     _lib.call('fte_batch_hard_triplet_fwd_bwd', features, labels, 0.0 if margin is None else float(margin), int(margin is None), 1.0 / n,
               rows, df, n, d, ws, ws.numel() * 4, _stream())
     return rows, df
+
+
+def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, margin_cos=0.0, num_classes=None):
+    """Additive-margin softmax on the normalised features and weight columns: ArcFace (angular margin `margin`, cos(theta + m))
+    and CosFace (cosine margin `margin_cos`, cos(theta) - m3), scale S = `scale`; the contract is fte.h's
+    fte_margin_softmax_fwd_bwd.  ArcFace: scale=64, margin=0.5, margin_cos=0; CosFace: scale=64, margin=0, margin_cos=0.35.
+    features [N, D], weights [D, ld] (columns num_classes..ld-1 are padding, default num_classes = ld), labels [N] int32;
+    D % 64 == 0 and ld % 64 == 0 (the classifier products' tiling: pad with zero columns).
+    -> (loss [0-d] = mean over the rows, dfeatures [N, D], dweights [D, ld]): the exact gradient of the mean through both
+    normalisations; padding columns get 0."""
+    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
+    weights = _check(weights, torch.float32, 'weights')
+    n, d = features.shape
+    ld = weights.shape[1]
+    if weights.shape[0] != d or labels.shape != (n,):
+        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
+                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
+    c = ld if num_classes is None else int(num_classes)
+    st = _stream()
+    dev = features.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    wsb = max(_lib.query('fte_gemm_ws_bytes', n, ld, d), 4096)
+    ws = torch.empty(wsb // 4 + 1024, **f32)
+    wsb = ws.numel() * 4
+    s = torch.empty(n, ld, **f32)
+    xn, rowcoef, rows = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
+    wn, colcoef = torch.empty(ld, **f32), torch.empty(ld, **f32)
+    G = torch.empty(n, ld, **f32)
+    dx, dw = torch.empty_like(features), torch.empty_like(weights)
+    call = _lib.call
+    call('fte_gemm_nn', features, weights, None, s, n, ld, d, ws, wsb, st)
+    call('fte_row_norms', features, xn, n, d, d, st)
+    call('fte_col_norms', weights, wn, d, c, ld, st)
+    call('fte_margin_softmax_fwd_bwd', s, xn, wn, labels, float(scale), float(margin), float(margin_cos), None, rows, G, rowcoef,
+         n, c, ld, 1.0 / n, st)
+    call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, c, ld, st)
+    call('fte_gemm_tn', features, G, dw, n, ld, d, ws, wsb, st)
+    call('fte_add_scaled_rows_cols', dw, weights, None, colcoef, d, ld, ld, st)
+    call('fte_gemm_nt', G, weights, None, None, 0, None, dx, None, n, ld, d, ws, wsb, st)
+    call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
+    return _scaled_sum(rows, 1.0 / n), dx, dw

@@ -13,7 +13,7 @@ from collections import OrderedDict
 import torch
 
 from .. import _lib
-from .net_base import Network, side_stream
+from .net_base import MARGIN_PRESETS, Network, margin_params, side_stream
 from .sphere import Variable, same_pads
 
 BN_EPS = 1e-3          # nets/resnet.py:97-99 via layers.batch_norm defaults
@@ -80,8 +80,9 @@ class GraphNet(Network):
     multiple; the padding channels are exactly zero in the forward and backward pass (zero weight rows / columns, BN of
     a constant-zero channel with beta 0 stays 0, and every gradient flowing into them is 0), so results equal the
     unpadded net's while all kernels keep their float4 / MFMA-tile granularity.  Heads: 'softmax' (CE on the classifier), 'focal' (loss.py:18-27 instead of CE), 'softmax+center' (CE + weight * center loss
-    on the pooled features, loss.py:29-45) and 'triplet' (batch-hard triplet on the pooled features, loss.py:47-78, no
-    classifier)."""
+    on the pooled features, loss.py:29-45), 'triplet' (batch-hard triplet on the pooled features, loss.py:47-78, no
+    classifier) and 'arcface' / 'cosface' (additive-margin softmax on the normalised classifier input and columns, fte.h
+    fte_margin_softmax_fwd_bwd; (S, m, m3) in margin_scale / margin / margin_cos)."""
 
     head = 'softmax'
     channel_pad = 1
@@ -107,6 +108,15 @@ class GraphNet(Network):
         self.center_comm = None           # set by DataParallel(sync_centers=True): all-gather the scatter rows, one table for all replicas
         self.triplet_margin = None        # 'triplet': None = soft-margin (softplus), loss.py:47
         self.focal_gamma, self.focal_alpha = 1.0, 2.0     # 'focal': loss.py:18 defaults (names as in the reference)
+        self.margin_scale = self.margin = self.margin_cos = None      # 'arcface' / 'cosface': S, m, m3 (_set_head)
+
+    def _set_head(self, head, scale=None, margin=None, margin_cos=None):
+        """the subclasses' head= argument; a margin head resolves (S, m, m3) against its preset (nets/net_base.py MARGIN_PRESETS)"""
+        self.head = head
+        if head in MARGIN_PRESETS:
+            self.margin_scale, self.margin, self.margin_cos = margin_params(head, scale, margin, margin_cos)
+        elif (scale, margin, margin_cos) != (None, None, None):
+            raise ValueError('scale / margin / margin_cos belong to the arcface / cosface heads, not %r' % head)
 
     # ---- to be provided by the subclass ----------------------------------------------------------
     def build_graph(self, in_ch, num_classes):
@@ -709,6 +719,9 @@ class GraphNet(Network):
         fdim = self.shapes[self.feature_name][0]
         self.dfeat = torch.empty(n, fdim, **f32)
         self.ones_n = torch.ones(n, **f32)
+        if self.head in MARGIN_PRESETS:
+            self.xn, self.rowcoef = torch.empty(n, **f32), torch.empty(n, **f32)
+            self.wn, self.colcoef = torch.empty(self.cpad, **f32), torch.empty(self.cpad, **f32)
         need = max(need, 4 * n * fdim, 12 * n * n)
         self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
         self.ws_bytes = self.ws.numel() * 4
@@ -1158,6 +1171,15 @@ class GraphNet(Network):
             if self.head == 'focal':                         # loss.py:18-27 on the classifier logits
                 call('fte_focal_loss_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.focal_gamma, self.focal_alpha, self.tower_scale / n, st)
+            elif self.head in MARGIN_PRESETS:                # the margin on the raw classifier output; backward_head adds the norm terms
+                op = self.plan[-1]
+                k = self.shapes[op[2]][0]
+                call('fte_row_norms', self.t[op[2]], self.xn, n, k, k, st)
+                call('fte_col_norms', self.view(op[3]), self.wn, k, self.num_classes, self.cpad, st)
+                call('fte_margin_softmax_fwd_bwd', self.t['logits'], self.xn, self.wn, labels, self.margin_scale, self.margin,
+                     self.margin_cos, None, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
+                     self.tower_scale / n, st)
+                call('fte_asoftmax_colcoef', self.G, self.t['logits'], self.wn, self.colcoef, n, self.num_classes, self.cpad, st)
             else:
                 call('fte_softmax_ce_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.tower_scale / n, st)
@@ -1261,13 +1283,20 @@ class GraphNet(Network):
         self._grad = {}
         gin = torch.empty(n, k, dtype=torch.float32, device=self.device)
         side = self.side if os.environ.get('FTE_HEAD_SIDE', '1') != '0' else None
+        margin = self.head in MARGIN_PRESETS
+        gw = self.view(op[3], self.grads)
         if side is not None:
             main = torch.cuda.current_stream()
             side.wait_event(main.record_event())         # G (the loss head's gradient) and the features are complete
-            _lib.call('fte_gemm_tn', self.t[op[2]], self.G, self.view(op[3], self.grads), n, self.cpad, k, self.ws_side, self.ws_bytes, side.cuda_stream)
+            _lib.call('fte_gemm_tn', self.t[op[2]], self.G, gw, n, self.cpad, k, self.ws_side, self.ws_bytes, side.cuda_stream)
         else:
-            _lib.call('fte_gemm_tn', self.t[op[2]], self.G, self.view(op[3], self.grads), n, self.cpad, k, self.ws, self.ws_bytes, st)
+            _lib.call('fte_gemm_tn', self.t[op[2]], self.G, gw, n, self.cpad, k, self.ws, self.ws_bytes, st)
+        if margin:                                       # dW += colcoef (.) W, on the stream of the product, before the bucket is reduced
+            _lib.call('fte_add_scaled_rows_cols', gw, self.view(op[3]), None, self.colcoef, k, self.cpad, self.cpad,
+                      side.cuda_stream if side is not None else st)
         _lib.call('fte_gemm_nt', self.G, self.view(op[3]), None, None, 0, None, gin, None, n, self.cpad, k, self.ws, self.ws_bytes, st)
+        if margin:                                       # dx += rowcoef (.) x
+            _lib.call('fte_add_scaled_rows_cols', gin, self.t[op[2]], self.rowcoef, None, n, k, k, st)
         if side is not None and join:
             torch.cuda.current_stream().wait_stream(side)
         self._grad[op[2]] = gin

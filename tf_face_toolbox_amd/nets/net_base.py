@@ -8,6 +8,23 @@ gradient arena the parallel wrappers all-reduce.
 """
 import abc
 
+# (S, m, m3) of the additive-margin heads: ArcFace (Deng et al. 2019: s = 64, m = 0.5) and CosFace (Wang et al. 2018: s = 64,
+# m = 0.35, here the cosine margin m3)
+MARGIN_PRESETS = {'arcface': (64.0, 0.5, 0.0), 'cosface': (64.0, 0.0, 0.35)}
+
+
+def margin_params(head, scale=None, margin=None, margin_cos=None):
+    """(S, m, m3) of the additive-margin head `head`: the given values, the head's preset where an argument is None."""
+    if head not in MARGIN_PRESETS:
+        raise ValueError('%r is not an additive-margin head (%s)' % (head, ', '.join(sorted(MARGIN_PRESETS))))
+    ps, pm, pm3 = MARGIN_PRESETS[head]
+    S = float(ps if scale is None else scale)
+    m = float(pm if margin is None else margin)
+    m3 = float(pm3 if margin_cos is None else margin_cos)
+    if not (S > 0.0 and 0.0 <= m < 3.141592653589793 and abs(m3) < 1.0):
+        raise ValueError('margin head needs scale > 0, 0 <= margin < pi and |margin_cos| < 1 (got %r, %r, %r)' % (S, m, m3))
+    return S, m, m3
+
 
 def net_select(name, data_format='NCHW', weight_decay=5e-4):
     """nets/net_base.py:22-63.  Names kept verbatim; `SphereNet-ASoftmax` is the margin net the
@@ -19,9 +36,15 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4):
     elif name == 'SphereNet-ASoftmax':
         from .sphere import SphereNetMargin
         network = SphereNetMargin(data_format=data_format, weight_decay=weight_decay)
+    elif name in ('SphereNet-ArcFace', 'SphereNet-CosFace'):      # additive-margin heads (fte.h fte_margin_softmax_fwd_bwd)
+        from .sphere import SphereNetAdditiveMargin
+        network = SphereNetAdditiveMargin(data_format=data_format, weight_decay=weight_decay, head=name.split('-')[1].lower())
     elif name == 'ResNet-50':
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay)
+    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface'):
+        from .resnet import ResNet
+        network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay, head=name.split('-')[2])
     elif name == 'ResNet-26':                    # not a reference factory name; the class accepts 26 (nets/resnet.py:39-40)
         from .resnet import ResNet
         network = ResNet(num_layers=26, data_format=data_format, weight_decay=weight_decay)
@@ -87,6 +110,16 @@ class Network(abc.ABC):
 
     def param_list(self, is_training, trainable, scope=None):
         raise NotImplementedError
+
+    def set_margin(self, scale=None, margin=None, margin_cos=None):
+        """Margin nets only: replace the head's (S, m, m3) -- train.py --margin_scale / --margin / --margin_cos; None keeps a
+        value.  Takes effect from the next forward / loss_function."""
+        head = getattr(self, 'head', None)
+        if head not in MARGIN_PRESETS:
+            raise ValueError('%s has no additive-margin head' % self.name)
+        self.margin_scale, self.margin, self.margin_cos = margin_params(
+            head, self.margin_scale if scale is None else scale, self.margin if margin is None else margin,
+            self.margin_cos if margin_cos is None else margin_cos)
 
     def mult_lr_list(self, scope=None):
         return [1.0 for _ in self.param_list(is_training=True, trainable=True, scope=scope)]

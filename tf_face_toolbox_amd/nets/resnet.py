@@ -8,7 +8,8 @@ from .graph import GraphNet
 
 
 class ResNet(GraphNet):
-    def __init__(self, num_layers, pre_act=False, weight_decay=0.0005, data_format='NCHW', name='ResNet', seed=0):
+    def __init__(self, num_layers, pre_act=False, weight_decay=0.0005, data_format='NCHW', name='ResNet', seed=0, head='softmax',
+                 scale=None, margin=None, margin_cos=None):
         assert (num_layers - 2) % 3 == 0, "num_layers-2 must be divided by 3."        # nets/resnet.py:31
         self.num_layers = num_layers
         self.pre_act = pre_act
@@ -26,6 +27,7 @@ class ResNet(GraphNet):
         self.num_outputs = [256, 512, 1024, 2048]
         super(ResNet, self).__init__(weight_decay, data_format, name + '-' + str(num_layers), seed)
         self.feature_name = 'features'
+        self._set_head(head, scale, margin, margin_cos)
 
     # -- graph construction (what backbone()/forward() build as TF ops in the reference) -----------
     def conv_bn_relu(self, g, spec, scope, out, inp, cin, num_outputs, kernel_size, stride=1, relu=True):
@@ -80,10 +82,10 @@ class ResNeXt(ResNet):
     variable `conv2_3x3/weights` of shape [32,3,3,gw,gw]."""
 
     def __init__(self, num_layers, num_card=32, weight_decay=0.0005, data_format='NCHW', name='ResNeXt', seed=0,
-                 head='softmax', center_weight=0.0):
+                 head='softmax', center_weight=0.0, scale=None, margin=None, margin_cos=None):
         self.num_card = num_card
-        super(ResNeXt, self).__init__(num_layers, weight_decay=weight_decay, data_format=data_format, name=name, seed=seed)
-        self.head = head
+        super(ResNeXt, self).__init__(num_layers, weight_decay=weight_decay, data_format=data_format, name=name, seed=seed,
+                                      head=head, scale=scale, margin=margin, margin_cos=margin_cos)
         self.center_weight = center_weight
 
     def resBlock(self, g, spec, scope, t, x, cin, num_outputs, stride=1):
@@ -114,9 +116,9 @@ class SENet(ResNet):
     no such class: the composition and its oracle are the build's."""
 
     def __init__(self, num_layers, weight_decay=0.0005, data_format='NCHW', name='SENet', seed=0, head='softmax',
-                 triplet_margin=None):
-        super(SENet, self).__init__(num_layers, weight_decay=weight_decay, data_format=data_format, name=name, seed=seed)
-        self.head = head
+                 triplet_margin=None, scale=None, margin=None, margin_cos=None):
+        super(SENet, self).__init__(num_layers, weight_decay=weight_decay, data_format=data_format, name=name, seed=seed,
+                                    head=head, scale=scale, margin=margin, margin_cos=margin_cos)
         self.triplet_margin = triplet_margin
 
     def resBlock(self, g, spec, scope, t, x, cin, num_outputs, stride=1):

@@ -23,7 +23,7 @@ from collections import OrderedDict
 import torch
 
 from .. import _lib
-from .net_base import Network, side_stream
+from .net_base import MARGIN_PRESETS, Network, margin_params, side_stream
 
 NUM_BLOCKS = (1, 2, 4, 1)     # nets/sphere.py:58,62,66,70
 EMBED = 512                   # nets/sphere.py:73
@@ -215,7 +215,7 @@ class SphereNet(Network):
         self.emb = torch.empty(n, EMBED, **f32)
         self.s_raw = torch.empty(n, self.cpad, **f32)
         self.G = torch.empty(n, self.cpad, **f32)
-        self.logits_buf = torch.empty(n, self.cpad, **f32) if self.head == 'asoftmax' else self.s_raw
+        self.logits_buf = torch.empty(n, self.cpad, **f32) if self.head == 'asoftmax' or self.head in MARGIN_PRESETS else self.s_raw
         self.loss_rows = torch.empty(n, **f32)
         self.xn = torch.empty(n, **f32)
         self.wn = torch.empty(self.cpad, **f32)
@@ -719,18 +719,25 @@ class SphereNetMargin(SphereNet):
         wc = self.view('classifier/fc_classifier/weights')
         _lib.call('fte_row_norms', self.emb, self.xn, n, EMBED, EMBED, st)
         _lib.call('fte_col_norms', wc, self.wn, EMBED, self.num_classes, self.cpad, st)
+        self._margin_head(labels, n, st)
+        _lib.call('fte_asoftmax_colcoef', self.G, self.s_raw, self.wn, self.colcoef, n, self.num_classes, self.cpad, st)
+        return {'logits': self.logits_buf[:, :self.num_classes]}
+
+    def _margin_head(self, labels, n, st):
+        """margin logits, loss rows, G = dLoss/ds and rowcoef from s_raw and the norms"""
         self.lam = self.current_lambda()
         _lib.call('fte_asoftmax_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.lam, self.logits_buf, self.loss_rows,
                   self.G, self.rowcoef, n, self.num_classes, self.cpad, self._grad_scale(n), st)
-        _lib.call('fte_asoftmax_colcoef', self.G, self.s_raw, self.wn, self.colcoef, n, self.num_classes, self.cpad, st)
-        return {'logits': self.logits_buf[:, :self.num_classes]}
+
+    def _others(self):
+        others = OrderedDict()
+        others['lambda'] = self.lam
+        return others
 
     def loss_function(self, scope, labels, **logits):
         n = labels.shape[0]
         self._finish_losses(n)
-        others = OrderedDict()
-        others['lambda'] = self.lam
-        return [self.loss_slots[0], self.loss_slots[1]], ['cross_entropy', 'reg_loss'], others
+        return [self.loss_slots[0], self.loss_slots[1]], ['cross_entropy', 'reg_loss'], self._others()
 
     def _head_backward(self, n, st):
         super(SphereNetMargin, self)._head_backward(n, st)
@@ -738,3 +745,26 @@ class SphereNetMargin(SphereNet):
         gwc = self.view('classifier/fc_classifier/weights', self.grads)
         _lib.call('fte_add_scaled_rows_cols', gwc, wc, None, self.colcoef, EMBED, self.cpad, self.cpad, st)
         _lib.call('fte_add_scaled_rows_cols', self.demb, self.emb, self.rowcoef, None, n, EMBED, EMBED, st)
+
+
+class SphereNetAdditiveMargin(SphereNetMargin):
+    """SphereNet-20 + an additive-margin softmax head on the normalised embedding and classifier columns: ArcFace
+    (head='arcface', cos(theta + m)) or CosFace (head='cosface', cos(theta) - m3), scale S; fte.h fte_margin_softmax_fwd_bwd
+    states the contract.  `scale` / `margin` / `margin_cos` = S / m / m3, None = the head's preset (nets/net_base.py
+    MARGIN_PRESETS).  A margin net like SphereNetMargin (labels enter forward, DataParallel_margin drives it) with the same
+    norm-correction backward (rowcoef (.) x, colcoef (.) W): the gradient is exact through both normalisations, the margin is
+    not applied under no_grad.  The variables and their names are SphereNet's."""
+
+    def __init__(self, weight_decay=0.0005, data_format='NCHW', name='SphereNet', seed=0, head='arcface',
+                 scale=None, margin=None, margin_cos=None):
+        super(SphereNetAdditiveMargin, self).__init__(weight_decay, data_format, name, seed)
+        self.margin_scale, self.margin, self.margin_cos = margin_params(head, scale, margin, margin_cos)
+        self.head = head
+
+    def _margin_head(self, labels, n, st):
+        _lib.call('fte_margin_softmax_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.margin_scale, self.margin,
+                  self.margin_cos, self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
+                  self._grad_scale(n), st)
+
+    def _others(self):
+        return OrderedDict()

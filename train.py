@@ -63,6 +63,10 @@ def build_parser():
     parser.add_argument('--mfma_dtype', type=str, default='f32',
                         help='f32 (the reference arithmetic), bf16 (bf16 MFMA operands, fp32 accumulate and storage) or bf16s (bf16 operands and bf16 '
                              'storage of activations / inter-layer gradients; fp32 accumulate, sums and master weights: SphereNet).')
+    for flag, what in (('--margin_scale', 'scale S'), ('--margin', 'angular margin m (ArcFace)'), ('--margin_cos', 'cosine margin m3 (CosFace)')):
+        parser.add_argument(flag, type=float, default=None,
+                            help='additive-margin nets (SphereNet-ArcFace / -CosFace, ResNet-50-arcface / -cosface) only: the %s; '
+                                 "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35)" % what)
     return parser
 
 
@@ -173,6 +177,9 @@ def train(FLAGS):
     try:
         batches_per_epoch = inputs['num_examples'] // batch_size + 1                                  # train.py:172
         network = net_select(FLAGS.net_name, FLAGS.data_format, FLAGS.weight_decay)                  # train.py:174
+        margins = (FLAGS.margin_scale, FLAGS.margin, FLAGS.margin_cos)
+        if getattr(network, 'margin_scale', None) is not None and margins != (None, None, None):
+            network.set_margin(*margins)
         lr = lr_config(FLAGS, FLAGS.lr_decay_method, batches_per_epoch)                              # train.py:176
         if FLAGS.num_gpus > 1:                                                                        # train.py:178-183
             model = DataParallel_margin(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay, num_gpus=FLAGS.num_gpus,
