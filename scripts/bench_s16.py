@@ -1,5 +1,5 @@
 """Times the bf16-STORAGE conv forward / data gradient (fte_conv2d_fwd_s16 / fte_conv2d_dgrad_s16) on the four stride-1 SphereNet
-stages and prints a checksum of each result, so that kernel variants selected by environment hooks (FTE_IGEMM16_CFG, ...) can be
+stages and prints a checksum of each result, so that kernel variants selected by environment hooks (FTE_IGEMM16_PERSIST, ...) can be
 compared for speed AND equality in one gpurun call.        python scripts/bench_s16.py [B] [reps] [stages, e.g. 14,28]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B on ONE box of environment settings: each "VAR=val" three times, interleaved; per-layer minimum of bench_s16.py
-#   bash scripts/dev/ab_env.sh "FTE_IGEMM16_PERSIST=1" "FTE_IGEMM16_PERSIST=20"
+#   bash scripts/dev/ab_env.sh "FTE_IGEMM16_PERSIST=1" "FTE_IGEMM16_PERSIST=0"
 for r in 1 2 3; do for e in "$@"; do env $e python scripts/bench_s16.py 512 10 2>/dev/null | grep "x" | sed "s/^/CFG[$e] /"; done; done > /tmp/abe.log
 python3 - "$@" <<'PY'
 import sys, re, collections

@@ -1,4 +1,5 @@
-"""Debug: conv forward / dgrad s16 outputs of the persistent kernel against the per-tile kernel (two child processes, one per mode)."""
+"""Debug: conv forward / dgrad s16 outputs of the persistent kernel against the per-tile kernel (two child processes, one per mode:
+FTE_IGEMM16_PERSIST=0 / 1)."""
 import sys, os, subprocess
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 if len(sys.argv) > 1 and sys.argv[1] == 'child':

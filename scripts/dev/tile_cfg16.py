@@ -1,5 +1,5 @@
-"""fte_conv2d_fwd_s16 (bf16 storage, 1x1, no BN statistics) on one shape: microseconds per call -- for the FTE_IGEMM16_CFG / _DEEP /
-_PERSIST hooks (which tile of the LDS-DMA kernels a small-shard pointwise launch should use).
+"""fte_conv2d_fwd_s16 (bf16 storage, 1x1, no BN statistics) on one shape: microseconds per call -- for the FTE_IGEMM16_DEEP /
+_DEEP_TILES / _PERSIST hooks (which kernel of the LDS-DMA family a small-shard pointwise launch should use).
     python scripts/dev/tile_cfg16.py HW CIN COUT B"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

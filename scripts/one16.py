@@ -1,4 +1,4 @@
-"""Times ONE bf16-source conv forward (fte_conv2d_fwd16) at batch B: for ablation / PMC passes of igemm16.hip.
+"""Times ONE bf16-source conv forward (fte_conv2d_fwd16) at batch B: for PMC passes of igemm16.hip.
     python scripts/one16.py HW CIN COUT [B] [reps]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,4 +22,4 @@ e0.record()
 for _ in range(reps): f()
 e1.record(); torch.cuda.synchronize()
 t = e0.elapsed_time(e1) / reps
-print('%dx%d %d->%d B=%d: %.3f ms %.1f TF  (FTE_IGEMM16_ABL=%s)' % (hw, hw, cin, cout, B, t, 2.0 * B * hw * hw * 9 * cin * cout / t / 1e9, os.environ.get('FTE_IGEMM16_ABL', '0')))
+print('%dx%d %d->%d B=%d: %.3f ms %.1f TF' % (hw, hw, cin, cout, B, t, 2.0 * B * hw * hw * 9 * cin * cout / t / 1e9))

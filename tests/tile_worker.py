@@ -135,23 +135,23 @@ def _stored_ok(got16, ref64, scale):
     return float((err / lim).max()), bool((err <= lim).all())
 
 
-def run_s16fwd(n, h, w, cin, cout, stride, r):
+def run_s16fwd(n, h, w, cin, cout, stride, r, k=3):
     """fte_conv2d_fwd_s16 (bf16 x / shortcut in, bf16 z / y out): the persistent bf16 kernels at the sizes that select them"""
     assert stride == 1
     x, x16 = _bf(r.standard_normal((n, h, w, cin), dtype=np.float32))
-    wt = (r.standard_normal((3, 3, cin, cout), dtype=np.float32) * 0.05).astype(np.float32)
+    wt = (r.standard_normal((k, k, cin, cout), dtype=np.float32) * 0.05).astype(np.float32)
     wd = torch.from_numpy(wt).cuda()
-    w16 = torch.empty(3, 3, cin, cout, dtype=torch.int16, device='cuda'); w16t = torch.empty(3, 3, cout, cin, dtype=torch.int16, device='cuda')
-    call('fte_pack_weights_bf16', wd, w16, w16t, 3, cin, cout, stream())
+    w16 = torch.empty(k, k, cin, cout, dtype=torch.int16, device='cuda'); w16t = torch.empty(k, k, cout, cin, dtype=torch.int16, device='cuda')
+    call('fte_pack_weights_bf16', wd, w16, w16t, k, cin, cout, stream())
     wb = wd.bfloat16().float().cpu().numpy().astype(np.float64)
     b = r.standard_normal(cout, dtype=np.float32)
     al = (0.25 + 0.1 * r.standard_normal(cout, dtype=np.float32)).astype(np.float32)
     res, res16 = _bf(r.standard_normal((n, h, w, cout), dtype=np.float32))
     z16 = torch.empty(n, h, w, cout, dtype=torch.int16, device='cuda'); y16 = torch.empty_like(z16)
-    wsb, nb = ws(query('fte_conv2d_fwd_ws_bytes', n, h, w, cin, cout, 3, 1))
+    wsb, nb = ws(query('fte_conv2d_fwd_ws_bytes', n, h, w, cin, cout, k, 1))
     _lib.query('fte_prof_enable', 1)
     call('fte_conv2d_fwd_s16', x16, w16t, torch.from_numpy(b).cuda(), torch.from_numpy(al).cuda(), res16, z16, y16, None, None,
-         n, h, w, cin, cout, 3, 1, wsb, nb, stream())
+         n, h, w, cin, cout, k, 1, wsb, nb, stream())
     _lib.query('fte_prof_enable', 0)
     syms, splits = _records()
     b64, al64 = b.astype(np.float64), al.astype(np.float64)
@@ -165,13 +165,13 @@ def run_s16fwd(n, h, w, cin, cout, stride, r):
     return syms, splits, {'z_worst_over_limit': wz, 'y_worst_over_limit': wy}, ok
 
 
-def run_s16dgrad(n, h, w, cin, cout, stride, r):
+def run_s16dgrad(n, h, w, cin, cout, stride, r, k=3):
     """fte_conv2d_dgrad_s16 (bf16 dz / skip gradient / previous z in, bf16 raw / dz out, fp32 dalpha / dbias sums)"""
     assert stride == 1
-    wt = (r.standard_normal((3, 3, cin, cout), dtype=np.float32) * 0.05).astype(np.float32)
+    wt = (r.standard_normal((k, k, cin, cout), dtype=np.float32) * 0.05).astype(np.float32)
     wd = torch.from_numpy(wt).cuda()
-    w16 = torch.empty(3, 3, cin, cout, dtype=torch.int16, device='cuda'); w16t = torch.empty(3, 3, cout, cin, dtype=torch.int16, device='cuda')
-    call('fte_pack_weights_bf16', wd, w16, w16t, 3, cin, cout, stream())
+    w16 = torch.empty(k, k, cin, cout, dtype=torch.int16, device='cuda'); w16t = torch.empty(k, k, cout, cin, dtype=torch.int16, device='cuda')
+    call('fte_pack_weights_bf16', wd, w16, w16t, k, cin, cout, stream())
     wb = wd.bfloat16().float().cpu().numpy().astype(np.float64)
     dz, dz16 = _bf(r.standard_normal((n, h, w, cout), dtype=np.float32))
     addin, add16 = _bf(r.standard_normal((n, h, w, cin), dtype=np.float32))
@@ -181,9 +181,9 @@ def run_s16dgrad(n, h, w, cin, cout, stride, r):
     alp = (0.25 + 0.1 * r.standard_normal(cin, dtype=np.float32)).astype(np.float32)
     raw16 = torch.empty(n, h, w, cin, dtype=torch.int16, device='cuda'); dzp16 = torch.empty_like(raw16)
     da = torch.empty(cin, device='cuda'); db = torch.empty(cin, device='cuda')
-    wsb, nb = ws(query('fte_conv2d_dgrad_ws_bytes', n, h, w, cin, cout, 3, 1))
+    wsb, nb = ws(query('fte_conv2d_dgrad_ws_bytes', n, h, w, cin, cout, k, 1))
     _lib.query('fte_prof_enable', 1)
-    call('fte_conv2d_dgrad_s16', dz16, w16, add16, zp16, torch.from_numpy(alp).cuda(), raw16, dzp16, da, db, n, h, w, cin, cout, 3, 1, wsb, nb, stream())
+    call('fte_conv2d_dgrad_s16', dz16, w16, add16, zp16, torch.from_numpy(alp).cuda(), raw16, dzp16, da, db, n, h, w, cin, cout, k, 1, wsb, nb, stream())
     _lib.query('fte_prof_enable', 0)
     syms, splits = _records()
     al64 = alp.astype(np.float64)
@@ -249,7 +249,9 @@ def main():
     for ci, c in enumerate(cases):
         op, dims = c[0], [int(v) for v in c[1:]]
         r = np.random.default_rng(100 + ci)
-        syms, splits, errs, ok = {'fwd': run_fwd, 'dgrad': run_dgrad, 'wgrad': run_wgrad, 's16fwd': run_s16fwd, 's16dgrad': run_s16dgrad, 's16wgrad': run_s16wgrad, 's16wgrad1': run_s16wgrad1}[op](*dims, r)
+        syms, splits, errs, ok = {'fwd': run_fwd, 'dgrad': run_dgrad, 'wgrad': run_wgrad, 's16fwd': run_s16fwd, 's16dgrad': run_s16dgrad,
+                                  's16fwd1': lambda *a: run_s16fwd(*a, k=1), 's16dgrad1': lambda *a: run_s16dgrad(*a, k=1),
+                                  's16wgrad': run_s16wgrad, 's16wgrad1': run_s16wgrad1}[op](*dims, r)
         out.append({'case': c, 'symbols': syms, 'splits': splits, 'errors': errs, 'ok': bool(ok)})
         ok_all = ok_all and ok
         torch.cuda.empty_cache()

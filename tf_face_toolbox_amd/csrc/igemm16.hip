@@ -44,22 +44,13 @@ __device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t& r, char* lds
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds, 16, voff, soff, 0, 0);
 }
 
-template <class T>
-__device__ __forceinline__ void keep_alive(const T& v) {      // ablation builds: the value stays computed without being used
-    asm volatile("" ::"v"(v));
-}
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// ABL (diagnostic builds only, FTE_IGEMM16_ABL): 0 = the kernel; 1 = no MFMAs, 2 = no DMA (stale LDS), 3 = no epilogue, 4 = no
-// fragment reads (MFMAs on whatever the registers hold)
-// PF = 1: the fragments of sub-step ks + 1 are read while the MFMAs of sub-step ks run (register double buffer), and the scalar
-// loads of the next tile's tap offsets are taken before the barrier instead of between the fragment reads
 // (body shared by two kernel symbols: igemm16_kernel, and igemm16_bn_kernel = the same with the BN-fusion epilogue compiled in)
-template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW, int ABL, int PF, bool BNM>
+template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW, bool BNM>
 __device__ __forceinline__ void igemm16_body(const IgemmParams& p) {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     static_assert((WM * WN == 4 || WM * WN == 8) && TM >= 1 && TN >= 1 && NST >= 2, "4 or 8 waves");
@@ -149,11 +140,9 @@ __device__ __forceinline__ void igemm16_body(const IgemmParams& p) {
         const unsigned toff = (unsigned)((p.a_dh[tap0 + itap] * p.a_IW + p.a_dw[tap0 + itap]) * p.a_ld + ikc) * 2u;    // wave-uniform
         const unsigned boff = (unsigned)(p.b_tapoff[tap0 + itap] + ikc) * 2u;
 #pragma unroll
-        for (int i = 0; i < A_P; ++i)
-            if constexpr (ABL != 2) dma16(rsrcA, As + i * (RP * ROWB), ((a_mask[i] >> itap) & 1) ? a_base[i] + toff : OOB, 0);
+        for (int i = 0; i < A_P; ++i) dma16(rsrcA, As + i * (RP * ROWB), ((a_mask[i] >> itap) & 1) ? a_base[i] + toff : OOB, 0);
 #pragma unroll
-        for (int i = 0; i < B_P; ++i)
-            if constexpr (ABL != 2) dma16(rsrcB, Bs + i * (RP * ROWB), b_base[i], boff);
+        for (int i = 0; i < B_P; ++i) dma16(rsrcB, Bs + i * (RP * ROWB), b_base[i], boff);
         if (++itap == NT) { itap = 0; ikc += BK16; }
     };
 
@@ -190,54 +179,10 @@ __device__ __forceinline__ void igemm16_body(const IgemmParams& p) {
             bf16x8 fa[TM], fb[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
-                if constexpr (ABL != 4) fa[i] = *reinterpret_cast<const bf16x8*>(As + a_row[i] * ROWB + (((2 * ks + lh) ^ ((a_row[i] >> 1) & 7)) << 4));
-                else asm volatile("" : "=v"(fa[i]));
+                fa[i] = *reinterpret_cast<const bf16x8*>(As + a_row[i] * ROWB + (((2 * ks + lh) ^ ((a_row[i] >> 1) & 7)) << 4));
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-                if constexpr (ABL != 4) fb[j] = *reinterpret_cast<const bf16x8*>(Bs + b_row[j] * ROWB + (((2 * ks + lh) ^ ((b_row[j] >> 1) & 7)) << 4));
-                else asm volatile("" : "=v"(fb[j]));
-            if (fillnext) {
-#pragma unroll
-                for (int idx = 0; idx < L; ++idx) {
-                    if (idx * 4 / L != ks) continue;
-                    if constexpr (ABL != 2) {
-                        if (idx < A_P) dma16(rsrcA, Ad + idx * (RP * ROWB), ((a_mask[idx < A_P ? idx : 0] >> itap) & 1) ? a_base[idx < A_P ? idx : 0] + toff : OOB, 0);
-                        else dma16(rsrcB, Bd + (idx - A_P) * (RP * ROWB), b_base[idx >= A_P ? idx - A_P : 0], boff);
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    if constexpr (ABL != 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-                    else { keep_alive(fa[i]); keep_alive(fb[j]); }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (fillnext) {
-            if (++itap == NT) { itap = 0; ikc += BK16; }
-        }
-    };
-
-    // PF = 1: the same K-step with the fragment reads one sub-step ahead of their MFMAs
-    auto kstep_pf = [&](int stage, int fill, bool fillnext, unsigned toff, unsigned boff) {
-        const char* As = smem16 + stage * STAGE;
-        const char* Bs = As + BM * ROWB;
-        char* Ad = smem16 + fill * STAGE + wid * 1024;
-        char* Bd = Ad + BM * ROWB;
-        bf16x8 fa[2][TM], fb[2][TN];
-        auto ld = [&](int ks, int b) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                fa[b][i] = *reinterpret_cast<const bf16x8*>(As + a_row[i] * ROWB + (((2 * ks + lh) ^ ((a_row[i] >> 1) & 7)) << 4));
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[b][j] = *reinterpret_cast<const bf16x8*>(Bs + b_row[j] * ROWB + (((2 * ks + lh) ^ ((b_row[j] >> 1) & 7)) << 4));
-        };
-        ld(0, 0);
-#pragma unroll
-        for (int ks = 0; ks < BK16 / 16; ++ks) {
-            if (ks + 1 < BK16 / 16) ld(ks + 1, (ks + 1) & 1);
+                fb[j] = *reinterpret_cast<const bf16x8*>(Bs + b_row[j] * ROWB + (((2 * ks + lh) ^ ((b_row[j] >> 1) & 7)) << 4));
             if (fillnext) {
 #pragma unroll
                 for (int idx = 0; idx < L; ++idx) {
@@ -249,7 +194,7 @@ __device__ __forceinline__ void igemm16_body(const IgemmParams& p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks & 1][i], fb[ks & 1][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (fillnext) {
@@ -265,244 +210,25 @@ __device__ __forceinline__ void igemm16_body(const IgemmParams& p) {
         if (s < nk) issue(s);
     int stage = 0, fill = NST - 1;
     for (int t = 0; t < nk; ++t) {
-        unsigned toff = 0, boff = 0;
-        if constexpr (PF) {
-            if (t + NST - 1 < nk) {
-                toff = (unsigned)((p.a_dh[tap0 + itap] * p.a_IW + p.a_dw[tap0 + itap]) * p.a_ld + ikc) * 2u;    // wave-uniform
-                boff = (unsigned)(p.b_tapoff[tap0 + itap] + ikc) * 2u;
-            }
-            asm volatile("" : "+s"(toff), "+s"(boff));               // the scalar loads complete here, under the wait for the tile
-        }
         if (t + NST - 1 <= nk) wait_vmcnt<(NST - 2) * L>();          // steady state: the NST - 2 younger tiles stay in flight
         else wait_vmcnt<0>();                                        // last steps: fewer tiles are outstanding
         __builtin_amdgcn_s_barrier();
-        if constexpr (PF) kstep_pf(stage, fill, t + NST - 1 < nk, toff, boff);
-        else kstep(stage, fill, t + NST - 1 < nk);
+        kstep(stage, fill, t + NST - 1 < nk);
         stage = stage + 1 == NST ? 0 : stage + 1;
         fill = fill + 1 == NST ? 0 : fill + 1;
     }
     wait_vmcnt<0>();
     __syncthreads();                       // the epilogue reuses the LDS
-    if constexpr (ABL == 3) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) keep_alive(acc[i][j][r]);
-        return;
-    }
     igemm_epilogue<BM, BN, WM, WN, EPI, true, BNM>(p, acc, reinterpret_cast<float*>(smem16), bid, split, m0, n0, mt, c_ph, c_pw, prow);
 }
-template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW, int ABL = 0, int PF = 0>
+template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW>
 __global__ __launch_bounds__(64 * WM * WN, MINW) void igemm16_kernel(const IgemmParams p) {
-    igemm16_body<BM, BN, WM, WN, EPI, NST, MINW, ABL, PF, false>(p);
+    igemm16_body<BM, BN, WM, WN, EPI, NST, MINW, false>(p);
 }
 // conv -> BN pairs of the graph nets (igemm.h "BN fusion")
 template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW>
 __global__ __launch_bounds__(64 * WM * WN, MINW) void igemm16_bn_kernel(const IgemmParams p) {
-    igemm16_body<BM, BN, WM, WN, EPI, NST, MINW, 0, 0, true>(p);
-}
-
-// ---- window variant (3x3, stride 1, TF-SAME; W <= 30): the A operand of a 64-channel chunk is fetched ONCE per tile -------------
-// In linear pixel space the source row of (output row m, tap (dh, dw)) is m + dh * W + dw wherever it lies inside the image, so
-// the nine taps of a chunk are row-shifted views of the BM + 2 W + 2 rows [m0 - W - 1, m0 + BM + W]: that window is DMA'd once
-// per chunk (two buffers: the next chunk's window arrives one piece per K-step under the current chunk's taps), a tap's fragment
-// is the row li + W + 1 + dh W + dw of it, and the image edges are a 9-bit mask per lane that zeroes the fragment.  igemm16_kernel
-// re-fetches the A tile for every (tap, chunk): 16 of the 32 LDS-DMA pieces of a K-step; here 16 (B) + 24 / 9 (window).
-__device__ __forceinline__ void wait_vmcnt_dyn(int n) {           // s_waitcnt takes an immediate: n is wave-uniform and small
-    switch (n) {
-        case 0: wait_vmcnt<0>(); break;   case 1: wait_vmcnt<1>(); break;   case 2: wait_vmcnt<2>(); break;
-        case 3: wait_vmcnt<3>(); break;   case 4: wait_vmcnt<4>(); break;   case 5: wait_vmcnt<5>(); break;
-        case 6: wait_vmcnt<6>(); break;   case 7: wait_vmcnt<7>(); break;   case 8: wait_vmcnt<8>(); break;
-        case 9: wait_vmcnt<9>(); break;   case 10: wait_vmcnt<10>(); break; case 11: wait_vmcnt<11>(); break;
-        default: wait_vmcnt<12>(); break;
-    }
-}
-// NSTB = stages of the B ring (NSTB - 1 K-steps of B in flight)
-template <int BM, int BN, int WM, int WN, int EPI, int MINW, int NSTB = 2>
-__global__ __launch_bounds__(64 * WM * WN, MINW) void igemm16w_kernel(const IgemmParams p) {
-    constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    static_assert((WM * WN == 4 || WM * WN == 8 || WM * WN == 16) && TM >= 1 && TN >= 1 && NSTB >= 2 && NSTB <= 4, "4, 8 or 16 waves");
-    constexpr int NW = WM * WN, RP = 8 * NW, B_P = BN / RP, BSTAGE = BN * ROWB, MAXWP = (24 + NW - 1) / NW;
-    static_assert(BN % RP == 0, "tile rows per DMA pass");
-    extern __shared__ __attribute__((aligned(16))) char smem16[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wid / WN, wn = wid % WN;
-    const int li = lane & 31, lh = lane >> 5;
-
-    const int ntn = p.N / BN;
-    int bid = blockIdx.x;
-    const int split = blockIdx.y;
-    {
-        const int ntiles = gridDim.x;
-        const int q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7, loc = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
-    const int NT = p.a_NT;
-    const int mt = bid / ntn, nt_ = bid - mt * ntn;
-    const int m0 = p.m_base + mt * BM, n0 = nt_ * BN;
-    const int kbeg = split * p.kchunk;
-    const int kend = min(p.K, kbeg + p.kchunk);
-    const int nk = (kend - kbeg) / BK16;
-    const int Wd = p.a_IW;
-    const int NR = BM + 2 * Wd + 2;                     // window rows
-    const int NPC = (NR + 7) >> 3;                      // 1-KiB DMA pieces per window
-    const int WINB = NPC * 1024;
-    char* const win = smem16;
-    char* const bring = smem16 + 2 * WINB;
-
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.B), 0, p.b_bytes, 0x00020000);
-
-    // window pieces of this wave: wid, wid + 4, ...; a lane owns row 8 piece + (lane >> 3), LDS slot lane & 7 = source chunk ^ ((row >> 1) & 7)
-    unsigned w_off[MAXWP];
-#pragma unroll
-    for (int i = 0; i < MAXWP; ++i) {
-        const int r = (wid + NW * i) * 8 + (lane >> 3);
-        const int g = m0 - Wd - 1 + r;
-        const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-        w_off[i] = (r < NR && g >= 0 && g < p.M) ? (unsigned)(g * p.a_ld + (chunk << 3)) * 2u : OOB;
-    }
-    unsigned b_base[B_P];
-#pragma unroll
-    for (int i = 0; i < B_P; ++i) {
-        const int r = (tid >> 3) + RP * i;
-        const int chunk = (tid & 7) ^ ((r >> 1) & 7);
-        b_base[i] = (unsigned)((n0 + r) * p.b_ld + (chunk << 3)) * 2u;
-    }
-    auto issueW = [&](int buf, int chunk, int i) {
-        if (wid + NW * i < NPC) dma16(rsrcA, win + buf * WINB + (wid + NW * i) * 1024, w_off[i], (unsigned)chunk * (BK16 * 2));
-    };
-
-    // fragment rows and their tap masks
-    int a_row[TM], fmask[TM], b_row[TN];
-    {
-        const int a_hw = p.a_OH * p.a_OW;
-        const float r_ahw = 1.f / (float)a_hw, r_aow = 1.f / (float)p.a_OW;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            a_row[i] = wm * (TM * 32) + i * 32 + li;
-            const int m = m0 + a_row[i];
-            int mask = 0;
-            if (m < p.M) {
-                const int n = fdiv(m, a_hw, r_ahw), rem = m - n * a_hw;
-                const int oh = fdiv(rem, p.a_OW, r_aow), ow = rem - oh * p.a_OW;
-                for (int t = 0; t < NT; ++t) {
-                    const int ih = oh + p.a_dh[t], iw = ow + p.a_dw[t];
-                    if (ih >= 0 && ih < p.a_IH && iw >= 0 && iw < p.a_IW) mask |= 1 << t;
-                }
-            }
-            fmask[i] = mask;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) b_row[j] = wn * (TN * 32) + j * 32 + li;
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // K-step sigma = chunk * NT + tap (chunk outer, tap inner)
-    const int s_first = kbeg / BK16;
-    int ctap = s_first % NT, cchunk = s_first / NT;
-    const int last_chunk = (s_first + nk - 1) / NT;
-    int wnext = 0;                                       // pieces of the NEXT chunk's window issued so far (per wave)
-    int itap = ctap, ichunk = cchunk;                    // the step whose B tile is issued next
-    auto issueB = [&](int stage) {
-        const unsigned boff = (unsigned)(p.b_tapoff[itap] + ichunk * BK16) * 2u;
-#pragma unroll
-        for (int i = 0; i < B_P; ++i) dma16(rsrcB, bring + stage * BSTAGE + wid * 1024 + i * (RP * ROWB), b_base[i], boff);
-        if (++itap == NT) { itap = 0; ++ichunk; }
-    };
-    if (nk > 0) {
-#pragma unroll
-        for (int i = 0; i < MAXWP; ++i) issueW(cchunk & 1, cchunk, i);
-#pragma unroll
-        for (int s2 = 0; s2 < NSTB - 1; ++s2)
-            if (s2 < nk) issueB(s2);
-    }
-    // DMAs retire in order.  Issued per step s, in this order: the B tile of step s + NSTB - 1, then (at most) one piece of the next
-    // chunk's window.  Step t needs its own B tile (issued in step t - NSTB + 1) and every older piece; everything issued in steps
-    // t - NSTB + 2 .. t - 1 -- and the window piece of step t - NSTB + 1 -- may stay in flight.
-    int wq[NSTB];                                        // window pieces issued at the end of the last NSTB - 1 steps (wq[0] = oldest)
-#pragma unroll
-    for (int i = 0; i < NSTB; ++i) wq[i] = 0;
-    int stage = 0, fill = NSTB - 1;
-    for (int t = 0; t < nk; ++t) {
-        {
-            int allowed = 0;
-#pragma unroll
-            for (int i = 0; i < NSTB - 1; ++i) allowed += wq[i];
-            const int btiles = min(NSTB - 2, nk - 1 - t);                  // younger B tiles in flight (fewer near the end)
-            allowed += (btiles > 0 ? btiles : 0) * B_P;
-            wait_vmcnt_dyn(allowed);
-        }
-        __builtin_amdgcn_s_barrier();
-        const char* Aw = win + (cchunk & 1) * WINB;
-        const char* Bs = bring + stage * BSTAGE;
-        int ntap = ctap + 1, nchunk = cchunk;
-        if (ntap == NT) { ntap = 0; ++nchunk; }
-        const bool fillnext = t + NSTB - 1 < nk;
-        char* Bd = bring + fill * BSTAGE + wid * 1024;
-        const unsigned boff = fillnext ? (unsigned)(p.b_tapoff[itap] + ichunk * BK16) * 2u : 0u;
-        const int offt = Wd + 1 + p.a_dh[ctap] * Wd + p.a_dw[ctap];          // wave-uniform
-#pragma unroll
-        for (int ks = 0; ks < BK16 / 16; ++ks) {
-            bf16x8 fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int wr = a_row[i] + offt;
-                const bf16x8 v = *reinterpret_cast<const bf16x8*>(Aw + wr * ROWB + (((2 * ks + lh) ^ ((wr >> 1) & 7)) << 4));
-                const bool ok = (fmask[i] >> ctap) & 1;
-                const u32x4 raw = __builtin_bit_cast(u32x4, v);
-                fa[i] = __builtin_bit_cast(bf16x8, ok ? raw : u32x4{0u, 0u, 0u, 0u});
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[j] = *reinterpret_cast<const bf16x8*>(Bs + b_row[j] * ROWB + (((2 * ks + lh) ^ ((b_row[j] >> 1) & 7)) << 4));
-            if (fillnext) {
-#pragma unroll
-                for (int idx = 0; idx < B_P; ++idx)
-                    if (idx * 4 / B_P == ks) dma16(rsrcB, Bd + idx * (RP * ROWB), b_base[idx], boff);
-            }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (fillnext && ++itap == NT) { itap = 0; ++ichunk; }
-        // window of the next chunk: one piece per step, issued after this step's B pieces; whatever is left on the chunk's last step
-        int wlast = 0;
-        if (cchunk < last_chunk) {
-            const int want = (ctap == NT - 1) ? MAXWP : min(MAXWP, wnext + 1);
-            for (; wnext < want; ++wnext) {
-                if (wid + NW * wnext < NPC) ++wlast;                 // pieces actually issued (a short window has fewer than MAXWP per wave)
-#pragma unroll
-                for (int i = 0; i < MAXWP; ++i)
-                    if (i == wnext) issueW((cchunk + 1) & 1, cchunk + 1, i);
-            }
-        }
-        if (ntap == 0) wnext = 0;
-        ctap = ntap; cchunk = nchunk;
-#pragma unroll
-        for (int i = 0; i + 1 < NSTB - 1; ++i) wq[i] = wq[i + 1];
-        wq[NSTB - 2] = wlast;
-        stage = stage + 1 == NSTB ? 0 : stage + 1;
-        fill = fill + 1 == NSTB ? 0 : fill + 1;
-    }
-    wait_vmcnt<0>();
-    __syncthreads();
-    igemm_epilogue<BM, BN, WM, WN, EPI, true>(p, acc, reinterpret_cast<float*>(smem16), bid, split, m0, n0, mt, p.c_ph, p.c_pw, p.prow0);
+    igemm16_body<BM, BN, WM, WN, EPI, NST, MINW, true>(p);
 }
 
 // ---- persistent variant ------------------------------------------------------------------------------------------------------
@@ -526,7 +252,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
     return t;
 }
-// ---- epilogue of the swapped-operand kernels (igemm16p / igemm16r / igemm16rw): accumulator lane = output row, registers = columns ----
+// ---- epilogue of the swapped-operand kernels (igemm16p / igemm16rw): accumulator lane = output row, registers = columns ----
 // acc[i][j][r] of lane (li, lh): output row m0 + wm*TM*32 + i*32 + li (its offset: roff[i], < 0 beyond M), column n0 + wn*TN*32 + j*32 +
 // (r & 3) + 8 (r >> 2) + 4 lh.  v_permlane32_swap between the half-waves gives every lane 8 consecutive columns -- 16 bytes of a bf16 row
 // per load / store; no LDS patches.  These kernels only take bf16-STORAGE launches (launch16p_ok): the tensors of the epilogue are the
@@ -793,8 +519,7 @@ __device__ __forceinline__ int epilogue_rows(const EpiPtrs& ep, f32x16 (&acc)[BM
 // the epilogue then covers 8 rows x 128 contiguous bytes, and the half-wave exchange is gone.  Unit k = rows 8k .. 8k + 7 of the wave.
 // dalpha / dbias: a lane sums its eight columns over every unit (and over the tiles of a resident block, `carry`); the lanes of a
 // column meet (xor 8, 16, 32) only when the partial rows are written.
-// stg: this wave's STG x 256 bytes.  With KS = 2 they lie in the half of the B ring the last interval read (free until the loaders
-// pass the next tile's first barrier; the caller holds a block barrier between the last K-step and this function).
+// stg: this wave's STG x 256 bytes of LDS (beside the B ring).
 template <int BM, int BN, int WM, int WN, int EPI, int STG>
 __device__ __forceinline__ void epilogue_staged(const EpiPtrs& ep, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], char* stg, long base, int m_wave,
                                                 u32x4 (&ein0)[BM / WM / 8], u32x4 (&ein1)[BM / WM / 8], const float* colf, float* red,
@@ -1294,357 +1019,11 @@ hipError_t launch16p(const IgemmParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-// ---- ring variant with loader waves -----------------------------------------------------------------------------------------
-// What the stamped builds of igemm16p say (FTE_IGEMM16_STAMP, 14x14x256 at batch 512): a K-step of a block lasts ~1850-2000 cycles for
-// 256 cycles of MFMA per wave; the same with a four-stage ring, with one block per CU, with 44 % of the DMAs left out.  The MFMA pipe
-// and the LDS-DMA path are far from their limits (scripts/probes/lds_dma_vs_read.hip: 116 GB/s of DMA per CU BESIDE 93 % of the MFMA
-// peak, in different waves) -- what costs is a wave doing everything in turn: fragment reads it must wait for, two MFMAs, a DMA
-// instruction that holds the wave while the address path takes it, a wait for the landing, a barrier.  So the roles are split:
-//   * NLW loader waves only move tiles: per K-step each issues its share of the stage's 1-KiB pieces NST - 1 steps ahead (across tile
-//     boundaries), waits with a counted vmcnt for the stage the consumers need next, and meets them at the ONE barrier of the step;
-//   * WM x WN consumer waves (wave tile 64 x 64: four MFMAs per 16-deep sub-step, half the LDS fragment bytes per MFMA of the 32 x 64
-//     tile) only read fragments (PFD sub-steps ahead) and issue MFMAs; their epilogue is epilogue_rows, during which the loaders
-//     are already filling the ring for the next tile.
-// One block per CU (a 256 x 128 tile's three stages are 144 KB), three waves per SIMD.
-template <int BM, int BN, int WM, int WN, int EPI, int NST, int NLW, int PFD, int DBG = 0>
-__global__ __launch_bounds__(64 * (WM * WN + NLW), 1) void igemm16r_kernel(const IgemmParams p) {
-    constexpr int TM = BM / WM / 32, TN = BN / WN / 32, NCW = WM * WN;
-    constexpr int KA = BM / 8 / NLW, KB = BN / 8 / NLW, PPL = KA + KB;      // 1-KiB pieces (8 rows x 128 B) per loader wave and K-step
-    static_assert((BM / 8) % NLW == 0 && (BN / 8) % NLW == 0 && NST >= 3 && NST <= 4 && PFD >= 1 && PFD <= 3, "pieces per loader");
-    constexpr int STAGE = (BM + BN) * ROWB;
-    constexpr int NQ = NST - 2;
-    extern __shared__ __attribute__((aligned(16))) char smem16[];
-    float* const colf2 = reinterpret_cast<float*>(smem16 + NST * STAGE);   // [2][2][BN]: alpha, bias of the tile's columns, double-buffered
-    float* const red = colf2 + 4 * BN;                                     // [2][WM][BN]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    const int ntn = p.N / BN;
-    const int xcd = blockIdx.x & 7, per = gridDim.x >> 3;
-    const int q8 = p.ptiles >> 3, r8 = p.ptiles & 7;
-    const int xbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcnt = q8 + (xcd < r8 ? 1 : 0);
-    int idx = blockIdx.x >> 3;
-    if (idx >= xcnt) return;
-    const int NT = p.a_NT, nk = p.K / BK16;
-    const bool epi_barrier = EPI == EPI_DGRAD && p.PA != nullptr;
-    unsigned long long* const stamps = DBG ? reinterpret_cast<unsigned long long*>(p.PW) : nullptr;
-    int dbg_step = 0;
-
-    if (wid >= NCW) {
-        // =================================================== loader wave ===================================================
-        const int lw = wid - NCW;
-        constexpr unsigned OOB = 0x80000000u;
-        const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, p.a_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.B), 0, p.b_bytes, 0x00020000);
-        const int a_hw = p.a_OH * p.a_OW;
-        const float r_ahw = 1.f / (float)a_hw, r_aow = 1.f / (float)p.a_OW;
-        int tapA = 0, tapB = 0;                 // byte offsets of the taps, one per lane (v_readlane instead of dependent scalar loads)
-        if (lane < NT) {
-            tapA = ((p.a_dh[lane] * p.a_IW + p.a_dw[lane]) * p.a_ld) * 2;
-            tapB = p.b_tapoff[lane] * 2;
-        }
-        unsigned a_base[KA], b_base[KB];
-        int a_mask[KA];
-        // piece k of this wave = piece lw + NLW k of the stage: rows 8 (lw + NLW k) + (lane >> 3); k < KA: A rows, else B rows
-        auto setup = [&](int tile) {
-            const int mt = tile / ntn, nt_ = tile - mt * ntn;
-            const int m0 = p.m_base + mt * BM, n0 = nt_ * BN;
-#pragma unroll
-            for (int k = 0; k < KA; ++k) {
-                const int r = 8 * (lw + NLW * k) + (lane >> 3);
-                const int m = m0 + r;
-                int base = 0, mask = 0;
-                if (m < p.M) {
-                    const int n = fdiv(m, a_hw, r_ahw), rem = m - n * a_hw;
-                    const int oh = fdiv(rem, p.a_OW, r_aow), ow = rem - oh * p.a_OW;
-                    const int ih0 = oh * p.a_stride, iw0 = ow * p.a_stride;
-                    base = ((n * p.a_IH + ih0) * p.a_IW + iw0) * p.a_ld;
-                    for (int t = 0; t < NT; ++t) {
-                        const int ih = ih0 + p.a_dh[t], iw = iw0 + p.a_dw[t];
-                        if (ih >= 0 && ih < p.a_IH && iw >= 0 && iw < p.a_IW) mask |= 1 << t;
-                    }
-                }
-                const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-                a_base[k] = (unsigned)(base + (chunk << 3)) * 2u;
-                a_mask[k] = mask;
-            }
-#pragma unroll
-            for (int k = 0; k < KB; ++k) {
-                const int r = 8 * (lw + NLW * k) + (lane >> 3);
-                const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-                b_base[k] = (unsigned)((n0 + r) * p.b_ld + (chunk << 3)) * 2u;
-            }
-        };
-        int itap = 0, ikc = 0;
-        auto issue = [&](int stage) {
-            char* As = smem16 + stage * STAGE + lw * 1024;
-            char* Bs = As + BM * ROWB;
-            const unsigned toff = (unsigned)(__builtin_amdgcn_readlane(tapA, itap) + ikc * 2);
-            const unsigned boff = (unsigned)(__builtin_amdgcn_readlane(tapB, itap) + ikc * 2);
-#pragma unroll
-            for (int k = 0; k < KA; ++k) dma16(rsrcA, As + k * (NLW * 1024), ((a_mask[k] >> itap) & 1) ? a_base[k] + toff : OOB, 0);
-#pragma unroll
-            for (int k = 0; k < KB; ++k) dma16(rsrcB, Bs + k * (NLW * 1024), b_base[k], boff);
-            if (++itap == NT) { itap = 0; ikc += BK16; }
-        };
-        setup(xbase + idx);
-#pragma unroll
-        for (int s0 = 0; s0 < NST - 1; ++s0) issue(s0);
-        int qn[NQ];
-#pragma unroll
-        for (int k = 0; k < NQ; ++k) qn[k] = PPL;
-        int stage = 0;
-        for (;;) {
-            const int nidx = idx + per;
-            const bool hasnext = nidx < xcnt;
-            for (int t = 0; t < nk; ++t) {
-                const bool fillnext = t + NST - 1 < nk || hasnext;
-                if (t + NST - 1 == nk && hasnext) { setup(xbase + nidx); itap = 0; ikc = 0; }
-                unsigned long long st0 = 0, st1 = 0, st2 = 0;
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); st0 = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
-                {
-                    int allowed = 0;
-#pragma unroll
-                    for (int k = 0; k < NQ; ++k) allowed += qn[k];
-                    wait_vmcnt_upto(allowed);
-                }
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); st1 = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
-                __builtin_amdgcn_s_barrier();
-                if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); st2 = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
-                if (fillnext) issue(stage == 0 ? NST - 1 : stage - 1);                  // the stage the consumers read in the previous K-step
-                if constexpr (DBG) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    const unsigned long long st3 = stamp_now();
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (blockIdx.x == 0 && lw == 0 && dbg_step < 80 && lane == 0) {
-                        unsigned long long* o = stamps + (1 * 80 + dbg_step) * 4;
-                        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3;
-                    }
-                    ++dbg_step;
-                }
-                stage = stage + 1 == NST ? 0 : stage + 1;
-#pragma unroll
-                for (int k = 0; k + 1 < NQ; ++k) qn[k] = qn[k + 1];
-                qn[NQ - 1] = fillnext ? PPL : 0;
-            }
-            if (epi_barrier) __builtin_amdgcn_s_barrier();           // the consumers' epilogue holds one block barrier
-            if (!hasnext) break;
-            idx = nidx;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        return;
-    }
-
-    // ===================================================== consumer wave =====================================================
-    const int wm = wid / WN, wn = wid % WN;
-    const int li = lane & 31, lh = lane >> 5;
-    f32x16 acc[TM][TN];
-    int a_row[TM], b_row[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) a_row[i] = wm * (TM * 32) + i * 32 + li;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) b_row[j] = wn * (TN * 32) + j * 32 + li;
-    auto kstep = [&](int stage) {
-        const char* As = smem16 + stage * STAGE;
-        const char* Bs = As + BM * ROWB;
-        constexpr int NB = PFD + 1;
-        bf16x8 fa[NB][TM], fb[NB][TN];
-        auto ld = [&](int ks, int b) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                fa[b][i] = *reinterpret_cast<const bf16x8*>(As + a_row[i] * ROWB + (((2 * ks + lh) ^ ((a_row[i] >> 1) & 7)) << 4));
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                fb[b][j] = *reinterpret_cast<const bf16x8*>(Bs + b_row[j] * ROWB + (((2 * ks + lh) ^ ((b_row[j] >> 1) & 7)) << 4));
-        };
-#pragma unroll
-        for (int k0 = 0; k0 < PFD; ++k0) ld(k0, k0);
-#pragma unroll
-        for (int ks = 0; ks < BK16 / 16; ++ks) {
-            if (ks + PFD < BK16 / 16) ld(ks + PFD, (ks + PFD) % NB);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks % NB][j], fa[ks % NB][i], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    const bool in16 = EPI == EPI_FWD ? p.R16 != nullptr : (p.ADD16 != nullptr || p.Zin16 != nullptr);
-    const EpiPtrs ep = epi_ptrs<EPI>(p);
-    int stage = 0, kt = 0, n0_colf = -1;
-    for (;;) {
-        const int tile = xbase + idx;
-        const int mt = tile / ntn, nt_ = tile - mt * ntn;
-        const int m0 = p.m_base + mt * BM, n0 = nt_ * BN;
-        const int nidx = idx + per;
-        const bool hasnext = nidx < xcnt;
-        if (n0 != n0_colf) ++kt;                       // a new column tile: the other half of colf2
-        float* const colf = colf2 + (kt & 1) * 2 * BN;
-        int roff[TM];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + wm * (TM * 32) + i * 32 + li;
-            int off = -1;
-            if (m < p.M) {
-                if (p.c_OH == 0) {
-                    off = m * p.c_ld;
-                } else {
-                    const int hw = p.c_OH * p.c_OW;
-                    const int n = fdiv(m, hw, 1.f / (float)hw), rem = m - n * hw;
-                    const int oh = fdiv(rem, p.c_OW, 1.f / (float)p.c_OW), ow = rem - oh * p.c_OW;
-                    off = ((n * p.c_FH + oh * p.c_step + p.c_ph) * p.c_FW + ow * p.c_step + p.c_pw) * p.c_ld;
-                }
-            }
-            roff[i] = off;
-        }
-        // alpha / bias of the tile's columns -> this tile's half of colf2 (read in the epilogue, nk barriers later; the other half
-        // may still be read by waves in the previous tile's epilogue)
-        // (only when the column tile changes -- with an even block stride it never does: a load here waits, vmcnt being in order, for
-        // every store of the previous tile's epilogue to drain)
-        if (n0 != n0_colf) {
-            for (int c = tid; c < BN; c += 64 * NCW) {
-                float al = 1.f, bi = 0.f;
-                if constexpr (EPI == EPI_FWD) {
-                    if (p.alpha) al = p.alpha[n0 + c];
-                    if (p.bias) bi = p.bias[n0 + c];
-                } else {
-                    if (p.alpha) al = p.alpha[(n0 + c) % p.amod];
-                }
-                colf[c] = al;
-                colf[BN + c] = bi;
-            }
-            n0_colf = n0;
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        u32x4 ein0[TM][TN][2], ein1[TM][TN][2];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) { ein0[i][j][q] = u32x4{0u, 0u, 0u, 0u}; ein1[i][j][q] = u32x4{0u, 0u, 0u, 0u}; }
-
-        for (int t = 0; t < nk; ++t) {
-            unsigned long long st0 = 0, st1 = 0;
-            if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); st0 = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
-            __builtin_amdgcn_s_barrier();
-            if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); st1 = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
-            if (t == nk - 1 && in16) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const long o = (long)(roff[i] < 0 ? 0 : roff[i]) + n0 + wn * (TN * 32) + j * 32 + 16 * q + 8 * lh;
-                            if constexpr (EPI == EPI_FWD) {
-                                if (ep.i0) ein0[i][j][q] = *(g_cu32x4*)(ep.i0 + o);
-                            } else {
-                                if (ep.i0) ein0[i][j][q] = *(g_cu32x4*)(ep.i0 + o);
-                                if (ep.i1) ein1[i][j][q] = *(g_cu32x4*)(ep.i1 + o);
-                            }
-                        }
-            }
-            kstep(stage);
-            if constexpr (DBG) {
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long st2 = stamp_now();
-                __builtin_amdgcn_sched_barrier(0);
-                if (blockIdx.x == 0 && wid == 0 && dbg_step < 80 && lane == 0) {
-                    unsigned long long* o = stamps + (0 * 80 + dbg_step) * 4;
-                    o[0] = st0; o[1] = st1; o[2] = st2; o[3] = 0;
-                }
-                ++dbg_step;
-            }
-            stage = stage + 1 == NST ? 0 : stage + 1;
-        }
-        epilogue_rows<BM, BN, WM, WN, EPI>(ep, acc, roff, ein0, ein1, colf, red, mt, n0, tid, wm, wn, li, lh);
-        if (!hasnext) break;
-        idx = nidx;
-    }
-}
-
-template <int BM, int BN, int WM, int WN, int EPI, int NST, int NLW, int PFD>
-hipError_t launch16r(const IgemmParams& p, hipStream_t st) {
-    const int mt = (p.M - p.m_base + BM - 1) / BM, nt = p.N / BN;
-    IgemmParams q = p;
-    q.ptiles = mt * nt;
-    q.ptiles_dbg = 0;
-    const size_t lds = (size_t)NST * (BM + BN) * ROWB + (size_t)(4 * BN + 2 * WM * BN) * sizeof(float);
-    auto kern = igemm16r_kernel<BM, BN, WM, WN, EPI, NST, NLW, PFD>;
-    if (igemm_prof_on()) { const int ta[9] = {BM, BN, WM, WN, EPI, NST, NLW, PFD, 0}; igemm_note_symbol("igemm16r_kernel", ta, 9); }
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
-    const int per_xcd = cus / 8;                                       // one block per CU
-    const int need = (q.ptiles + 7) / 8;
-    const int grid = 8 * (need < per_xcd ? need : per_xcd);
-    constexpr int THREADS = 64 * (WM * WN + NLW);
-    static const bool stamps = getenv("FTE_IGEMM16_STAMP") != nullptr;
-    if (stamps) {              // diagnostic: the stamped build, its table on stderr
-        auto dk = igemm16r_kernel<BM, BN, WM, WN, EPI, NST, NLW, PFD, 1>;
-        static unsigned long long* buf = nullptr;
-        const size_t nb = 2 * 80 * 4 * sizeof(unsigned long long);
-        if (!buf) {
-            if (hipMalloc(&buf, nb) != hipSuccess) return hipErrorOutOfMemory;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        (void)hipMemsetAsync(buf, 0, nb, st);
-        q.PW = reinterpret_cast<float*>(buf);
-        hipLaunchKernelGGL(dk, dim3(grid), dim3(THREADS), lds, st, q);
-        (void)hipStreamSynchronize(st);
-        static unsigned long long host[2 * 80 * 4];
-        (void)hipMemcpy(host, buf, nb, hipMemcpyDeviceToHost);
-        const int nk = q.K / BK16;
-        fprintf(stderr, "[stamp] igemm16r<%d,%d,%d,%d,%d,%d,%d,%d> M %d N %d K %d tiles %d grid %d\n", BM, BN, WM, WN, EPI, NST, NLW, PFD, q.M, q.N, q.K, q.ptiles, grid);
-        {
-            const unsigned long long* h = host;
-            double sb = 0, sk = 0, sp = 0; int n = 0;
-            for (int i = 4; i < nk && i < 80; ++i) {
-                if (!h[i * 4]) break;
-                sb += (double)(h[i * 4 + 1] - h[i * 4]); sk += (double)(h[i * 4 + 2] - h[i * 4 + 1]); sp += (double)(h[i * 4] - h[(i - 1) * 4]); ++n;
-            }
-            if (n) fprintf(stderr, "[stamp]  consumer wave 0: per K-step period %.0f = barrier %.0f + body %.0f + rest\n", sp / n, sb / n, sk / n);
-            if (nk < 80 && h[nk * 4]) fprintf(stderr, "[stamp]   tile 0 -> 1: last body end to next barrier entry %.0f ticks (epilogue), tile 0 K loop %.0f\n",
-                                              (double)(h[nk * 4] - h[(nk - 1) * 4 + 2]), (double)(h[(nk - 1) * 4 + 2] - h[0]));
-            h = host + 80 * 4;
-            double sw = 0, sbb = 0, si = 0; sp = 0; n = 0;
-            for (int i = 4; i < nk && i < 80; ++i) {
-                if (!h[i * 4]) break;
-                sw += (double)(h[i * 4 + 1] - h[i * 4]); sbb += (double)(h[i * 4 + 2] - h[i * 4 + 1]); si += (double)(h[i * 4 + 3] - h[i * 4 + 2]);
-                sp += (double)(h[i * 4] - h[(i - 1) * 4]); ++n;
-            }
-            if (n) fprintf(stderr, "[stamp]  loader wave 0:   per K-step period %.0f = vmcnt wait %.0f + barrier %.0f + issue %.0f + rest\n", sp / n, sw / n, sbb / n, si / n);
-        }
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, st, q);
-    return hipGetLastError();
-}
-
 // ---- loader waves + A WINDOW (3x3, stride 1, TF-SAME) -------------------------------------------------------------------------
-// igemm16r moves (BM + BN) x 128 bytes per K-step and its loaders are what the consumers wait for (stamped: 1000 of the 2000 cycles
-// of a K-step at the barrier; 12 pieces per loader and step at the address path's ~90 cycles each).  For a 3x3 / stride-1 layer the
-// nine taps of a 64-channel chunk read row-shifted views of the same pixels, so the A operand is fetched ONCE per chunk:
+// With loader waves that move (BM + BN) x 128 bytes per K-step (igemm16r, retired) the loaders are what the consumers wait for
+// (stamped: 1000 of the 2000 cycles of a K-step at the barrier; 12 pieces per loader and step at the address path's ~90 cycles each).
+// For a 3x3 / stride-1 layer the nine taps of a 64-channel chunk read row-shifted views of the same pixels, so the A operand is
+// fetched ONCE per chunk:
 //   * pixels live in LDS at PADDED slots -- slot(img, y, x) = img (H+1)(W+1) + (y+1)(W+1) + x + 1: one zero slot ahead of every image
 //     row and one zero row ahead of every image, which is all the padding the eight neighbours ever touch -- so tap (dh, dw) of an
 //     output pixel is slot + dh (W+1) + dw for EVERY pixel: no edge masks in the MFMA loop (the zero slots are LDS-DMA'd from an
@@ -1660,7 +1039,7 @@ hipError_t launch16r(const IgemmParams& p, hipStream_t st) {
 // K-step the two consumer waves of a SIMD fill the MFMA pipe for ~1050, the rest is the barrier -- waiting for the slowest of twelve
 // waves -- and loop overhead): four B stages, consumers run two K-steps (32 MFMAs per wave) between barriers, loaders fill the
 // other two stages meanwhile; the window shrinks to the layers' real need (WCAP = 45) to make room in the 160 KB.
-// STG = rows per pass of the row-coalesced epilogue (epilogue_staged; 0 = the register epilogue epilogue_rows)
+// STG = rows per pass of the row-coalesced epilogue (epilogue_staged, KS = 1 only; 0 = the register epilogue epilogue_rows)
 template <int BM, int BN, int WM, int WN, int EPI, int NLW, int PFD, int WCAP, int KS = 1, int STG = 0, int DBG = 0>
 __global__ __launch_bounds__(64 * (WM * WN + NLW), 1) void igemm16rw_kernel(const IgemmParams p) {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32, NCW = WM * WN, NSTB = KS == 1 ? 3 : 2 * KS;
@@ -1668,12 +1047,13 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW), 1) void igemm16rw_kernel(cons
     constexpr int KW = (WCAP + NLW - 1) / NLW;          // window pieces (8 slots x 128 B) per loader wave; WCAP = the window's capacity
     constexpr int WPS = KS == 1 ? (KW + 5) / 6 : (KW + 2) / 3;      // window pieces a loader issues per barrier interval: all of them early in a chunk
     static_assert((BN / 8) % NLW == 0 && (KS == 1 || KS == 2) && (KS == 2 || (KW + WPS - 1) / WPS <= 9 - NSTB), "pieces per loader");
+    static_assert(STG == 0 || KS == 1, "the staged epilogue has LDS of its own only beside the three-stage B ring");
     constexpr int WINB = WCAP * 1024, BSTAGE = BN * ROWB;
     extern __shared__ __attribute__((aligned(16))) char smem16[];
     char* const bring = smem16 + 2 * WINB;
     float* const colf2 = reinterpret_cast<float*>(bring + NSTB * BSTAGE);  // [2][2][BN]
     float* const red = colf2 + 4 * BN;                                     // [2][WM][BN]
-    char* const stgfix = reinterpret_cast<char*>(red + 2 * WM * BN);       // STG > 0, KS = 1: [NCW][STG] rows of 256 bytes (KS = 2: in the B ring)
+    char* const stgfix = reinterpret_cast<char*>(red + 2 * WM * BN);       // STG > 0: [NCW][STG] rows of 256 bytes
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1832,7 +1212,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW), 1) void igemm16rw_kernel(cons
                     tau += 2;
                     if (tau >= 9) { tau -= 9; ++ch; ++gc; wstart = tau == 1; }      // tau == 1: the new chunk began at this interval's second K-step
                 }
-                if constexpr (STG > 0) __builtin_amdgcn_s_barrier();      // the consumers stage their epilogue in the ring half the last interval read
                 if (epi_barrier && (!hasnext || (xbase + nidx) % ntn != (xbase + idx) % ntn || (p.ptiles_dbg & 16))) __builtin_amdgcn_s_barrier();      // the consumers' flush
                 if (!hasnext) break;
                 idx = nidx;
@@ -2124,16 +1503,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW), 1) void igemm16rw_kernel(cons
             }
         }
         if constexpr (STG > 0) {
-            char* stg;
-            if constexpr (KS == 2) {
-                // the ring half of the last interval (the loaders refill it after the NEXT tile's first barrier); every consumer must
-                // have read its last B fragments first: one block barrier, matched by the loaders
-                __builtin_amdgcn_s_barrier();
-                stg = bring + ((stage + 2) & 3) * BSTAGE + wid * (STG * 256);
-                static_assert(KS != 2 || NCW * STG * 256 <= 2 * BSTAGE, "staging fits the ring half");
-            } else {
-                stg = stgfix + wid * (STG * 256);
-            }
+            char* const stg = stgfix + wid * (STG * 256);
             epilogue_staged<BM, BN, WM, WN, EPI, STG>(ep, acc, stg, sbase, m_wave, es0, es1, colf, red, mt, n0, tid, wm, wn, lane, carry, flush);
         } else {
             if (!(p.ptiles_dbg & 128) || flush)
@@ -2182,8 +1552,8 @@ hipError_t launch16rw(const IgemmParams& p, hipStream_t st) {
     static const int dbg = getenv("FTE_IGEMM16_DBG") ? atoi(getenv("FTE_IGEMM16_DBG")) : 0;
     q.ptiles_dbg = dbg;
     const size_t lds = (size_t)2 * WCAP * 1024 + (size_t)(KS == 1 ? 3 : 2 * KS) * BN * ROWB + (size_t)(4 * BN + 2 * WM * BN) * sizeof(float) +
-                       (size_t)(STG > 0 && KS == 1 ? WM * WN * STG * 256 : 0);
-    static_assert(2 * WCAP * 1024 + (KS == 1 ? 3 : 2 * KS) * BN * ROWB + (4 * BN + 2 * WM * BN) * 4 + (STG > 0 && KS == 1 ? WM * WN * STG * 256 : 0) <= 160 * 1024, "LDS");
+                       (size_t)WM * WN * STG * 256;
+    static_assert(2 * WCAP * 1024 + (KS == 1 ? 3 : 2 * KS) * BN * ROWB + (4 * BN + 2 * WM * BN) * 4 + WM * WN * STG * 256 <= 160 * 1024, "LDS");
     auto kern = igemm16rw_kernel<BM, BN, WM, WN, EPI, NLW, PFD, WCAP, KS, STG>;
     if (igemm_prof_on()) { const int ta[11] = {BM, BN, WM, WN, EPI, NLW, PFD, WCAP, KS, STG, 0}; igemm_note_symbol("igemm16rw_kernel", ta, 11); }
     static bool attr_done = false;
@@ -2269,33 +1639,15 @@ static bool launch16p_ok(const IgemmParams& p, int epi, int tile, int splits) {
     return true;
 }
 
-template <int BM, int BN, int WM, int WN, int EPI, int MINW, int NSTB = 2>
-hipError_t launch16w(const IgemmParams& p, int splits, hipStream_t st) {
-    const int mt = (p.M - p.m_base + BM - 1) / BM, nt = p.N / BN;
-    const int npc = (BM + 2 * p.a_IW + 2 + 7) / 8;
-    const size_t ring = (size_t)2 * npc * 1024 + (size_t)NSTB * BN * ROWB;
-    const size_t epi = (size_t)(BM + WM * WN * 32 * 36 + 2 * WM * BN) * sizeof(float);
-    const size_t lds = ring > epi ? ring : epi;
-    auto kern = igemm16w_kernel<BM, BN, WM, WN, EPI, MINW, NSTB>;
-    if (igemm_prof_on()) { const int ta[7] = {BM, BN, WM, WN, EPI, MINW, NSTB}; igemm_note_symbol("igemm16w_kernel", ta, 7); }
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(mt * nt, splits), dim3(64 * WM * WN), lds, st, p);
-    return hipGetLastError();
-}
-
-template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW, int ABL = 0, int PF = 0>
+template <int BM, int BN, int WM, int WN, int EPI, int NST, int MINW>
 hipError_t launch16(const IgemmParams& p, int splits, hipStream_t st) {
     const int mt = (p.M - p.m_base + BM - 1) / BM, nt = p.N / BN;
     const size_t ring = (size_t)NST * (BM + BN) * ROWB;
     const size_t epi = (size_t)(BM + WM * WN * 32 * 36 + 2 * WM * BN) * sizeof(float);
     const size_t lds = ring > epi ? ring : epi;
-    auto kern = igemm16_kernel<BM, BN, WM, WN, EPI, NST, MINW, ABL, PF>;
-    if (igemm_prof_on()) { const int ta[9] = {BM, BN, WM, WN, EPI, NST, MINW, ABL, PF}; igemm_note_symbol("igemm16_kernel", ta, 9); }
+    auto kern = igemm16_kernel<BM, BN, WM, WN, EPI, NST, MINW>;
+    // (the last two values: the retired ABL / PF template slots, kept so that the recorded names stay those of the symbol lists)
+    if (igemm_prof_on()) { const int ta[9] = {BM, BN, WM, WN, EPI, NST, MINW, 0, 0}; igemm_note_symbol("igemm16_kernel", ta, 9); }
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2379,62 +1731,9 @@ hipError_t igemm16_launch(const IgemmParams& p, int epi, int tile, int splits, h
         if (epi == EPI_FWD) return launch16bn<128, 64, 4, 2, EPI_FWD, 2, 6>(p, st);
         return launch16bn<128, 64, 4, 2, EPI_DGRAD, 2, 4>(p, st);      // (four waves per SIMD: at six the BN inputs spill 63 registers)
     }
-    static const int abl = getenv("FTE_IGEMM16_ABL") ? atoi(getenv("FTE_IGEMM16_ABL")) : 0;      // diagnostic: see the kernel's ABL
-    if (abl && tile == TILE_128x128 && epi == EPI_FWD) {
-        if (abl == 1) return launch16<128, 128, 2, 2, EPI_FWD, 4, 1, 1>(p, splits, st);
-        if (abl == 2) return launch16<128, 128, 2, 2, EPI_FWD, 4, 1, 2>(p, splits, st);
-        if (abl == 3) return launch16<128, 128, 2, 2, EPI_FWD, 4, 1, 3>(p, splits, st);
-        // the default configuration (two-stage ring, two blocks per CU) with the same ablations: 11, 12, 13; 10 = that kernel itself
-        if (abl == 10) return launch16<128, 128, 2, 2, EPI_FWD, 2, 2, 0>(p, splits, st);
-        if (abl == 11) return launch16<128, 128, 2, 2, EPI_FWD, 2, 2, 1>(p, splits, st);
-        if (abl == 12) return launch16<128, 128, 2, 2, EPI_FWD, 2, 2, 2>(p, splits, st);
-        if (abl == 13) return launch16<128, 128, 2, 2, EPI_FWD, 2, 2, 3>(p, splits, st);
-    }
-    // Measured on MI355X at batch 512 (forward, ms: 14x14x256 / 28x28x128 / 7x7x512): 4-stage ring at one block per CU 0.30 / 0.41 /
-    // 0.29; 2-stage ring at two blocks per CU 0.24 / 0.30 / 0.23 (default); 256x128 tile, 8 waves, 3 stages 0.24 / 0.31 / 0.28;
-    // the register-staged BF = 2 kernel 0.25 / 0.32 / 0.26.  Two co-resident blocks hide each other's prologue, epilogue and
-    // DMA latency better than a deeper ring of one block does.
-    // The window kernel (3x3 / stride 1 / W <= 30: A fetched once per 64-channel chunk instead of once per tap) is an OPTION, not the
-    // default.  Measured on SphereNet at batch 512, bf16 mode, one stream, ms per step (per-tap kernel -> window kernel):
-    //   four waves per block   17.19 -> 16.81   (16 + 24/9 DMA pieces per K-step instead of 32: the piece count is not the bound;
-    //                                            with vmcnt(0) at every step -- the next chunk's window piece forced to land within one
-    //                                            K-step -- nothing at all)
-    //   three / four B stages  20.5 / 20.9      (96 / 112 KB of LDS = ONE block per CU: deeper look-ahead loses to fewer waves)
-    //   eight waves (4 x 2)    15.77 -> 15.75   two blocks per CU = four waves per SIMD; 2 x 4: 16.1; sixteen waves: 17.3
-    // i.e. these launches are paced by how many waves a SIMD has to switch between while one waits on its LDS reads / barrier, and
-    // eight waves per block give the per-tap kernel the same gain.  FTE_IGEMM16_WIN = 1 (4 waves), 8, 9 (2 x 4), 16, 3 / 4 (B stages).
-    static const int winmode = getenv("FTE_IGEMM16_WIN") ? atoi(getenv("FTE_IGEMM16_WIN")) : 0;
-    bool near = true;                                   // every tap within one pixel of the output position (3x3, pad 1)
-    for (int t = 0; t < p.a_NT && t < 9; ++t) near = near && p.a_dh[t] >= -1 && p.a_dh[t] <= 1 && p.a_dw[t] >= -1 && p.a_dw[t] <= 1;
-    if (winmode && tile == TILE_128x128 && p.a_NT == 9 && near && p.a_stride == 1 && p.ncls <= 1 && p.a_IW <= 30 && p.a_IW >= 2 &&
-        p.a_OH == p.a_IH && p.a_OW == p.a_IW) {
-        if (winmode == 8) {          // eight waves (4 x 2, wave tile 32 x 64), two blocks per CU: four waves per SIMD
-            if (epi == EPI_FWD) return launch16w<128, 128, 4, 2, EPI_FWD, 4>(p, splits, st);
-            return launch16w<128, 128, 4, 2, EPI_DGRAD, 4>(p, splits, st);
-        }
-        if (winmode == 9) {          // eight waves as 2 x 4 (wave tile 64 x 32)
-            if (epi == EPI_FWD) return launch16w<128, 128, 2, 4, EPI_FWD, 4>(p, splits, st);
-            return launch16w<128, 128, 2, 4, EPI_DGRAD, 4>(p, splits, st);
-        }
-        if (winmode == 16) {         // sixteen waves (4 x 4, wave tile 32 x 32), two blocks per CU: eight waves per SIMD
-            if (epi == EPI_FWD) return launch16w<128, 128, 4, 4, EPI_FWD, 8>(p, splits, st);
-            return launch16w<128, 128, 4, 4, EPI_DGRAD, 8>(p, splits, st);
-        }
-        if (winmode == 3) {          // three B stages (two K-steps of B in flight), 96 KB: one block per CU
-            if (epi == EPI_FWD) return launch16w<128, 128, 2, 2, EPI_FWD, 1, 3>(p, splits, st);
-            return launch16w<128, 128, 2, 2, EPI_DGRAD, 1, 3>(p, splits, st);
-        }
-        if (winmode == 4) {          // four B stages, 112 KB: one block per CU
-            if (epi == EPI_FWD) return launch16w<128, 128, 2, 2, EPI_FWD, 1, 4>(p, splits, st);
-            return launch16w<128, 128, 2, 2, EPI_DGRAD, 1, 4>(p, splits, st);
-        }
-        if (epi == EPI_FWD) return launch16w<128, 128, 2, 2, EPI_FWD, 2>(p, splits, st);
-        return launch16w<128, 128, 2, 2, EPI_DGRAD, 2>(p, splits, st);
-    }
     // Resident kernels for bf16-STORAGE launches.  FTE_IGEMM16_PERSIST: 1 (default) = the window kernel igemm16rw for
     // every 3x3 / stride-1 layer, igemm16p for the other eligible forward launches and the N = 64 data gradients; 0 = the per-tile
-    // kernels below; 14 = igemm16p for every eligible launch; 22 = the window kernel with one K-step per barrier; 10 = igemm16r (loader
-    // waves, no window).  Measured and dropped (same table): igemm16p with a four-stage ring at one block per CU (0.234 vs 0.160 ms,
+    // kernels below.  Measured and dropped (same table): igemm16p with a four-stage ring at one block per CU (0.234 vs 0.160 ms,
     // 14x14x256 forward), a 256x128 tile without loader waves (0.209), fragment reads two / three sub-steps ahead at 128 registers
     // (spills: 0.168 / 0.170), four waves of 64x64 (0.168); the 128x128 data gradient on igemm16p (0.214 vs 0.202 per-tile).
     // Pointwise launches with at most a block or two per CU (the 1x1 data gradients of the 14x14 / 7x7 / 4x4 stages at a 128-image
@@ -2454,108 +1753,56 @@ hipError_t igemm16_launch(const IgemmParams& p, int epi, int tile, int splits, h
             }
         }
     }
-    static const int pers = getenv("FTE_IGEMM16_PERSIST") ? atoi(getenv("FTE_IGEMM16_PERSIST")) : 1;
-    static const int stg_env = getenv("FTE_IGEMM16_STG") ? atoi(getenv("FTE_IGEMM16_STG")) : 1;      // A/B hook: 0 = the register epilogue everywhere
-    const bool stg = stg_env != 0, stg2 = stg_env == 2;
+    static const bool pers = !(getenv("FTE_IGEMM16_PERSIST") && atoi(getenv("FTE_IGEMM16_PERSIST")) == 0);
     if (pers && launch16p_ok(p, epi, tile, splits)) {
-        const bool win = pers == 1 || pers == 22;
         if (tile == TILE_128x128) {
             // batch 512, ms on one box, per-tile kernel -> igemm16rw: forward 28x28x128 0.220 -> 0.155, 14x14x256 0.161 -> 0.138, 7x7x512
             // 0.185 -> 0.126; data gradient 0.293 -> 0.225, 0.198 -> 0.177, 0.215 -> 0.146
             // two K-steps per barrier, their fragments one stream (kstep2) with one sub-step fetched ahead: on one box, four alternating
             // runs each, the per-step totals of the 28x28 / 14x14 / 7x7 layers 2.163 -> 2.141 ms forward, 2.840 -> 2.793 data gradient
-            // (two sub-steps ahead spills 13 / 25 registers there)
-            if (pers == 1 && (p.K / BK16) % 2 == 0 && launch16rw_ok(p, 256, 45)) {
-                // (the row-coalesced epilogue through the free half of the B ring: SLOWER here -- 28x28x128 forward 0.157 -> 0.180 ms,
-                // data gradient 0.220 -> 0.294 (94 spilled registers beside 64 accumulators and two fetched-ahead inputs), 14x14x256
-                // 0.140 -> 0.146 / 0.175 -> 0.211; the stamped forward epilogue stays at 11-13k cycles: the wait for the inputs and
-                // ~600 VALU instructions per wave, two waves per SIMD, are what is left of it.  FTE_IGEMM16_STG=2 selects it)
-                if (stg2) {
-                    if (epi == EPI_FWD) return launch16rw<256, 128, 4, 2, EPI_FWD, 4, 2, 45, 2, 16>(p, st);
-                    return launch16rw<256, 128, 4, 2, EPI_DGRAD, 4, 2, 45, 2, 16>(p, st);
-                }
+            // (two sub-steps ahead spills 13 / 25 registers there).  An odd number of K-steps, or a window wider than 45 pieces, takes
+            // the one-K-step-per-barrier form.
+            // Retired (see the commit "igemm16: remove the bf16 conv variants the planner never selects"): the row-coalesced epilogue on
+            // this tile, 28x28x128 forward 0.157 -> 0.180 ms, data gradient 0.220 -> 0.294; igemm16r, loader waves without the window,
+            // stamped at 14x14x256: a K-step of 2000 cycles against 1540 here.
+            if ((p.K / BK16) % 2 == 0 && launch16rw_ok(p, 256, 45)) {
                 if (epi == EPI_FWD) return launch16rw<256, 128, 4, 2, EPI_FWD, 4, 1, 45, 2>(p, st);
                 return launch16rw<256, 128, 4, 2, EPI_DGRAD, 4, 1, 45, 2>(p, st);
             }
-            if (win && launch16rw_ok(p, 256, 48)) {
+            if (launch16rw_ok(p, 256, 48)) {
                 if (epi == EPI_FWD) return launch16rw<256, 128, 4, 2, EPI_FWD, 4, 2, 48>(p, st);
                 return launch16rw<256, 128, 4, 2, EPI_DGRAD, 4, 2, 48>(p, st);
             }
-            if (pers == 10 && p.K / BK16 >= 4 && (p.M - p.m_base) >= 256) {      // loader waves + 64 x 64 consumers, no window
-                if (epi == EPI_FWD) return launch16r<256, 128, 4, 2, EPI_FWD, 3, 4, 2>(p, st);
-                return launch16r<256, 128, 4, 2, EPI_DGRAD, 3, 4, 2>(p, st);
-            }
             if (epi == EPI_FWD) return launch16p<128, 128, 4, 2, EPI_FWD, 2, 4, 2>(p, st);
-            if (pers == 14) return launch16p<128, 128, 4, 2, EPI_DGRAD, 2, 4, 2>(p, st);
             // (a 128 x 128 data gradient the window kernel does not take -- stride 2, 1x1 -- stays on the per-tile kernel)
         } else {
             // N = 64: 256 x 64 tile, consumers 64 x 32 (56x56x64 at batch 512: forward 0.42 -> 0.37 (igemm16p) -> 0.24 ms, data
-            // gradient 0.62 -> 0.51 -> 0.42)
-            if (win && launch16rw_ok(p, 256, 56)) {
-                // eight row-waves of 32 x 64 (whole 128-byte rows per wave) and the row-coalesced epilogue (epilogue_staged): 56x56x64 at
-                // batch 512 forward 0.2415 -> 0.2250 ms, data gradient 0.381 -> 0.338
-                if (stg && pers == 1) {
-                    if (epi == EPI_FWD) return launch16rw<256, 64, 8, 1, EPI_FWD, 4, 2, 56, 1, 8>(p, st);
-                    return launch16rw<256, 64, 8, 1, EPI_DGRAD, 4, 2, 56, 1, 8>(p, st);
-                }
-                if (epi == EPI_FWD) return launch16rw<256, 64, 4, 2, EPI_FWD, 4, 2, 56>(p, st);
-                return launch16rw<256, 64, 4, 2, EPI_DGRAD, 4, 2, 56>(p, st);
+            // gradient 0.62 -> 0.51 -> 0.42); eight row-waves of 32 x 64 (whole 128-byte rows per wave) and the row-coalesced epilogue
+            // (epilogue_staged) against the retired register-epilogue form: forward 0.2415 -> 0.2250 ms, data gradient 0.381 -> 0.338
+            if (launch16rw_ok(p, 256, 56)) {
+                if (epi == EPI_FWD) return launch16rw<256, 64, 8, 1, EPI_FWD, 4, 2, 56, 1, 8>(p, st);
+                return launch16rw<256, 64, 8, 1, EPI_DGRAD, 4, 2, 56, 1, 8>(p, st);
             }
             if (epi == EPI_FWD) return launch16p<128, 64, 4, 2, EPI_FWD, 2, 6, 3>(p, st);
             return launch16p<128, 64, 4, 2, EPI_DGRAD, 2, 6, 3>(p, st);
         }
     }
-    // cfg 4 = cfg 1 with eight waves per block: SphereNet bf16 step 16.57 -> 15.77 ms (one stream), 16.0 -> 15.5 (two streams)
-    static const int cfg = getenv("FTE_IGEMM16_CFG") ? atoi(getenv("FTE_IGEMM16_CFG")) : 4;      // tuning hook
-    if (abl >= 20 && abl <= 24 && tile == TILE_128x128 && epi == EPI_FWD) {      // ablations of the default configuration
-        if (abl == 20) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4, 0>(p, splits, st);
-        if (abl == 21) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4, 1>(p, splits, st);
-        if (abl == 22) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4, 2>(p, splits, st);
-        if (abl == 23) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4, 3>(p, splits, st);
-        if (abl == 24) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4, 4>(p, splits, st);
-    }
-    if (cfg == 5 && tile == TILE_128x128) {          // four waves (2 x 2, wave tile 64 x 64), fragments read one sub-step ahead
-        if (epi == EPI_FWD) return launch16<128, 128, 2, 2, EPI_FWD, 2, 2, 0, 1>(p, splits, st);
-        return launch16<128, 128, 2, 2, EPI_DGRAD, 2, 2, 0, 1>(p, splits, st);
-    }
-    if (cfg == 6 && tile == TILE_128x128) {          // eight waves (4 x 2), fragments read one sub-step ahead
-        if (epi == EPI_FWD) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4, 0, 1>(p, splits, st);
-        return launch16<128, 128, 4, 2, EPI_DGRAD, 2, 4, 0, 1>(p, splits, st);
-    }
-    if (cfg == 4 && tile == TILE_128x128) {          // as cfg 1 with eight waves per block (4 x 2): four waves per SIMD
+    // Per-tile kernels: eight waves (4 x 2) per block, two-stage ring.  Measured on MI355X and retired (see the commit "igemm16: remove
+    // the bf16 conv variants the planner never selects" for their code):
+    //   four waves (2 x 2), two blocks per CU: SphereNet bf16 step 16.57 -> 15.77 ms with eight (one stream), 16.0 -> 15.5 (two streams)
+    //   4-stage ring at one block per CU, batch 512 forward 14x14x256 / 28x28x128 / 7x7x512: 0.30 / 0.41 / 0.29 ms against 0.24 / 0.30 / 0.23
+    //   256x128 tile, 8 waves, 3 stages: 0.24 / 0.31 / 0.28 ms; 256x256 tile: 14x14x256 0.239 -> 0.243, 7x7x512 0.244 -> 0.287 ms
+    //   fragment reads one sub-step ahead of their MFMAs (register double buffer), at four and eight waves: never the default
+    //   window kernel (A fetched once per 64-channel chunk of a 3x3 / stride-1 layer): four waves 17.19 -> 16.81 ms per SphereNet bf16
+    //     step, but eight waves 15.77 -> 15.75 -- the eight-wave per-tap kernel takes the same gain
+    //   N = 64 tile with four waves (two- or three-stage ring) instead of eight: see igemm16_handles
+    if (tile == TILE_128x128) {
         if (epi == EPI_FWD) return launch16<128, 128, 4, 2, EPI_FWD, 2, 4>(p, splits, st);
         return launch16<128, 128, 4, 2, EPI_DGRAD, 2, 4>(p, splits, st);
     }
-    if (cfg == 1 && tile == TILE_128x128) {          // 2-stage ring, two blocks per CU
-        if (epi == EPI_FWD) return launch16<128, 128, 2, 2, EPI_FWD, 2, 2>(p, splits, st);
-        return launch16<128, 128, 2, 2, EPI_DGRAD, 2, 2>(p, splits, st);
-    }
-    if (cfg == 2 && tile == TILE_128x128 && epi == EPI_FWD && !p.PW && (p.M - p.m_base) >= 256) {          // 256x128, eight waves (two per SIMD), one block per CU
-        // forward only: the dgrad epilogue's column partials are numbered by the PLANNED tile's rows (api.hip)
-        if (epi == EPI_FWD) return launch16<256, 128, 4, 2, EPI_FWD, 3, 2>(p, splits, st);
-    }
-    if (cfg == 3 && tile == TILE_128x128 && epi == EPI_FWD && !p.PW && (p.M - p.m_base) >= 256 && p.N % 256 == 0) {
-        // 256x256, eight waves of 64 x 128 (two per SIMD), one block per CU: half the staged bytes per FLOP of the 128x128 tile.
-        // Measured (forward, batch 512): 14x14x512->512 (784 tiles) 0.729 -> 0.618 ms = 767 TFLOP/s, but the net's own layers are
-        // too small for it -- 14x14x256 is 392 tiles on 256 CUs (0.239 -> 0.243 ms), 7x7x512 196 tiles (0.244 -> 0.287 ms).
-        return launch16<256, 256, 4, 2, EPI_FWD, 2, 2>(p, splits, st);
-    }
-    if (tile == TILE_128x128) {
-        if (epi == EPI_FWD) return launch16<128, 128, 2, 2, EPI_FWD, 4, 1>(p, splits, st);
-        return launch16<128, 128, 2, 2, EPI_DGRAD, 4, 1>(p, splits, st);
-    }
-    if (tile == TILE_128x64) {
-        static const int nmode = getenv("FTE_IGEMM16_NARROW") ? atoi(getenv("FTE_IGEMM16_NARROW")) : 8;      // 1: four waves, 3-stage ring; 4: four waves, 2-stage
-        if (nmode == 8) {            // eight waves (4 x 2, wave tile 32 x 32), 2-stage ring of 24 KB stages: three blocks per CU
-            if (epi == EPI_FWD) return launch16<128, 64, 4, 2, EPI_FWD, 2, 6>(p, splits, st);
-            return launch16<128, 64, 4, 2, EPI_DGRAD, 2, 6>(p, splits, st);
-        }
-        if (nmode == 4) {            // four waves, 2-stage ring, three blocks per CU
-            if (epi == EPI_FWD) return launch16<128, 64, 2, 2, EPI_FWD, 2, 3>(p, splits, st);
-            return launch16<128, 64, 2, 2, EPI_DGRAD, 2, 3>(p, splits, st);
-        }
-        if (epi == EPI_FWD) return launch16<128, 64, 2, 2, EPI_FWD, 3, 2>(p, splits, st);
-        return launch16<128, 64, 2, 2, EPI_DGRAD, 3, 2>(p, splits, st);
+    if (tile == TILE_128x64) {      // eight waves (4 x 2, wave tile 32 x 32), 2-stage ring of 24 KB stages: three blocks per CU
+        if (epi == EPI_FWD) return launch16<128, 64, 4, 2, EPI_FWD, 2, 6>(p, splits, st);
+        return launch16<128, 64, 4, 2, EPI_DGRAD, 2, 6>(p, splits, st);
     }
     return hipErrorInvalidValue;
 }
