@@ -647,6 +647,51 @@ int fte_momentum_update(float* w, float* acc, const float* g, long n,
 int fte_adam_update(float* w, float* m, float* v, const float* g, long n,
                     float lr, float b1, float b2, float eps, float wd, float gscale, int t, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Evaluation: similarity search and score statistics (verify.py).
+ * Scoring of extracted embeddings: LFW-style listed pairs, all-pairs TAR@FAR through genuine / impostor score histograms, and
+ * 1:N identification through a fused product + top-k.  All arithmetic is fp32 and the products run on v_mfma_f32_32x32x2_f32
+ * (an exact fp32 fma chain in a k order fixed by d alone, so a score does not depend on the tile, slice or chunk that computed
+ * it); these entry points IGNORE fte_set_mfma_dtype.  Rows are row-major [rows, d].  Like every entry point they neither allocate
+ * nor synchronise, and every tensor must stay below 2 GiB: a larger gallery or set is passed in chunks (fte_topk_merge combines
+ * the chunks' top-k lists; the histogram call accumulates, so the host walks the chunk pairs I <= J).
+ * ------------------------------------------------------------------------- */
+
+/* y[i,:] = x[i,:] / max(|x_i|, 1e-12) with |x_i| = sqrt(sum_c x[i,c]^2) reduced in a fixed order; norms[i] = |x_i| when
+ * norms != NULL.  x and y may alias.  FTE_EINVAL: x or y NULL, n < 1, d < 1, or a tensor of 2 GiB or more. */
+int fte_l2_normalize_rows(const float* x, float* y, float* norms, int n, int d, void* stream);
+/* out[p] = dot(x[ia[p],:], x[ib[p],:]) for p < npairs (the LFW protocol's listed pairs, on normalised rows).  An index outside
+ * [0, n) gives out[p] = NaN, never an out-of-bounds read.  FTE_EINVAL: a NULL pointer, n < 1, d < 1, npairs < 1, >= 2 GiB. */
+int fte_pair_scores(const float* x, const int32_t* ia, const int32_t* ib, float* out, int n, int d, int npairs, void* stream);
+/* Fused similarity + top-k.  probes [m, d] and gallery [n, d], both normalised, d % 32 == 0, 1 <= k <= 64, k <= n.
+ * scores [m, k] (fp32) and index [m, k] (int32): row i holds the k best gallery rows j by s = dot(probe_i, gallery_j), sorted by
+ * score descending; equal scores are ordered by the smaller gallery index, so the result is fully deterministic.  Every returned
+ * index is gallery_base + j.  exclude_self != 0 drops the pairs with probe_base + i == gallery_base + j (leave-one-out
+ * identification when probes and gallery are one set); a row then left with fewer than k candidates ends in (-inf, -1) slots.
+ * Two passes: a partial pass over (32-probe block, gallery slice) pairs, the slice count chosen from the CU count, writes each
+ * (row, slice) top-k list to ws; fte_topk_merge then merges the slices.  ws >= fte_topk_search_ws_bytes(m, n, d, k).
+ * FTE_EINVAL: a NULL pointer (ws excepted), m < 1, n < 1, d % 32, k outside 1..min(64, n), a base < 0, or a tensor >= 2 GiB.
+ * FTE_EWORKSPACE: ws NULL or short. */
+size_t fte_topk_search_ws_bytes(int m, int n, int d, int k);
+int fte_topk_search(const float* probes, const float* gallery, int m, int n, int d, int k, int gallery_base, int exclude_self,
+                    int probe_base, float* scores, int32_t* index, void* ws, size_t ws_bytes, void* stream);
+/* Merge of `lists` sorted top-k lists per row: in_scores / in_index [m, lists, k], each list in the order above (index < 0 marks
+ * an empty slot, after every real one) -> scores / index [m, k] in the same order.  The host merges the results of several
+ * gallery chunks with it (stack the chunks' [m, k] outputs into [m, lists, k]).  Indices are taken as they are (no base added).
+ * FTE_EINVAL: a NULL pointer, m < 1, lists outside 1..64, k outside 1..64, or a tensor >= 2 GiB. */
+int fte_topk_merge(const float* in_scores, const int32_t* in_index, int m, int lists, int k, float* scores, int32_t* index,
+                   void* stream);
+/* Fused similarity + score histograms.  a [na, d] with labels la [na], b [nb, d] with labels lb [nb], all normalised,
+ * d % 32 == 0.  same == 0: every pair (i of a, j of b) counts; same != 0: a and b are the same rows (na == nb) and only the
+ * pairs i < j count.  A pair's score s = dot(a_i, b_j) goes to bin
+ *     bin = clamp((int)((s + 1.0f) * (0.5f * nbins)), 0, nbins - 1)        (exactly this fp32 expression)
+ * of hist_genuine when la[i] == lb[j], else of hist_impostor.  Both are uint64 [nbins] and the call ACCUMULATES (+=) into them,
+ * so the host can stream chunk pairs of a set of any size; the counts are integer and independent of execution order.  Bin b
+ * covers scores [2b / nbins - 1, 2(b + 1) / nbins - 1).  nbins is a power of two in 256..8192.
+ * FTE_EINVAL: a NULL pointer, na < 1, nb < 1, d % 32, a bad nbins, same with na != nb, or a tensor >= 2 GiB. */
+int fte_score_histograms(const float* a, const int32_t* la, int na, const float* b, const int32_t* lb, int nb, int d, int same,
+                         int nbins, uint64_t* hist_genuine, uint64_t* hist_impostor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,12 @@ _SIGS = {
     'fte_conv3x3_fwd_keep': (c_int, [_P] * 7 + [c_int] * 6 + [_P, _P, c_size_t, _P]),
     'fte_conv3x3_wgrad_kept': (c_int, [_P] * 3 + [c_int] * 6 + [_P, _P, c_size_t, _P]),
     'fte_get_conv_algo': (c_int, []),
+    'fte_l2_normalize_rows': (c_int, [_P] * 3 + [c_int] * 2 + [_P]),
+    'fte_pair_scores': (c_int, [_P] * 4 + [c_int] * 3 + [_P]),
+    'fte_topk_search_ws_bytes': (c_size_t, [c_int] * 4),
+    'fte_topk_search': (c_int, [_P] * 2 + [c_int] * 7 + [_P] * 3 + [c_size_t, _P]),
+    'fte_topk_merge': (c_int, [_P] * 2 + [c_int] * 3 + [_P] * 3),
+    'fte_score_histograms': (c_int, [_P, _P, c_int, _P, _P] + [c_int] * 4 + [_P] * 3),
     'fte_dwconv3x3_fwd': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_dgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_wgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P, c_size_t, _P]),

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "layers.h"
 #include "wino.h"
+#include "search.h"
 
 namespace {
 
@@ -1817,6 +1818,43 @@ int fte_bn_train_stats_s16(const void* z, const float* gamma, const float* beta,
     if (!ws || ws_bytes < fte_bn_ws_bytes(c)) return FTE_EWORKSPACE;
     return rc(l_bn_train_stats(f32p(z), gamma, beta, rows, c, eps, decay, mean, rstd, scale, shift, moving_mean, moving_var,
                                (float*)ws, (hipStream_t)stream, flags));
+}
+
+// ---------------------------------------------------------------- evaluation (search.hip)
+static inline bool below_2g(long rows, long cols, long elem = 4) { return rows * cols * elem < (1L << 31); }
+int fte_l2_normalize_rows(const float* x, float* y, float* norms, int n, int d, void* stream) {
+    if (!x || !y || n < 1 || d < 1 || !below_2g(n, d)) return FTE_EINVAL;
+    return rc(s_normalize_rows(x, y, norms, n, d, (hipStream_t)stream));
+}
+int fte_pair_scores(const float* x, const int32_t* ia, const int32_t* ib, float* out, int n, int d, int npairs, void* stream) {
+    if (!x || !ia || !ib || !out || n < 1 || d < 1 || npairs < 1 || !below_2g(n, d)) return FTE_EINVAL;
+    return rc(s_pair_scores(x, ia, ib, out, n, d, npairs, (hipStream_t)stream));
+}
+size_t fte_topk_search_ws_bytes(int m, int n, int d, int k) {
+    (void)d;
+    if (m < 1 || n < 1 || k < 1 || k > 64) return 0;
+    return s_topk_ws_bytes(m, n, k);
+}
+int fte_topk_search(const float* probes, const float* gallery, int m, int n, int d, int k, int gallery_base, int exclude_self,
+                    int probe_base, float* scores, int32_t* index, void* ws, size_t ws_bytes, void* stream) {
+    if (!probes || !gallery || !scores || !index || m < 1 || n < 1 || d < 32 || d % 32 || k < 1 || k > 64 || k > n || gallery_base < 0 ||
+        probe_base < 0 || !below_2g(m, d) || !below_2g(n, d) || !below_2g(m, k) || (long)gallery_base + n > 0x7fffffffL)
+        return FTE_EINVAL;
+    if (!ws || ws_bytes < s_topk_ws_bytes(m, n, k)) return FTE_EWORKSPACE;
+    return rc(s_topk_search(probes, gallery, m, n, d, k, gallery_base, exclude_self != 0, probe_base, scores, index, ws, (hipStream_t)stream));
+}
+int fte_topk_merge(const float* in_scores, const int32_t* in_index, int m, int lists, int k, float* scores, int32_t* index, void* stream) {
+    if (!in_scores || !in_index || !scores || !index || m < 1 || lists < 1 || lists > 64 || k < 1 || k > 64 || !below_2g((long)m * lists, k))
+        return FTE_EINVAL;
+    return rc(s_topk_merge(in_scores, in_index, m, lists, k, scores, index, (hipStream_t)stream));
+}
+int fte_score_histograms(const float* a, const int32_t* la, int na, const float* b, const int32_t* lb, int nb, int d, int same,
+                         int nbins, uint64_t* hist_genuine, uint64_t* hist_impostor, void* stream) {
+    if (!a || !la || !b || !lb || !hist_genuine || !hist_impostor || na < 1 || nb < 1 || d < 32 || d % 32 || nbins < 256 || nbins > 8192 ||
+        (nbins & (nbins - 1)) || (same && na != nb) || !below_2g(na, d) || !below_2g(nb, d))
+        return FTE_EINVAL;
+    return rc(s_score_histograms(a, la, na, b, lb, nb, d, same != 0, nbins, (unsigned long long*)hist_genuine,
+                                 (unsigned long long*)hist_impostor, (hipStream_t)stream));
 }
 
 }  // extern "C"

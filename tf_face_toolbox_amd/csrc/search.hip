@@ -1,0 +1,334 @@
+// search.hip -- evaluation kernels behind include/fte.h "Evaluation: similarity search and score statistics".
+// Row normalisation, listed-pair scores, fused similarity + top-k (partial pass + merge) and fused similarity + score histograms.
+// All arithmetic is fp32; the products run on v_mfma_f32_32x32x2_f32 (an exact k-ordered fp32 fma chain), whatever
+// fte_set_mfma_dtype says.
+//
+// The products are oriented S^T = G . P^T: a 32-row block of the lane-side set ("probes", b) sits on the 32 lanes of a wave
+// (lane l holds column l & 31 of the accumulator tile), and 32-row tiles of the register-side set (gallery, a) run through the 16
+// accumulator registers (row (i & 3) + 8 (i >> 2) + 4 (l >> 5) of register i).  Each wave takes TG = 2 register-side tiles per step,
+// so one probe operand feeds two MFMAs.  Operands come straight from global memory: over a 32-wide k block, lane (r, h) loads
+// float4s at k = 32q + 16h + 4u (u = 0..3) of its row, and MFMA t = 4u + e of the block takes element e, i.e. sums k = 32q + t and
+// 32q + 16 + t.  That k order is fixed by d alone, so a score never depends on the tile, slice or chunk that computed it.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "igemm.h"
+#include "search.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int TG = 2;                  // register-side tiles per wave step (64 rows)
+constexpr int SLACK = 32;              // top-k: room above k kept per probe before a compaction
+
+__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+// acc[t][i] = dot(lane-side row, register-side row of tile t) over d (d % 32 == 0); bp / ap[t] already point at column 16h.
+__device__ __forceinline__ void dot_tiles(const float* bp, const float* const (&ap)[TG], int d, f32x16 (&acc)[TG]) {
+#pragma unroll
+    for (int t = 0; t < TG; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    float4 B[4], A[TG][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        B[u] = *(const float4*)(bp + 4 * u);
+#pragma unroll
+        for (int t = 0; t < TG; ++t) A[t][u] = *(const float4*)(ap[t] + 4 * u);
+    }
+    for (int q = 0; q < d; q += 32) {
+        float4 Bc[4], Ac[TG][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            Bc[u] = B[u];
+#pragma unroll
+            for (int t = 0; t < TG; ++t) Ac[t][u] = A[t][u];
+        }
+        if (q + 32 < d) {                    // next k block in flight while this one multiplies
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                B[u] = *(const float4*)(bp + q + 32 + 4 * u);
+#pragma unroll
+                for (int t = 0; t < TG; ++t) A[t][u] = *(const float4*)(ap[t] + q + 32 + 4 * u);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float b4[4] = {Bc[u].x, Bc[u].y, Bc[u].z, Bc[u].w};
+#pragma unroll
+            for (int t = 0; t < TG; ++t) {
+                const float a4[4] = {Ac[t][u].x, Ac[t][u].y, Ac[t][u].z, Ac[t][u].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], acc[t], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// (score, index) order of every result: score descending, then index ascending; index < 0 marks an empty slot, last of all
+__device__ __forceinline__ bool better(float s1, int i1, float s2, int i2) {
+    if (i1 < 0) return false;
+    if (i2 < 0) return true;
+    return s1 > s2 || (s1 == s2 && i1 < i2);
+}
+
+__device__ __forceinline__ void wave_lds_sync() {        // LDS written by other lanes of this wave becomes visible
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// ---------------------------------------------------------------- row normalisation, listed pairs (one wave per row / pair)
+__global__ __launch_bounds__(256) void normalize_rows_kernel(const float* x, float* y, float* norms, int n, int d) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const float* xr = x + (long)row * d;
+    float ss = 0.f;
+    for (int c = lane; c < d; c += 64) ss = fmaf(xr[c], xr[c], ss);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);     // every lane ends with the same sum
+    const float nrm = sqrtf(ss), den = fmaxf(nrm, 1e-12f);
+    if (norms && lane == 0) norms[row] = nrm;
+    float* yr = y + (long)row * d;                                         // y may alias x: each lane rewrites what it read
+    for (int c = lane; c < d; c += 64) yr[c] = xr[c] / den;
+}
+
+__global__ __launch_bounds__(256) void pair_scores_kernel(const float* x, const int32_t* ia, const int32_t* ib, float* out, int n, int d,
+                                                          int np) {
+    const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (p >= np) return;
+    const int a = ia[p], b = ib[p];
+    if (a < 0 || a >= n || b < 0 || b >= n) {
+        if (lane == 0) out[p] = __builtin_nanf("");
+        return;
+    }
+    const float* xa = x + (long)a * d;
+    const float* xb = x + (long)b * d;
+    float s = 0.f;
+    for (int c = lane; c < d; c += 64) s = fmaf(xa[c], xb[c], s);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) out[p] = s;
+}
+
+// ---------------------------------------------------------------- top-k, partial pass
+// One wave per (32-probe block, gallery slice).  Each probe keeps a candidate list in LDS (sc / ix, [slot][probe]: conflict-free
+// for a common slot) shared by its two lanes, and one running threshold: the k-th best kept score once k are kept.  Gallery rows
+// reach a lane in increasing index order, so a later row with a score equal to the threshold loses the tie and `s > thr` admits
+// exactly the rows that can still enter.  When some probe's list passes k + SLACK, the wave compacts every list to its exact top k.
+__device__ void compact(float* sc, int* ix, int r, int h, int& cnt, float& thr, int k) {
+    wave_lds_sync();
+    if (h == 0) {
+        const int keep = min(cnt, k);
+        for (int t = 0; t < keep; ++t) {          // selection: slots 0..keep-1 end sorted
+            float bs = sc[t * 32 + r];
+            int bi = ix[t * 32 + r], bj = t;
+            for (int j = t + 1; j < cnt; ++j) {
+                const float s = sc[j * 32 + r];
+                const int i = ix[j * 32 + r];
+                if (s > bs || (s == bs && i < bi)) { bs = s; bi = i; bj = j; }
+            }
+            if (bj != t) {
+                sc[bj * 32 + r] = sc[t * 32 + r];
+                ix[bj * 32 + r] = ix[t * 32 + r];
+                sc[t * 32 + r] = bs;
+                ix[t * 32 + r] = bi;
+            }
+        }
+        cnt = keep;
+        thr = keep == k ? sc[(k - 1) * 32 + r] : -INFINITY;
+    }
+    wave_lds_sync();
+    cnt = __shfl(cnt, r);
+    thr = __shfl(thr, r);
+}
+
+__global__ __launch_bounds__(64) void topk_partial_kernel(const float* __restrict__ P, const float* __restrict__ G, int m, int n, int d,
+                                                          int k, int steps_per_slice, int gbase, int excl, int pbase,
+                                                          float* __restrict__ ws_s, int* __restrict__ ws_i) {
+    extern __shared__ float lds[];
+    const int cap = k + SLACK + 32 * TG;
+    float* sc = lds;
+    int* ix = (int*)(lds + cap * 32);
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int probe = blockIdx.x * 32 + r, S = gridDim.y, slice = blockIdx.y;
+    const bool pvalid = probe < m;
+    const int nsteps = (n + 63) / 64;
+    const int s0 = slice * steps_per_slice, s1 = min(nsteps, s0 + steps_per_slice);
+    const long self = excl ? (long)pbase + probe - gbase : -1;             // the gallery row this probe skips (local index)
+    const float* bp = P + (long)min(probe, m - 1) * d + 16 * h;
+    float thr = -INFINITY;
+    int cnt = 0;
+    for (int st = s0; st < s1; ++st) {
+        const int g = st * 64;
+        const float* ap[TG];
+#pragma unroll
+        for (int t = 0; t < TG; ++t) ap[t] = G + (long)min(g + 32 * t + r, n - 1) * d + 16 * h;
+        f32x16 acc[TG];
+        dot_tiles(bp, ap, d, acc);
+        unsigned cm = 0;
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = g + 32 * t + acc_row(i, h);
+                const bool ok = pvalid && acc[t][i] > thr && row < n && row != self;
+                cm |= (unsigned)ok << (16 * t + i);
+            }
+        if (__any(cm != 0)) {
+            const unsigned pm = (unsigned)__shfl_xor((int)cm, 32);          // the probe's other lane: it fills the slots after ours
+            int off = cnt + (h ? __popc(pm) : 0);
+#pragma unroll
+            for (int t = 0; t < TG; ++t)
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if ((cm >> (16 * t + i)) & 1u) {
+                        sc[off * 32 + r] = acc[t][i];
+                        ix[off * 32 + r] = gbase + g + 32 * t + acc_row(i, h);
+                        ++off;
+                    }
+            cnt += __popc(cm) + __popc(pm);
+            if (__any(cnt > k + SLACK)) compact(sc, ix, r, h, cnt, thr, k);
+        }
+    }
+    compact(sc, ix, r, h, cnt, thr, k);
+    if (h == 0 && pvalid) {
+        float* os = ws_s + ((long)probe * S + slice) * k;
+        int* oi = ws_i + ((long)probe * S + slice) * k;
+        for (int t = 0; t < k; ++t) {
+            os[t] = t < cnt ? sc[t * 32 + r] : -INFINITY;
+            oi[t] = t < cnt ? ix[t * 32 + r] : -1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- top-k merge: L sorted lists of k per row -> one (one wave per row)
+__global__ __launch_bounds__(64) void topk_merge_kernel(const float* __restrict__ in_s, const int32_t* __restrict__ in_i, int L, int k,
+                                                        float* __restrict__ out_s, int32_t* __restrict__ out_i) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const float* ls = in_s + ((long)row * L + lane) * k;
+    const int32_t* li = in_i + ((long)row * L + lane) * k;
+    int p = 0;
+    float s = -INFINITY;
+    int ix = -1;
+    if (lane < L) { s = ls[0]; ix = li[0]; }
+    for (int t = 0; t < k; ++t) {
+        float bs = s;
+        int bi = ix, bl = lane;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {       // (key, lane) is a total order: every lane ends with the same winner
+            const float os = __shfl_xor(bs, off);
+            const int oi = __shfl_xor(bi, off), ol = __shfl_xor(bl, off);
+            if (better(os, oi, bs, bi) || (!better(bs, bi, os, oi) && ol < bl)) { bs = os; bi = oi; bl = ol; }
+        }
+        if (lane == 0) {
+            out_s[(long)row * k + t] = bs;
+            out_i[(long)row * k + t] = bi;
+        }
+        if (lane == bl) {
+            ++p;
+            if (lane < L && p < k) { s = ls[p]; ix = li[p]; }
+            else { s = -INFINITY; ix = -1; }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- score histograms
+// Four waves per block share two LDS uint32 histograms (genuine, impostor); waves stride over (32-row b tile, 64-row a step) pairs;
+// in the triangle (same) a tile with no pair i < j is skipped before its product.  The block adds its non-zero bins to the uint64
+// outputs with global atomics at the end; integer adds keep the counts independent of order.
+__global__ __launch_bounds__(256) void score_hist_kernel(const float* __restrict__ A, const int32_t* __restrict__ la, int na,
+                                                         const float* __restrict__ B, const int32_t* __restrict__ lb, int nb, int d,
+                                                         int same, int nbins, long ntiles, int nbt, unsigned long long* hg,
+                                                         unsigned long long* hi) {
+    extern __shared__ unsigned hl[];
+    for (int i = threadIdx.x; i < 2 * nbins; i += 256) hl[i] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wave = threadIdx.x >> 6;
+    const float half = 0.5f * nbins;
+    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
+        const int b0 = (int)(tile % nbt) * 32, a0 = (int)(tile / nbt) * 64;
+        if (same && a0 >= b0 + 31) continue;                // every pair of the tile has i >= j
+        const int j = b0 + r, jc = min(j, nb - 1);
+        const int lj = lb[jc];
+        const float* bp = B + (long)jc * d + 16 * h;
+        const float* ap[TG];
+#pragma unroll
+        for (int t = 0; t < TG; ++t) ap[t] = A + (long)min(a0 + 32 * t + r, na - 1) * d + 16 * h;
+        f32x16 acc[TG];
+        dot_tiles(bp, ap, d, acc);
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = a0 + 32 * t + acc_row(i, h);
+                if (row < na && j < nb && (!same || row < j)) {
+                    const int bin = min(max((int)((acc[t][i] + 1.0f) * half), 0), nbins - 1);
+                    atomicAdd(&hl[(la[row] == lj ? 0 : nbins) + bin], 1u);
+                }
+            }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * nbins; i += 256) {
+        const unsigned v = hl[i];
+        if (v) atomicAdd(i < nbins ? &hg[i] : &hi[i - nbins], (unsigned long long)v);
+    }
+}
+
+}  // namespace
+
+hipError_t s_normalize_rows(const float* x, float* y, float* norms, int n, int d, hipStream_t st) {
+    normalize_rows_kernel<<<(n + 3) / 4, 256, 0, st>>>(x, y, norms, n, d);
+    return hipGetLastError();
+}
+
+hipError_t s_pair_scores(const float* x, const int32_t* ia, const int32_t* ib, float* out, int n, int d, int npairs, hipStream_t st) {
+    pair_scores_kernel<<<(npairs + 3) / 4, 256, 0, st>>>(x, ia, ib, out, n, d, npairs);
+    return hipGetLastError();
+}
+
+int s_topk_slices(int m, int n, int k) {
+    (void)k;
+    const long ptiles = (m + 31) / 32, nsteps = (n + 63) / 64;
+    const long want = 8L * igemm_num_cus();                 // one-wave blocks: about two rounds of four per CU
+    long S = (want + ptiles - 1) / ptiles;
+    if (S > 64) S = 64;                                     // the merge takes at most 64 lists
+    if (S > nsteps) S = nsteps;
+    return (int)(S < 1 ? 1 : S);
+}
+
+size_t s_topk_ws_bytes(int m, int n, int k) {
+    return (size_t)m * s_topk_slices(m, n, k) * k * (sizeof(float) + sizeof(int32_t));
+}
+
+hipError_t s_topk_search(const float* probes, const float* gallery, int m, int n, int d, int k, int gallery_base, int exclude_self,
+                         int probe_base, float* scores, int32_t* index, void* ws, hipStream_t st) {
+    const int S = s_topk_slices(m, n, k), nsteps = (n + 63) / 64;
+    float* ws_s = (float*)ws;
+    int32_t* ws_i = (int32_t*)(ws_s + (size_t)m * S * k);
+    const size_t lds = (size_t)(k + SLACK + 32 * TG) * 32 * (sizeof(float) + sizeof(int));
+    topk_partial_kernel<<<dim3((m + 31) / 32, S), 64, lds, st>>>(probes, gallery, m, n, d, k, (nsteps + S - 1) / S, gallery_base,
+                                                                 exclude_self, probe_base, ws_s, ws_i);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return s_topk_merge(ws_s, ws_i, m, S, k, scores, index, st);
+}
+
+hipError_t s_topk_merge(const float* in_scores, const int32_t* in_index, int m, int lists, int k, float* scores, int32_t* index,
+                        hipStream_t st) {
+    topk_merge_kernel<<<m, 64, 0, st>>>(in_scores, in_index, lists, k, scores, index);
+    return hipGetLastError();
+}
+
+hipError_t s_score_histograms(const float* a, const int32_t* la, int na, const float* b, const int32_t* lb, int nb, int d, int same,
+                              int nbins, unsigned long long* hg, unsigned long long* hi, hipStream_t st) {
+    const int nbt = (nb + 31) / 32;
+    const long ntiles = (long)nbt * ((na + 63) / 64);
+    long blocks = 2L * igemm_num_cus();
+    const long per_block_cap = 1L << 20;                    // tiles per block: its uint32 bins see at most 2^20 * 2048 = 2^31 pairs
+    if (blocks < (ntiles + per_block_cap - 1) / per_block_cap) blocks = (ntiles + per_block_cap - 1) / per_block_cap;
+    if (blocks > (ntiles + 3) / 4) blocks = (ntiles + 3) / 4;
+    score_hist_kernel<<<(unsigned)blocks, 256, (size_t)2 * nbins * sizeof(unsigned), st>>>(a, la, na, b, lb, nb, d, same, nbins, ntiles,
+                                                                                           nbt, hg, hi);
+    return hipGetLastError();
+}
