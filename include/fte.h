@@ -692,6 +692,45 @@ int fte_topk_merge(const float* in_scores, const int32_t* in_index, int m, int l
 int fte_score_histograms(const float* a, const int32_t* la, int na, const float* b, const int32_t* lb, int nb, int d, int same,
                          int nbins, uint64_t* hist_genuine, uint64_t* hist_impostor, void* stream);
 
+/* ---- Templates (IJB-style set-to-set comparison; verify.py --protocol templates / template_search) ----
+ * A template is a set of image rows of one subject, grouped into media (one still image, or the frames of one video).  Both
+ * entry points take the grouping as int32 CSR lists over the feature rows x [n, d]:
+ *     members   [n_members]        feature row of each member, template-major (template 0's media first, each media's members
+ *                                  in listed order);
+ *     media_off [n_media + 1]      media m has members[media_off[m] .. media_off[m + 1]);
+ *     tmpl_off  [n_templates + 1]  template t has media tmpl_off[t] .. tmpl_off[t + 1] - 1.
+ * The offsets are read on the device and never trusted: an offset outside its list or a decreasing pair, like a member row
+ * outside [0, n), makes that template's result NaN and is never an out-of-bounds read. */
+
+/* Media-aware template pooling.  For each template t, with w[r] = 1 when w == NULL:
+ *     v = sum over media m of t, in listed order, of  ( sum over members i of m, in listed order: w[r_i] * x[r_i,:] ) / W_m,
+ *         W_m = sum of those w[r_i] in the same order (fp32); a media with W_m == 0 (or no members) contributes nothing;
+ *     out[t,:] = v / max(|v|, 1e-12)      (exactly the fte_l2_normalize_rows rule and reduction order: the pooled row is
+ *                                           bitwise what fte_l2_normalize_rows gives on the unnormalised v)
+ * Every column's sum is one sequential chain in list order, so out depends on the lists alone, not on the launch geometry.  A
+ * template with no media (or only zero-weight media) gives a zero row; one with a member row outside [0, n) or bad offsets gives
+ * a NaN row.  x [n, d], w [n] (optional), out [n_templates, d], any d >= 1.  HBM / L2 bound: a gather with a fixed-order sum.
+ * FTE_EINVAL: a NULL pointer (w excepted), n, d, n_members, n_media or n_templates < 1, or a tensor of 2 GiB or more. */
+int fte_template_pool(const float* x, const float* w, int n, int d, const int32_t* members, int n_members, const int32_t* media_off,
+                      int n_media, const int32_t* tmpl_off, int n_templates, float* out, void* stream);
+/* Set-to-set softmax score fusion (the IJB-A "SoftMax" template comparison).  x [n, d] normalised rows, d % 32 == 0; media are
+ * ignored: template t is the member rows members[media_off[tmpl_off[t]] .. media_off[tmpl_off[t + 1]]).  For each listed pair
+ * p < npairs with A = ta[p], B = tb[p] and betas[0 .. nbetas) (a HOST array, 1 <= nbetas <= 32, each beta in [0, 40]):
+ *     out[p] = (1 / nbetas) sum over b of  N_b / D_b,   N_b = sum_{i in A, j in B} s_ij e_ijb,  D_b = sum_{i in A, j in B} e_ijb,
+ *     s_ij = dot(x_i, x_j) (fp32 on v_mfma_f32_16x16x4_f32, a k order fixed by d alone),
+ *     e_ijb = exp2(c_b * s_ij - c_b) with c_b = (float)(beta_b * log2(e)) (hardware exp2; fp32 fma for the argument).
+ * Shifting the exponent by the bound |s| <= 1 cancels in N_b / D_b and keeps e in [2^-116, 1]: a normal float for beta <= 40,
+ * so no sum can overflow and D_b > 0.  beta = 0 gives the plain mean of the |A| |B| scores.  No score matrix is materialised.
+ * The sums run over 16 x 16 tiles of the pair in an order, and are reduced over the lanes in an order, fixed by (|A|, |B|,
+ * nbetas): a pair's result depends only on its two member lists, x and betas -- not on its position, npairs or the grid -- so
+ * the host may reorder pairs (largest first, for load balance) without changing a bit.  An out-of-range template id, an empty
+ * template, bad offsets or a member row outside [0, n) gives out[p] = NaN.
+ * FTE_EINVAL: a NULL pointer, n, n_members, n_media, n_templates or npairs < 1, d < 32 or d % 32, nbetas outside 1..32, a beta
+ * outside [0, 40] (or NaN), or a tensor of 2 GiB or more. */
+int fte_set_pair_scores(const float* x, int n, int d, const int32_t* members, int n_members, const int32_t* media_off, int n_media,
+                        const int32_t* tmpl_off, int n_templates, const int32_t* ta, const int32_t* tb, int npairs, const float* betas,
+                        int nbetas, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1857,4 +1857,23 @@ int fte_score_histograms(const float* a, const int32_t* la, int na, const float*
                                  (unsigned long long*)hist_impostor, (hipStream_t)stream));
 }
 
+int fte_template_pool(const float* x, const float* w, int n, int d, const int32_t* members, int n_members, const int32_t* media_off,
+                      int n_media, const int32_t* tmpl_off, int n_templates, float* out, void* stream) {
+    if (!x || !members || !media_off || !tmpl_off || !out || n < 1 || d < 1 || n_members < 1 || n_media < 1 || n_templates < 1 ||
+        !below_2g(n, d) || !below_2g(n_templates, d) || !below_2g(n_members, 1) || !below_2g(n_media + 1L, 1) || !below_2g(n_templates + 1L, 1))
+        return FTE_EINVAL;
+    return rc(s_template_pool(x, w, n, d, members, n_members, media_off, n_media, tmpl_off, n_templates, out, (hipStream_t)stream));
+}
+int fte_set_pair_scores(const float* x, int n, int d, const int32_t* members, int n_members, const int32_t* media_off, int n_media,
+                        const int32_t* tmpl_off, int n_templates, const int32_t* ta, const int32_t* tb, int npairs, const float* betas,
+                        int nbetas, float* out, void* stream) {
+    if (!x || !members || !media_off || !tmpl_off || !ta || !tb || !betas || !out || n < 1 || d < 32 || d % 32 || n_members < 1 ||
+        n_media < 1 || n_templates < 1 || npairs < 1 || nbetas < 1 || nbetas > 32 || !below_2g(n, d) ||
+        !below_2g(n_members, 1) || !below_2g(n_media + 1L, 1) || !below_2g(n_templates + 1L, 1) || !below_2g(npairs, 1))
+        return FTE_EINVAL;
+    for (int k = 0; k < nbetas; ++k)
+        if (!(betas[k] >= 0.f && betas[k] <= 40.f)) return FTE_EINVAL;          // NaN fails too
+    return rc(s_set_pair_scores(x, n, d, members, n_members, media_off, n_media, tmpl_off, n_templates, ta, tb, npairs, betas, nbetas, out,
+                                (hipStream_t)stream));
+}
 }  // extern "C"

@@ -1,5 +1,6 @@
-// search.h -- evaluation kernels (search.hip): row normalisation, listed-pair scores, fused similarity + top-k and fused
-// similarity + score histograms.  fp32 throughout (v_mfma_f32_32x32x2_f32); fte_set_mfma_dtype does not apply.
+// search.h -- evaluation kernels (search.hip): row normalisation, listed-pair scores, fused similarity + top-k, fused
+// similarity + score histograms, template pooling and set-to-set softmax score fusion.  fp32 throughout (v_mfma_f32_32x32x2_f32,
+// v_mfma_f32_16x16x4_f32); fte_set_mfma_dtype does not apply.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -15,3 +16,9 @@ hipError_t s_topk_merge(const float* in_scores, const int32_t* in_index, int m, 
                         hipStream_t st);
 hipError_t s_score_histograms(const float* a, const int32_t* la, int na, const float* b, const int32_t* lb, int nb, int d, int same,
                               int nbins, unsigned long long* hg, unsigned long long* hi, hipStream_t st);
+hipError_t s_template_pool(const float* x, const float* w, int n, int d, const int32_t* members, int n_members, const int32_t* media_off,
+                           int n_media, const int32_t* tmpl_off, int n_templates, float* out, hipStream_t st);
+// betas: host array of nbetas (1..32) values
+hipError_t s_set_pair_scores(const float* x, int n, int d, const int32_t* members, int n_members, const int32_t* media_off, int n_media,
+                             const int32_t* tmpl_off, int n_templates, const int32_t* ta, const int32_t* tb, int npairs,
+                             const float* betas, int nbetas, float* out, hipStream_t st);

@@ -18,6 +18,7 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TG = 2;                  // register-side tiles per wave step (64 rows)
 constexpr int SLACK = 32;              // top-k: room above k kept per probe before a compaction
 
@@ -275,6 +276,224 @@ __global__ __launch_bounds__(256) void score_hist_kernel(const float* __restrict
     }
 }
 
+// ---------------------------------------------------------------- template pooling (one wave per template)
+// Lane l owns columns c = c0 + l + 64 j (j < PC) of a 64 * PC column chunk and walks the template's media and members in listed
+// order, so every column's sum is a fixed sequential chain; the norm is the normalize_rows_kernel reduction (same lane/column map,
+// same butterfly), so a pooled row is bit-identical to normalising the unnormalised pooled sum with fte_l2_normalize_rows.
+constexpr int PC = 8;                  // columns per lane per chunk: d <= 512 stays in registers
+constexpr int PU = 4;                  // member rows in flight per wave
+
+__global__ __launch_bounds__(256) void template_pool_kernel(const float* __restrict__ x, const float* __restrict__ w, int n, int d,
+                                                            const int32_t* __restrict__ members, int nmem,
+                                                            const int32_t* __restrict__ media_off, int nmedia,
+                                                            const int32_t* __restrict__ tmpl_off, int nt, float* __restrict__ out) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= nt) return;
+    const int m0 = tmpl_off[t], m1 = tmpl_off[t + 1];
+    bool bad = !(0 <= m0 && m0 <= m1 && m1 <= nmedia);          // every test below reads wave-uniform values
+    float* o = out + (long)t * d;
+    const bool regs = d <= 64 * PC;
+    float acc[PC], ss = 0.f;
+    for (int c0 = 0; c0 < d && !bad; c0 += 64 * PC) {
+#pragma unroll
+        for (int j = 0; j < PC; ++j) acc[j] = 0.f;
+        for (int m = m0; m < m1 && !bad; ++m) {
+            const int i0 = media_off[m], i1 = media_off[m + 1];
+            if (!(0 <= i0 && i0 <= i1 && i1 <= nmem)) { bad = true; break; }
+            float sm[PC], ws = 0.f;
+#pragma unroll
+            for (int j = 0; j < PC; ++j) sm[j] = 0.f;
+            for (int i = i0; i < i1 && !bad; i += PU) {
+                const int cnt = min(PU, i1 - i);
+                int r[PU];
+                float v[PU][PC], wu[PU];
+#pragma unroll
+                for (int u = 0; u < PU; ++u) {
+                    r[u] = u < cnt ? members[i + u] : 0;
+                    if (r[u] < 0 || r[u] >= n) bad = true;
+                }
+                if (bad) break;
+#pragma unroll
+                for (int u = 0; u < PU; ++u) {
+                    const float* xr = x + (long)r[u] * d;
+                    wu[u] = u < cnt ? (w ? w[r[u]] : 1.f) : 0.f;
+#pragma unroll
+                    for (int j = 0; j < PC; ++j) {
+                        const int c = c0 + lane + 64 * j;
+                        v[u][j] = (u < cnt && c < d) ? xr[c] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < PU; ++u)
+                    if (u < cnt) {
+                        ws += wu[u];
+#pragma unroll
+                        for (int j = 0; j < PC; ++j) sm[j] = fmaf(wu[u], v[u][j], sm[j]);
+                    }
+            }
+            if (!bad && ws != 0.f)
+#pragma unroll
+                for (int j = 0; j < PC; ++j) acc[j] += sm[j] / ws;
+        }
+#pragma unroll
+        for (int j = 0; j < PC; ++j) {
+            const int c = c0 + lane + 64 * j;
+            if (c < d) {
+                ss = fmaf(acc[j], acc[j], ss);
+                if (!regs) o[c] = acc[j];                           // re-read and scaled below by the lane that wrote it
+            }
+        }
+    }
+    if (bad) {
+        for (int c = lane; c < d; c += 64) o[c] = __builtin_nanf("");
+        return;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
+    const float den = fmaxf(sqrtf(ss), 1e-12f);
+    if (regs) {
+#pragma unroll
+        for (int j = 0; j < PC; ++j) {
+            const int c = lane + 64 * j;
+            if (c < d) o[c] = acc[j] / den;
+        }
+    } else {
+        for (int c = lane; c < d; c += 64) o[c] = o[c] / den;
+    }
+}
+
+// ---------------------------------------------------------------- set-to-set softmax score fusion (one wave per pair)
+// The pair's |A| x |B| scores come in 16 x 16 tiles of v_mfma_f32_16x16x4_f32 (A rows on (lane & 15, register rows), B rows on
+// lane & 15 of the columns), A tiles outer, B tiles inner, two B tiles per step while two remain (one A operand feeds both).
+// Operands come straight from global memory: over a 32-wide k block, lane (r, g = lane >> 4) loads float4s at k = 32q + 8g + 4u
+// (u = 0, 1) of its row, and MFMA t = 4u + e of the block takes element e, i.e. sums k = 32q + 8g' + 4u + e over g'.  That k order
+// is fixed by d alone.  The epilogue keeps per-lane running sums num[b] += s e, den[b] += e with e = exp2(c_b (s - 1)),
+// c_b = beta_b log2(e); the tile order, the lane butterfly and the beta order are fixed by (|A|, |B|, nbetas) alone.
+constexpr int MAXB = 32;
+struct BetaC { float c[MAXB]; };
+
+template <int NT>
+__device__ __forceinline__ void dot16(const float* ap, const float* const (&bp)[NT], int d, f32x4 (&acc)[NT]) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float4 A[2], B[NT][2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        A[u] = *(const float4*)(ap + 4 * u);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) B[t][u] = *(const float4*)(bp[t] + 4 * u);
+    }
+    for (int q = 0; q < d; q += 32) {
+        float4 Ac[2], Bc[NT][2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            Ac[u] = A[u];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) Bc[t][u] = B[t][u];
+        }
+        if (q + 32 < d) {                    // next k block in flight while this one multiplies
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                A[u] = *(const float4*)(ap + q + 32 + 4 * u);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) B[t][u] = *(const float4*)(bp[t] + q + 32 + 4 * u);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const float a4[4] = {Ac[u].x, Ac[u].y, Ac[u].z, Ac[u].w};
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float b4[4] = {Bc[t][u].x, Bc[t][u].y, Bc[t][u].z, Bc[t][u].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[e], b4[e], acc[t], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// members of template t: [s, e) of `members`; false for a bad id, bad offsets or an empty template
+__device__ __forceinline__ bool template_range(int t, int nt, const int32_t* media_off, int nmedia, const int32_t* tmpl_off, int nmem,
+                                               int& s, int& e) {
+    if (t < 0 || t >= nt) return false;
+    const int m0 = tmpl_off[t], m1 = tmpl_off[t + 1];
+    if (!(0 <= m0 && m0 < m1 && m1 <= nmedia)) return false;
+    s = media_off[m0];
+    e = media_off[m1];
+    return 0 <= s && s < e && e <= nmem;
+}
+
+__device__ __forceinline__ void softmax_acc(float s, const BetaC& bc, int nb, float (&num)[MAXB], float (&den)[MAXB]) {
+#pragma unroll
+    for (int k = 0; k < MAXB; ++k)
+        if (k < nb) {
+            const float e = __builtin_amdgcn_exp2f(fmaf(bc.c[k], s, -bc.c[k]));     // in (2^-116, 1]: a normal float
+            num[k] = fmaf(s, e, num[k]);
+            den[k] += e;
+        }
+}
+
+template <int NT>
+__device__ __forceinline__ void pair_step(const float* x, const int32_t* members, int d, int a0, int na, int ti, int b0, int nbm, int tj,
+                                          int r, int g, const BetaC& bc, int nb, float (&num)[MAXB], float (&den)[MAXB]) {
+    const float* ap = x + (long)members[a0 + min(16 * ti + r, na - 1)] * d + 8 * g;
+    const float* bp[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) bp[t] = x + (long)members[b0 + min(16 * (tj + t) + r, nbm - 1)] * d + 8 * g;
+    f32x4 acc[NT];
+    dot16<NT>(ap, bp, d, acc);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (16 * ti + 4 * g + q < na && 16 * (tj + t) + r < nbm) softmax_acc(acc[t][q], bc, nb, num, den);
+}
+
+__global__ __launch_bounds__(256) void set_pair_scores_kernel(const float* __restrict__ x, int n, int d, const int32_t* __restrict__ members,
+                                                              int nmem, const int32_t* __restrict__ media_off, int nmedia,
+                                                              const int32_t* __restrict__ tmpl_off, int nt, const int32_t* __restrict__ ta,
+                                                              const int32_t* __restrict__ tb, int np, BetaC bc, int nb,
+                                                              float* __restrict__ out) {
+    const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (p >= np) return;
+    int a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+    bool ok = template_range(ta[p], nt, media_off, nmedia, tmpl_off, nmem, a0, a1) &&
+              template_range(tb[p], nt, media_off, nmedia, tmpl_off, nmem, b0, b1);
+    if (ok) {
+        bool badrow = false;
+        for (int i = a0 + lane; i < a1; i += 64) badrow |= members[i] < 0 || members[i] >= n;
+        for (int i = b0 + lane; i < b1; i += 64) badrow |= members[i] < 0 || members[i] >= n;
+        ok = !__any(badrow);
+    }
+    if (!ok) {
+        if (lane == 0) out[p] = __builtin_nanf("");
+        return;
+    }
+    const int na = a1 - a0, nbm = b1 - b0, TA = (na + 15) / 16, TB = (nbm + 15) / 16;
+    const int r = lane & 15, g = lane >> 4;
+    float num[MAXB], den[MAXB];
+#pragma unroll
+    for (int k = 0; k < MAXB; ++k) num[k] = den[k] = 0.f;
+    for (int ti = 0; ti < TA; ++ti) {
+        int tj = 0;
+        for (; tj + 2 <= TB; tj += 2) pair_step<2>(x, members, d, a0, na, ti, b0, nbm, tj, r, g, bc, nb, num, den);
+        if (tj < TB) pair_step<1>(x, members, d, a0, na, ti, b0, nbm, tj, r, g, bc, nb, num, den);
+    }
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXB; ++k)
+        if (k < nb) {
+            float nu = num[k], de = den[k];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                nu += __shfl_xor(nu, off);
+                de += __shfl_xor(de, off);
+            }
+            tot += nu / de;
+        }
+    if (lane == 0) out[p] = tot / (float)nb;
+}
+
 }  // namespace
 
 hipError_t s_normalize_rows(const float* x, float* y, float* norms, int n, int d, hipStream_t st) {
@@ -330,5 +549,22 @@ hipError_t s_score_histograms(const float* a, const int32_t* la, int na, const f
     if (blocks > (ntiles + 3) / 4) blocks = (ntiles + 3) / 4;
     score_hist_kernel<<<(unsigned)blocks, 256, (size_t)2 * nbins * sizeof(unsigned), st>>>(a, la, na, b, lb, nb, d, same, nbins, ntiles,
                                                                                            nbt, hg, hi);
+    return hipGetLastError();
+}
+
+hipError_t s_template_pool(const float* x, const float* w, int n, int d, const int32_t* members, int n_members, const int32_t* media_off,
+                           int n_media, const int32_t* tmpl_off, int n_templates, float* out, hipStream_t st) {
+    template_pool_kernel<<<(n_templates + 3) / 4, 256, 0, st>>>(x, w, n, d, members, n_members, media_off, n_media, tmpl_off, n_templates,
+                                                                out);
+    return hipGetLastError();
+}
+
+hipError_t s_set_pair_scores(const float* x, int n, int d, const int32_t* members, int n_members, const int32_t* media_off, int n_media,
+                             const int32_t* tmpl_off, int n_templates, const int32_t* ta, const int32_t* tb, int npairs,
+                             const float* betas, int nbetas, float* out, hipStream_t st) {
+    BetaC bc = {};
+    for (int k = 0; k < nbetas && k < MAXB; ++k) bc.c[k] = betas[k] * 1.44269504088896340736f;     // beta * log2(e), rounded once
+    set_pair_scores_kernel<<<(npairs + 3) / 4, 256, 0, st>>>(x, n, d, members, n_members, media_off, n_media, tmpl_off, n_templates, ta, tb,
+                                                             npairs, bc, nbetas, out);
     return hipGetLastError();
 }

@@ -1,10 +1,13 @@
-"""Face verification and 1:N identification scoring of extracted embeddings (verify.py; DESIGN.md 4.10).
+"""Face verification and 1:N identification scoring of extracted embeddings (verify.py; DESIGN.md 4.10, 4.11).
 
 Device side (torch CUDA tensors in): every product and reduction is a libfte.so call (include/fte.h, "Evaluation: similarity
 search and score statistics"); there is no torch fallback for the arithmetic.  torch only allocates, pads and stacks.
 
 Host side (numpy, importable without a GPU): the LFW pairs.txt parser and row mapping, the 10-fold accuracy protocol, TAR@FAR
-from score histograms, and CMC from top-k indices."""
+from score histograms, and CMC from top-k indices; for templates (IJB-style sets of images grouped into media): the metadata and
+template-pair parsers, the CSR grouping the kernels take, exact TAR@FAR from listed scores and open-set identification."""
+import csv
+import ctypes
 import os
 
 import numpy as np
@@ -123,6 +126,97 @@ def score_histograms(feats, labels, nbins=8192, chunk_rows=None):
             _lib.call('fte_score_histograms', feats[a0:a1], lab[a0:a1], a1 - a0, feats[b0:b1], lab[b0:b1], b1 - b0, d, same, nbins,
                       hg, hi, st)
     return hg.cpu().numpy().astype(np.uint64), hi.cpu().numpy().astype(np.uint64)
+
+
+def _check_x(x, what):
+    import torch
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError('%s: expected a 2-D float32 CUDA tensor, got %s' % (what, tuple(x.shape)))
+    if x.numel() * 4 > _TENSOR_LIMIT:
+        raise ValueError('%s: x is %d x %d = %.2f GiB; the library takes tensors below 2 GiB (pass fewer rows)'
+                         % (what, x.shape[0], x.shape[1], x.numel() * 4 / 2.0 ** 30))
+
+
+def _i32(a, dev):
+    """an int32 device copy of a list / numpy array; a tensor already there is taken as it is"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(a, np.int64)).astype(np.int32)).to(dev)
+
+
+def template_pool(x, members, media_off, tmpl_off, weights=None):
+    """Media-aware template pooling (fte_template_pool): out [n_templates, d] float32, row t = normalize(sum over media of t of
+    the weighted mean of the media's member rows of x).  members / media_off / tmpl_off: the CSR lists of build_templates();
+    weights: optional per-row weights [n] (None: 1).  Lists, numpy arrays or tensors.  A template with no media gives a zero row, a bad member row a NaN row."""
+    import torch
+    _check_x(x, 'template_pool')
+    n, d = x.shape
+    dev = x.device
+    nt = len(tmpl_off) - 1
+    if len(members) < 1 or len(media_off) < 2 or nt < 1:
+        raise ValueError('template_pool: empty members / media_off / tmpl_off')
+    w = None
+    if weights is not None:
+        w = (weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights, np.float32)))
+        w = w.to(device=dev, dtype=torch.float32).contiguous()
+        if w.numel() != n:
+            raise ValueError('template_pool: %d weights for %d rows' % (w.numel(), n))
+    out = torch.empty(nt, d, dtype=torch.float32, device=dev)
+    x = x.contiguous()
+    _lib.call('fte_template_pool', x, w, n, d, _i32(members, dev), len(members), _i32(media_off, dev), len(media_off) - 1,
+              _i32(tmpl_off, dev), nt, out, _stream())
+    return out
+
+
+def _host(a):
+    import torch
+    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def template_sizes(media_off, tmpl_off):
+    """members per template (media ignored), from the CSR lists"""
+    media_off = np.asarray(media_off, np.int64)
+    tmpl_off = np.asarray(tmpl_off, np.int64)
+    return media_off[tmpl_off[1:]] - media_off[tmpl_off[:-1]]
+
+
+def set_pair_scores(x, members, media_off, tmpl_off, ta, tb, betas=range(0, 21)):
+    """Set-to-set softmax score fusion (fte_set_pair_scores) of the listed template pairs (ta[p], tb[p]) over normalised image
+    rows x [n, d] (d % 32 == 0): the mean over betas of the exp(beta s)-weighted mean of the |A| |B| image scores.  The pairs are
+    handed to the library largest first (by the power of two at or below their 16 x 16 tile count), and within one such class
+    grouped by template so that consecutive waves reuse the same rows from cache; a pair's result does not depend on its
+    position.  The output is returned in the listed order, float32 [npairs].  Lists, numpy arrays or tensors."""
+    import torch
+    _check_x(x, 'set_pair_scores')
+    n, d = x.shape
+    if d % 32:
+        raise ValueError('set_pair_scores: d = %d is not a multiple of 32 (use normalize())' % d)
+    betas = np.asarray(list(betas), np.float32)
+    if not 1 <= len(betas) <= 32 or np.any(~(betas >= 0)) or np.any(betas > 40):
+        raise ValueError('set_pair_scores: betas must be 1..32 values in [0, 40], got %s' % (betas.tolist(),))
+    dev = x.device
+    ta, tb = _i32(ta, dev).reshape(-1), _i32(tb, dev).reshape(-1)
+    if ta.shape != tb.shape or ta.numel() < 1:
+        raise ValueError('set_pair_scores: ta and tb must be equal, non-empty lists')
+    nt = len(tmpl_off) - 1
+    # the order handed to the library, computed on the device (a host sort of 15M pairs takes seconds): largest first by the
+    # power of two at or below the pair's 16 x 16 tile count, and within one such class by template A, so that consecutive
+    # waves reuse its rows from cache; an out-of-range id costs nothing (NaN)
+    tiles16 = torch.as_tensor(np.concatenate([(template_sizes(_host(media_off), _host(tmpl_off)) + 15) // 16, [0]]), device=dev)
+    ok = lambda t: torch.where((t >= 0) & (t < nt), t.long(), torch.full_like(t, nt, dtype=torch.int64))
+    tiles = (tiles16[ok(ta)] * tiles16[ok(tb)]).clamp_min(1).double()
+    cls = torch.floor(torch.log2(tiles)).long()                                 # 0 .. 62
+    key = (63 - cls) * (nt + 1) + ok(ta)
+    order = torch.sort(key, stable=True)[1]
+    out = torch.empty(ta.numel(), dtype=torch.float32, device=dev)
+    x = x.contiguous()
+    _lib.call('fte_set_pair_scores', x, n, d, _i32(members, dev), len(members), _i32(media_off, dev), len(media_off) - 1,
+              _i32(tmpl_off, dev), nt, ta[order].contiguous(), tb[order].contiguous(), ta.numel(),
+              betas.ctypes.data_as(ctypes.c_void_p), len(betas), out, _stream())
+    res = torch.empty_like(out)
+    res[order] = out
+    return res
 
 
 # ------------------------------------------------------------------ host side: protocols
@@ -244,3 +338,187 @@ def cmc(index, probe_labels, gallery_labels, ranks=(1, 5, 10)):
     hit[ok] = gl[index[ok]] == np.broadcast_to(pl[:, None], index.shape)[ok]
     first = np.where(hit.any(1), hit.argmax(1), index.shape[1])
     return {r: float(np.mean(first < r)) for r in ranks}
+
+
+# ------------------------------------------------------------------ host side: templates (IJB-A / -B / -C style)
+def read_template_metadata(path, weight_column=None):
+    """IJB-A-style metadata CSV with a header row.  Columns are read by name (case and surrounding blanks ignored):
+    TEMPLATE_ID, SUBJECT_ID, FILE, MEDIA_ID, and `weight_column` when given; every other column is ignored.  Returns a dict of
+    per-row lists: template (int64), subject (int64), file (str), media (str) and weight (float32, or None).  Raises ValueError
+    for a missing column or a template whose rows name two subjects."""
+    with open(os.path.expanduser(path), newline='') as f:
+        rows = [r for r in csv.reader(f) if r and any(c.strip() for c in r)]
+    if not rows:
+        raise ValueError('%s is empty' % path)
+    head = [c.strip().upper() for c in rows[0]]
+    want = ['TEMPLATE_ID', 'SUBJECT_ID', 'FILE', 'MEDIA_ID'] + ([weight_column.strip().upper()] if weight_column else [])
+    col = {}
+    for name in want:
+        if name not in head:
+            raise ValueError('%s: no column %s in the header %s' % (path, name, rows[0]))
+        col[name] = head.index(name)
+    tid, sid, files, media, weight = [], [], [], [], []
+    for ln, r in enumerate(rows[1:], 2):
+        try:
+            tid.append(int(float(r[col['TEMPLATE_ID']])))
+            sid.append(int(float(r[col['SUBJECT_ID']])))
+            files.append(r[col['FILE']].strip())
+            media.append(r[col['MEDIA_ID']].strip())
+            if weight_column:
+                weight.append(float(r[col[want[-1]]]))
+        except (IndexError, ValueError):
+            raise ValueError('%s:%d: bad metadata row %r' % (path, ln, ','.join(r)))
+    tid = np.asarray(tid, np.int64)
+    sid = np.asarray(sid, np.int64)
+    subj = {}
+    for t, s in zip(tid.tolist(), sid.tolist()):
+        if subj.setdefault(t, s) != s:
+            raise ValueError('%s: template %d names subjects %d and %d' % (path, t, subj[t], s))
+    return {'template': tid, 'subject': sid, 'file': files, 'media': media,
+            'weight': np.asarray(weight, np.float32) if weight_column else None}
+
+
+def build_templates(meta):
+    """The CSR grouping the template kernels take, from read_template_metadata() output (feature row i = metadata row i).
+    Templates in ascending id, media of a template in order of first appearance, members of a media in metadata order.  Returns a
+    dict: members int32 [rows], media_off int32 [n_media + 1], tmpl_off int32 [n_templates + 1], template_ids int64
+    [n_templates], subjects int64 [n_templates]."""
+    tid = np.asarray(meta['template'], np.int64)
+    sid = np.asarray(meta['subject'], np.int64)
+    media = meta['media']
+    ids = np.unique(tid)
+    members, media_off, tmpl_off, subjects = [], [0], [0], []
+    rows_of = {}
+    for i, t in enumerate(tid.tolist()):
+        rows_of.setdefault(t, []).append(i)
+    for t in ids.tolist():
+        groups = {}
+        for i in rows_of[t]:
+            groups.setdefault(media[i], []).append(i)                  # dicts keep first-appearance order
+        for g in groups.values():
+            members.extend(g)
+            media_off.append(len(members))
+        tmpl_off.append(len(media_off) - 1)
+        subjects.append(sid[rows_of[t][0]])
+    return {'members': np.asarray(members, np.int32), 'media_off': np.asarray(media_off, np.int32),
+            'tmpl_off': np.asarray(tmpl_off, np.int32), 'template_ids': ids, 'subjects': np.asarray(subjects, np.int64)}
+
+
+def read_template_pairs(path, template_subjects=None):
+    """Template pairs `t1 t2 [label]`, comma- or blank-separated, one per line (a non-numeric first line is taken as a header).
+    Without a label a pair is genuine when both templates have the same subject in `template_subjects` ({template id: subject}).
+    Returns (t1 int64, t2 int64, genuine bool)."""
+    t1, t2, gen = [], [], []
+    for ln, line in enumerate(open(os.path.expanduser(path)), 1):
+        tok = line.replace(',', ' ').split()
+        if not tok:
+            continue
+        try:
+            a, b = int(float(tok[0])), int(float(tok[1]))
+        except (IndexError, ValueError):
+            if ln == 1 and not t1:
+                continue
+            raise ValueError('%s:%d: bad pairs line %r' % (path, ln, line.strip()))
+        if len(tok) >= 3:
+            g = bool(int(float(tok[2])))
+        else:
+            if template_subjects is None:
+                raise ValueError('%s:%d: no label and no template subjects to derive it from' % (path, ln))
+            for t in (a, b):
+                if t not in template_subjects:
+                    raise ValueError('%s:%d: template %d is not in the metadata' % (path, ln, t))
+            g = template_subjects[a] == template_subjects[b]
+        t1.append(a)
+        t2.append(b)
+        gen.append(g)
+    if not t1:
+        raise ValueError('%s lists no pairs' % path)
+    return np.asarray(t1, np.int64), np.asarray(t2, np.int64), np.asarray(gen, bool)
+
+
+def template_index(template_ids, ids, what='template'):
+    """positions of `ids` in the ascending `template_ids` of build_templates(); KeyError naming the first unknown id"""
+    template_ids = np.asarray(template_ids, np.int64)
+    ids = np.asarray(ids, np.int64)
+    pos = np.searchsorted(template_ids, ids)
+    bad = (pos >= len(template_ids)) | (template_ids[np.minimum(pos, len(template_ids) - 1)] != ids)
+    if bad.any():
+        raise KeyError('%s %d is not in the metadata' % (what, ids[np.argmax(bad)]))
+    return pos
+
+
+def check_data_list(image_paths, meta, list_path='the data list'):
+    """Row i of the feature file must be metadata row i: the list has the metadata's row count and path i ends with FILE i (at a
+    path-component boundary).  Raises ValueError naming the first mismatch."""
+    files = meta['file']
+    if len(image_paths) != len(files):
+        raise ValueError('%s lists %d images, the template metadata has %d rows' % (list_path, len(image_paths), len(files)))
+    for i, (p, f) in enumerate(zip(image_paths, files)):
+        p, f = p.replace('\\', '/'), f.replace('\\', '/').lstrip('/')
+        if not (p == f or p.endswith('/' + f)):
+            raise ValueError('%s row %d is %s, but metadata row %d names FILE %s' % (list_path, i, p, i, f))
+
+
+def write_template_list(meta, image_root, out):
+    """The image list evaluate.py reads, one `path subject` line per metadata row in metadata order (feature row i = metadata
+    row i), with path = image_root/FILE."""
+    with open(os.path.expanduser(out), 'w') as f:
+        for name, s in zip(meta['file'], np.asarray(meta['subject']).tolist()):
+            f.write('%s %d\n' % (os.path.join(image_root, name.replace('\\', '/').lstrip('/')), s))
+
+
+def _kth_threshold(neg, rate):
+    """the k-th largest (0-based) of the negative scores, k = floor(rate * n): accepting s > it admits at most k negatives"""
+    neg = np.sort(np.asarray(neg, np.float64))[::-1]
+    return neg[min(int(np.floor(rate * len(neg))), len(neg) - 1)]
+
+
+def tar_at_far_scores(scores, genuine, fars=(1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)):
+    """Exact TAR at each target FAR from listed pair scores: with i_k the k-th largest impostor score (0-based),
+    k = floor(FAR * n_imp), the threshold accepts s > i_k.  Returns one dict per target: far, tar, achieved_far, threshold -- or
+    'n/a' where fewer than round(1 / FAR) impostor pairs (or no genuine pair) exist, as tar_at_far."""
+    scores = np.asarray(scores, np.float64)
+    genuine = np.asarray(genuine, bool)
+    if scores.shape != genuine.shape:
+        raise ValueError('tar_at_far_scores: %d scores for %d labels' % (scores.size, genuine.size))
+    if np.isnan(scores).any():
+        raise ValueError('tar_at_far_scores: %d NaN scores (a bad or empty template)' % int(np.isnan(scores).sum()))
+    g, imp = scores[genuine], scores[~genuine]
+    out = []
+    for far in fars:
+        if len(imp) < round(1.0 / far) or len(g) == 0:
+            out.append({'far': far, 'tar': 'n/a', 'achieved_far': 'n/a', 'threshold': 'n/a'})
+            continue
+        thr = _kth_threshold(imp, far)
+        out.append({'far': far, 'tar': float(np.mean(g > thr)), 'achieved_far': float(np.mean(imp > thr)), 'threshold': float(thr)})
+    return out
+
+
+def open_set_identification(top_scores, top_index, probe_subjects, gallery_subjects, ranks=(1, 5, 10), fpirs=(0.01, 0.1)):
+    """Open-set 1:N identification of probe templates against gallery templates from the search result (top_scores /
+    top_index [m, k], best first; index < 0 an empty slot).  A probe is mated when its subject has a gallery template.
+    cmc: over mated probes, the fraction whose mate is among the first r results.  TPIR@FPIR: the threshold is the k-th largest
+    (0-based, k = floor(FPIR * n_nonmated)) of the non-mated probes' top-1 scores; TPIR is the fraction of mated probes whose
+    rank-1 result is the mate and scores above it ('n/a' where fewer than round(1 / FPIR) non-mated probes exist)."""
+    ts = np.asarray(top_scores, np.float64)
+    ti = np.asarray(top_index, np.int64)
+    ps = np.asarray(probe_subjects, np.int64)
+    gs = np.asarray(gallery_subjects, np.int64)
+    mated = np.isin(ps, gs)
+    hit = np.zeros(ti.shape, bool)
+    ok = ti >= 0
+    hit[ok] = gs[ti[ok]] == np.broadcast_to(ps[:, None], ti.shape)[ok]
+    first = np.where(hit.any(1), hit.argmax(1), ti.shape[1])
+    nm = int(mated.sum())
+    cmc_ = {r: (float(np.mean(first[mated] < r)) if nm else 'n/a') for r in ranks}
+    top1 = ts[:, 0]
+    tp = []
+    for fpir in fpirs:
+        neg = top1[~mated]
+        if len(neg) < round(1.0 / fpir) or nm == 0:
+            tp.append({'fpir': fpir, 'tpir': 'n/a', 'achieved_fpir': 'n/a', 'threshold': 'n/a'})
+            continue
+        thr = _kth_threshold(neg, fpir)
+        tpir = float(np.mean((first[mated] == 0) & (top1[mated] > thr)))
+        tp.append({'fpir': fpir, 'tpir': tpir, 'achieved_fpir': float(np.mean(neg > thr)), 'threshold': float(thr)})
+    return {'mated': nm, 'non_mated': int((~mated).sum()), 'cmc': cmc_, 'tpir_at_fpir': tp}
