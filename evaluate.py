@@ -60,16 +60,21 @@ def evaluate(FLAGS):
         saver.restore(model, latest)
         step = str(saver.step_of(latest))
         print('Extracting features from model saved in iteration %s...' % step)
-        wfea = None
-        while wfea is None or wfea.shape[0] < num_images:
+        # filled in place, allocated at the first batch (its width and dtype): growing it per batch copies O(n^2) bytes, about
+        # 4 TB for a million-row distractor list
+        wfea, done = None, 0
+        while done < num_images:
             start_time = time.time()
             # SphereNet: forward(is_training=False) is the flip-averaged embedding (nets/sphere.py:97-101); the graph nets: the
             # pooled backbone features (their reference forward() cannot be called without num_classes, nets/resnet.py:147)
             batch = next_images()
             fea = (model.eval_features(batch) if hasattr(model, 'eval_features') else model.forward(batch, is_training=False)).cpu().numpy()
-            wfea = fea if wfea is None else np.vstack((wfea, fea))
-            print('%d/%d features extracted... %.2fms elapsed' % (min(wfea.shape[0], num_images), num_images,
-                                                                (time.time() - start_time) * 1000))
+            if wfea is None:
+                wfea = np.empty((num_images,) + fea.shape[1:], fea.dtype)
+            take = min(fea.shape[0], num_images - done)
+            wfea[done:done + take] = fea[:take]
+            done += take
+            print('%d/%d features extracted... %.2fms elapsed' % (done, num_images, (time.time() - start_time) * 1000))
     finally:
         # orderly shutdown: producer thread joined, decode workers reaped, device drained (see train.py _run_and_leave)
         try:                                    # never raise from a finally block: a checkpoint / device error on its way out must stay the one reported

@@ -731,6 +731,45 @@ int fte_set_pair_scores(const float* x, int n, int d, const int32_t* members, in
                         const int32_t* tmpl_off, int n_templates, const int32_t* ta, const int32_t* tb, int npairs, const float* betas,
                         int nbetas, float* out, void* stream);
 
+/* ---- MegaFace (challenge 1 style million-distractor identification and verification; verify.py --protocol megaface,
+ * DESIGN.md 4.12) ----
+ * The protocol, which the host side (verification.py megaface_*) implements on these two calls:
+ *   probe set: the FaceScrub rows with labels; distractors: rows of a path-only list, row i = line i.  Noise removal drops a
+ *   distractor whose path equals a listed path or ends with "/" + that path, before anything else.  Size N: the first N kept
+ *   distractor rows in list order (a size above the kept count is capped to it).
+ *   genuine pairs: every ordered pair (p, g) of distinct FaceScrub rows with the same label.
+ *   rank of (p, g) at size N: 1 + #{d < N : s(p, d) >= s(p, g)}: TIES COUNT AGAINST THE GENUINE PAIR.  CMC(k) at size N: the
+ *   fraction of pairs with rank <= k.
+ *   verification at size N: genuine = unordered same-label FaceScrub pairs, impostor = every (FaceScrub row, distractor d < N)
+ *   pair, TAR at FAR from fte_score_histograms-binned histograms.
+ * Scores are fp32 cosines of normalised rows on v_mfma_f32_32x32x2_f32 with the probe on the lane side and the other row on the
+ * register side, in the k order of the other evaluation products (fixed by d alone).  s(p, g) from fte_megaface_pair_scores and
+ * s(p, d) inside fte_megaface_scan are the same arithmetic: a distractor that is a bitwise copy of g ties exactly and counts,
+ * wherever it falls. */
+
+/* out[j] = s(probes[ip[j]], rows[ig[j]]) for j < npairs, in the scan's arithmetic (above).  probes [m, d] and rows [n, d]
+ * normalised, d % 32 == 0.  An index outside [0, m) or [0, n) gives out[j] = NaN, never an out-of-bounds read.
+ * FTE_EINVAL: a NULL pointer, m, n or npairs < 1, d < 32 or d % 32, or a tensor of 2 GiB or more. */
+int fte_megaface_pair_scores(const float* probes, int m, const float* rows, int n, int d, const int32_t* ip, const int32_t* ig,
+                             int npairs, float* out, void* stream);
+/* Fused rank count + impostor histogram of probes [m, d] against one range of distractor rows [n, d] (both normalised,
+ * d % 32 == 0), with no score matrix.  Each probe's genuine scores, sorted DESCENDING, are an int32 CSR list: probe p has
+ * thresholds thr[thr_off[p] .. thr_off[p + 1]) (thr_off [m + 1], thr [nthr], fp32).  The call ACCUMULATES (+=):
+ *     counts[j] += #{rows r of the range : s(p, r) >= thr[j]}       for every threshold j of every probe p   (uint64 [nthr])
+ *     hist[bin(s(p, r))] += 1                                       for every probe p and row r              (uint64 [nbins])
+ * with bin() the fte_score_histograms formula, nbins a power of two in 256..8192.  The host scans each size bucket
+ * [N_{b-1}, N_b) as its own range (or several chunks of it) and sums; every count is an integer, so the result does not depend
+ * on order, chunking or the launch geometry.  A probe whose list is bad (thr_off[p] > thr_off[p + 1], or outside 0..nthr) or
+ * empty is SKIPPED for the counts (its slots are left as they are) but its scores still enter hist; a list that is not sorted
+ * descending gives wrong counts for that probe, never an out-of-bounds access.  ws (>= fte_megaface_scan_ws_bytes) holds a
+ * uint64 per threshold: survivors of a fast reject against the probe's smallest threshold are counted at the first threshold
+ * they reach, and a second kernel turns those into the prefix sums.  ws is cleared by the call (hipMemsetAsync on the stream).
+ * FTE_EINVAL: a NULL pointer (ws excepted), m, n or nthr < 1, d < 32 or d % 32, a bad nbins, or a tensor of 2 GiB or more.
+ * FTE_EWORKSPACE: ws NULL or short. */
+size_t fte_megaface_scan_ws_bytes(int m, int nthr);
+int fte_megaface_scan(const float* probes, int m, const float* rows, int n, int d, const int32_t* thr_off, const float* thr, int nthr,
+                      int nbins, uint64_t* counts, uint64_t* hist, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

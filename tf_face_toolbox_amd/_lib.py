@@ -125,6 +125,9 @@ _SIGS = {
     'fte_score_histograms': (c_int, [_P, _P, c_int, _P, _P] + [c_int] * 4 + [_P] * 3),
     'fte_template_pool': (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
     'fte_set_pair_scores': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P]),
+    'fte_megaface_pair_scores': (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
+    'fte_megaface_scan_ws_bytes': (c_size_t, [c_int] * 2),
+    'fte_megaface_scan': (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     'fte_dwconv3x3_fwd': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_dgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_wgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P, c_size_t, _P]),

@@ -1876,4 +1876,25 @@ int fte_set_pair_scores(const float* x, int n, int d, const int32_t* members, in
     return rc(s_set_pair_scores(x, n, d, members, n_members, media_off, n_media, tmpl_off, n_templates, ta, tb, npairs, betas, nbetas, out,
                                 (hipStream_t)stream));
 }
+
+int fte_megaface_pair_scores(const float* probes, int m, const float* rows, int n, int d, const int32_t* ip, const int32_t* ig, int npairs,
+                             float* out, void* stream) {
+    if (!probes || !rows || !ip || !ig || !out || m < 1 || n < 1 || d < 32 || d % 32 || npairs < 1 || !below_2g(m, d) || !below_2g(n, d) ||
+        !below_2g(npairs, 1))
+        return FTE_EINVAL;
+    return rc(s_mf_pair_scores(probes, m, rows, n, d, ip, ig, npairs, out, (hipStream_t)stream));
+}
+size_t fte_megaface_scan_ws_bytes(int m, int nthr) {
+    if (m < 1 || nthr < 1) return 0;
+    return s_mf_scan_ws_bytes(nthr);
+}
+int fte_megaface_scan(const float* probes, int m, const float* rows, int n, int d, const int32_t* thr_off, const float* thr, int nthr,
+                      int nbins, uint64_t* counts, uint64_t* hist, void* ws, size_t ws_bytes, void* stream) {
+    if (!probes || !rows || !thr_off || !thr || !counts || !hist || m < 1 || n < 1 || d < 32 || d % 32 || nthr < 1 || nbins < 256 ||
+        nbins > 8192 || (nbins & (nbins - 1)) || !below_2g(m, d) || !below_2g(n, d) || !below_2g(m + 1L, 1) || !below_2g(nthr, 2))
+        return FTE_EINVAL;
+    if (!ws || ws_bytes < s_mf_scan_ws_bytes(nthr)) return FTE_EWORKSPACE;
+    return rc(s_mf_scan(probes, m, rows, n, d, thr_off, thr, nthr, nbins, (unsigned long long*)counts, (unsigned long long*)hist, ws,
+                        (hipStream_t)stream));
+}
 }  // extern "C"

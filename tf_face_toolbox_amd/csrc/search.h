@@ -1,5 +1,5 @@
 // search.h -- evaluation kernels (search.hip): row normalisation, listed-pair scores, fused similarity + top-k, fused
-// similarity + score histograms, template pooling and set-to-set softmax score fusion.  fp32 throughout (v_mfma_f32_32x32x2_f32,
+// similarity + score histograms, template pooling, set-to-set softmax score fusion and the MegaFace rank / impostor scan.  fp32 throughout (v_mfma_f32_32x32x2_f32,
 // v_mfma_f32_16x16x4_f32); fte_set_mfma_dtype does not apply.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,3 +22,8 @@ hipError_t s_template_pool(const float* x, const float* w, int n, int d, const i
 hipError_t s_set_pair_scores(const float* x, int n, int d, const int32_t* members, int n_members, const int32_t* media_off, int n_media,
                              const int32_t* tmpl_off, int n_templates, const int32_t* ta, const int32_t* tb, int npairs,
                              const float* betas, int nbetas, float* out, hipStream_t st);
+hipError_t s_mf_pair_scores(const float* probes, int m, const float* rows, int n, int d, const int32_t* ip, const int32_t* ig, int npairs,
+                            float* out, hipStream_t st);
+size_t s_mf_scan_ws_bytes(int nthr);
+hipError_t s_mf_scan(const float* probes, int m, const float* rows, int n, int d, const int32_t* thr_off, const float* thr, int nthr,
+                     int nbins, unsigned long long* counts, unsigned long long* hist, void* ws, hipStream_t st);

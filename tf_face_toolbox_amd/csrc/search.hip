@@ -494,6 +494,166 @@ __global__ __launch_bounds__(256) void set_pair_scores_kernel(const float* __res
     if (lane == 0) out[p] = tot / (float)nb;
 }
 
+// ---------------------------------------------------------------- MegaFace: genuine scores, fused rank count + impostor histogram
+// Both kernels use dot_tiles' operand orientation and k order (probes on the lanes, the other rows through the registers, lane
+// (r, h) at k = 32q + 16h + 4u, MFMA t = 4u + e), for NP lane-side blocks and NT register-side tiles at once: every accumulator
+// is the same MFMA chain over the same operands, so a genuine score s(p, g) is bitwise the scan's s(p, d) for a copy d of g.
+template <int NP, int NT>
+__device__ __forceinline__ void dot_blocks(const float* const (&bp)[NP], const float* const (&ap)[NT], int d, f32x16 (&acc)[NP][NT]) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[p][t][i] = 0.f;
+    float4 B[NP][4], A[NT][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) B[p][u] = *(const float4*)(bp[p] + 4 * u);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) A[t][u] = *(const float4*)(ap[t] + 4 * u);
+    }
+    for (int q = 0; q < d; q += 32) {
+        float4 Bc[NP][4], Ac[NT][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) Bc[p][u] = B[p][u];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) Ac[t][u] = A[t][u];
+        }
+        if (q + 32 < d) {                    // next k block in flight while this one multiplies
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) B[p][u] = *(const float4*)(bp[p] + q + 32 + 4 * u);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) A[t][u] = *(const float4*)(ap[t] + q + 32 + 4 * u);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const float b4[4] = {Bc[p][u].x, Bc[p][u].y, Bc[p][u].z, Bc[p][u].w};
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const float a4[4] = {Ac[t][u].x, Ac[t][u].y, Ac[t][u].z, Ac[t][u].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[p][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], acc[p][t], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+// One wave per 32 listed pairs: pair j's probe row on lane column j, its target row on register row j, the score on the diagonal
+// (row j sits in lane (j, (j >> 2) & 1), register (j & 3) + 4 (j >> 3)).  A row index outside its set gives NaN.
+__global__ __launch_bounds__(256) void mf_pair_scores_kernel(const float* __restrict__ P, int m, const float* __restrict__ G, int n, int d,
+                                                             const int32_t* __restrict__ ip, const int32_t* __restrict__ ig, int np,
+                                                             float* __restrict__ out) {
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    if (w * 32 >= np) return;
+    const int pair = min(w * 32 + r, np - 1);
+    const int a = ip[pair], b = ig[pair];
+    const bool ok = a >= 0 && a < m && b >= 0 && b < n;
+    const float* bp[1] = {P + (long)(ok ? a : 0) * d + 16 * h};
+    const float* ap[1] = {G + (long)(ok ? b : 0) * d + 16 * h};
+    f32x16 acc[1][1];
+    dot_blocks<1, 1>(bp, ap, d, acc);
+    if (h != ((r >> 2) & 1) || w * 32 + r >= np) return;
+    const int want = (r & 3) + 4 * (r >> 3);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (i == want) s = acc[0][0][i];
+    out[pair] = ok ? s : __builtin_nanf("");
+}
+
+// The scan.  Four waves per block share one LDS uint32 impostor histogram; waves stride over (MP-probe block, 64-row step) tiles,
+// probe block fastest, so a 64-row step of the distractors is read from HBM once and met by every probe block while it is in L2.
+// A wave holds MF_PB 32-probe blocks sharing each distractor operand.  Per probe a lane keeps its smallest genuine score (the CSR
+// list is sorted descending): a score below it counts nowhere, which is nearly every score of a trained model.  A survivor
+// binary-searches the probe's list for the first threshold it reaches and adds 1 there (ws, uint64); mf_prefix_kernel turns those
+// into the counts.  Integer adds only: the results do not depend on the order.
+constexpr int MF_PB = 2;               // 32-probe blocks per wave
+constexpr int MF_MP = 32 * MF_PB;      // probes per tile
+
+__global__ __launch_bounds__(256) void mf_scan_kernel(const float* __restrict__ P, int m, const float* __restrict__ G, int n, int d,
+                                                      const int32_t* __restrict__ thr_off, const float* __restrict__ thr, int T,
+                                                      int nbins, long ntiles, int npb, unsigned long long* __restrict__ first,
+                                                      unsigned long long* __restrict__ hist) {
+    extern __shared__ unsigned hl[];
+    for (int i = threadIdx.x; i < nbins; i += 256) hl[i] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wave = threadIdx.x >> 6;
+    const float half = 0.5f * nbins;
+    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
+        const int p0 = (int)(tile % npb) * MF_MP, g0 = (int)(tile / npb) * 64;
+        const float* bp[MF_PB];
+        int o0[MF_PB], o1[MF_PB];
+        float tmin[MF_PB];
+        bool pv[MF_PB];
+#pragma unroll
+        for (int p = 0; p < MF_PB; ++p) {
+            const int probe = p0 + 32 * p + r;
+            pv[p] = probe < m;
+            const int pc = min(probe, m - 1);
+            bp[p] = P + (long)pc * d + 16 * h;
+            o0[p] = thr_off[pc];
+            o1[p] = thr_off[pc + 1];
+            const bool ok = pv[p] && 0 <= o0[p] && o0[p] < o1[p] && o1[p] <= T;    // bad or empty list: counts nowhere
+            if (!ok) o0[p] = o1[p] = 0;
+            tmin[p] = ok ? thr[o1[p] - 1] : 0.f;
+        }
+        const float* ap[TG];
+#pragma unroll
+        for (int t = 0; t < TG; ++t) ap[t] = G + (long)min(g0 + 32 * t + r, n - 1) * d + 16 * h;
+        f32x16 acc[MF_PB][TG];
+        dot_blocks<MF_PB, TG>(bp, ap, d, acc);
+#pragma unroll
+        for (int p = 0; p < MF_PB; ++p)
+#pragma unroll
+            for (int t = 0; t < TG; ++t)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int row = g0 + 32 * t + acc_row(i, h);
+                    if (!pv[p] || row >= n) continue;
+                    const float s = acc[p][t][i];
+                    atomicAdd(&hl[min(max((int)((s + 1.0f) * half), 0), nbins - 1)], 1u);
+                    if (o1[p] > o0[p] && s >= tmin[p]) {
+                        int lo = o0[p], hi = o1[p];              // first j in [o0, o1) with thr[j] <= s
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            if (thr[mid] <= s) hi = mid;
+                            else lo = mid + 1;
+                        }
+                        if (lo < o1[p]) atomicAdd(&first[lo], 1ull);
+                    }
+                }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nbins; i += 256) {
+        const unsigned v = hl[i];
+        if (v) atomicAdd(&hist[i], (unsigned long long)v);
+    }
+}
+
+// counts[j] += sum of first[o0 .. j] over each probe's list (one thread per probe, in list order); a bad list is skipped
+__global__ __launch_bounds__(256) void mf_prefix_kernel(const int32_t* __restrict__ thr_off, int m, int T,
+                                                        const unsigned long long* __restrict__ first, unsigned long long* __restrict__ counts) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= m) return;
+    const int o0 = thr_off[p], o1 = thr_off[p + 1];
+    if (!(0 <= o0 && o0 < o1 && o1 <= T)) return;
+    unsigned long long run = 0;
+    for (int j = o0; j < o1; ++j) {
+        run += first[j];
+        counts[j] += run;
+    }
+}
+
 }  // namespace
 
 hipError_t s_normalize_rows(const float* x, float* y, float* norms, int n, int d, hipStream_t st) {
@@ -566,5 +726,33 @@ hipError_t s_set_pair_scores(const float* x, int n, int d, const int32_t* member
     for (int k = 0; k < nbetas && k < MAXB; ++k) bc.c[k] = betas[k] * 1.44269504088896340736f;     // beta * log2(e), rounded once
     set_pair_scores_kernel<<<(npairs + 3) / 4, 256, 0, st>>>(x, n, d, members, n_members, media_off, n_media, tmpl_off, n_templates, ta, tb,
                                                              npairs, bc, nbetas, out);
+    return hipGetLastError();
+}
+
+hipError_t s_mf_pair_scores(const float* probes, int m, const float* rows, int n, int d, const int32_t* ip, const int32_t* ig, int npairs,
+                            float* out, hipStream_t st) {
+    const int waves = (npairs + 31) / 32;
+    mf_pair_scores_kernel<<<(waves + 3) / 4, 256, 0, st>>>(probes, m, rows, n, d, ip, ig, npairs, out);
+    return hipGetLastError();
+}
+
+size_t s_mf_scan_ws_bytes(int nthr) { return (size_t)nthr * sizeof(unsigned long long); }
+
+hipError_t s_mf_scan(const float* probes, int m, const float* rows, int n, int d, const int32_t* thr_off, const float* thr, int nthr,
+                     int nbins, unsigned long long* counts, unsigned long long* hist, void* ws, hipStream_t st) {
+    unsigned long long* first = (unsigned long long*)ws;
+    hipError_t e = hipMemsetAsync(first, 0, s_mf_scan_ws_bytes(nthr), st);
+    if (e != hipSuccess) return e;
+    const int npb = (m + MF_MP - 1) / MF_MP;
+    const long ntiles = (long)npb * ((n + 63) / 64);
+    long blocks = 2L * igemm_num_cus();
+    const long per_block_cap = (1L << 31) / (64L * MF_MP);  // tiles per block: its uint32 bins see at most 2^31 scores
+    if (blocks < (ntiles + per_block_cap - 1) / per_block_cap) blocks = (ntiles + per_block_cap - 1) / per_block_cap;
+    if (blocks > (ntiles + 3) / 4) blocks = (ntiles + 3) / 4;
+    mf_scan_kernel<<<(unsigned)blocks, 256, (size_t)nbins * sizeof(unsigned), st>>>(probes, m, rows, n, d, thr_off, thr, nthr, nbins, ntiles,
+                                                                                    npb, first, hist);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    mf_prefix_kernel<<<(m + 255) / 256, 256, 0, st>>>(thr_off, m, nthr, first, counts);
     return hipGetLastError();
 }

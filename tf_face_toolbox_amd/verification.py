@@ -1,11 +1,13 @@
-"""Face verification and 1:N identification scoring of extracted embeddings (verify.py; DESIGN.md 4.10, 4.11).
+"""Face verification and 1:N identification scoring of extracted embeddings (verify.py; DESIGN.md 4.10, 4.11, 4.12).
 
 Device side (torch CUDA tensors in): every product and reduction is a libfte.so call (include/fte.h, "Evaluation: similarity
 search and score statistics"); there is no torch fallback for the arithmetic.  torch only allocates, pads and stacks.
 
 Host side (numpy, importable without a GPU): the LFW pairs.txt parser and row mapping, the 10-fold accuracy protocol, TAR@FAR
 from score histograms, and CMC from top-k indices; for templates (IJB-style sets of images grouped into media): the metadata and
-template-pair parsers, the CSR grouping the kernels take, exact TAR@FAR from listed scores and open-set identification."""
+template-pair parsers, the CSR grouping the kernels take, exact TAR@FAR from listed scores and open-set identification; for
+MegaFace (FaceScrub probes against up to a million distractors): the genuine-pair CSR, noise removal, distractor sizes, ranks -> CMC
+and the per-size TAR table."""
 import csv
 import ctypes
 import os
@@ -217,6 +219,93 @@ def set_pair_scores(x, members, media_off, tmpl_off, ta, tb, betas=range(0, 21))
     res = torch.empty_like(out)
     res[order] = out
     return res
+
+
+def megaface_pair_scores(probes, ip, ig, rows=None):
+    """s(probes[ip[j]], rows[ig[j]]) float32 [npairs] (fte_megaface_pair_scores), in fte_megaface_scan's arithmetic; rows=None:
+    the probe set itself (the MegaFace genuine pairs).  probes / rows: normalised [*, d], d % 32 == 0."""
+    import torch
+    rows = probes if rows is None else rows
+    _check_x(probes, 'megaface_pair_scores')
+    _check_x(rows, 'megaface_pair_scores')
+    m, d = probes.shape
+    if rows.shape[1] != d or d % 32:
+        raise ValueError('megaface_pair_scores: probes %s and rows %s need the same d, a multiple of 32' % (tuple(probes.shape), tuple(rows.shape)))
+    dev = probes.device
+    ip, ig = _i32(ip, dev).reshape(-1), _i32(ig, dev).reshape(-1)
+    if ip.shape != ig.shape or ip.numel() < 1:
+        raise ValueError('megaface_pair_scores: ip and ig must be equal, non-empty lists')
+    out = torch.empty(ip.numel(), dtype=torch.float32, device=dev)
+    probes, rows = probes.contiguous(), rows.contiguous()
+    _lib.call('fte_megaface_pair_scores', probes, m, rows, rows.shape[0], d, ip, ig, ip.numel(), out, _stream())
+    return out
+
+
+def megaface_scan(probes, distractors, sizes, thr_off, thr, nbins=8192, chunk_rows=None):
+    """Fused rank count + impostor histogram (fte_megaface_scan) of probes [m, d] against the first N rows of distractors for
+    every N in `sizes` (ascending, each <= len(distractors)), in one pass: bucket [N_{b-1}, N_b) is scanned as its own range (in
+    chunks below 2 GiB, or of about `chunk_rows` rows) and the buckets are summed on the host.  thr_off [m + 1] / thr [T]: each
+    probe's genuine scores sorted descending (megaface_thresholds).  Returns (counts uint64 [len(sizes), T]: counts[b, j] =
+    #{d < N_b : s(p, d) >= thr[j]}, hist uint64 [len(sizes), nbins]: the impostor histogram of probes x distractors[:N_b])."""
+    import torch
+    m, d = probes.shape
+    n = distractors.shape[0]
+    if distractors.shape[1] != d or d % 32:
+        raise ValueError('megaface_scan: probes %s and distractors %s need the same d, a multiple of 32'
+                         % (tuple(probes.shape), tuple(distractors.shape)))
+    if nbins < 256 or nbins > 8192 or nbins & (nbins - 1):
+        raise ValueError('megaface_scan: nbins = %d is not a power of two in 256..8192' % nbins)
+    sizes = [int(v) for v in sizes]
+    if not sizes or sizes[0] < 1 or sizes[-1] > n or any(b <= a for a, b in zip(sizes, sizes[1:])):
+        raise ValueError('megaface_scan: sizes %s must ascend strictly within 1..%d' % (sizes, n))
+    dev = probes.device
+    off = _i32(thr_off, dev).reshape(-1)
+    if off.numel() != m + 1:
+        raise ValueError('megaface_scan: thr_off has %d entries for %d probes' % (off.numel(), m))
+    T = len(thr)
+    t = (thr if isinstance(thr, torch.Tensor) else torch.as_tensor(np.asarray(thr, np.float32))).to(device=dev, dtype=torch.float32)
+    if T == 0:                                      # no genuine pair: one unused slot that no probe's list reaches
+        t = torch.zeros(1, dtype=torch.float32, device=dev)
+    t = t.contiguous()
+    nt = t.numel()
+    rows = chunk_rows or _default_rows(d)
+    if 2 * rows * d * 4 > _TENSOR_LIMIT:
+        rows = _default_rows(d)
+    probes, distractors = probes.contiguous(), distractors.contiguous()
+    wsb = _lib.query('fte_megaface_scan_ws_bytes', m, nt)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    cnt = torch.zeros(len(sizes), nt, dtype=torch.int64, device=dev)
+    hist = torch.zeros(len(sizes), nbins, dtype=torch.int64, device=dev)
+    st = _stream()
+    lo = 0
+    for b, hi in enumerate(sizes):
+        for g0, g1 in _chunks(hi - lo, rows):
+            _lib.call('fte_megaface_scan', probes, m, distractors[lo + g0:lo + g1], g1 - g0, d, off, t, nt, nbins, cnt[b], hist[b],
+                      ws, wsb, st)
+        lo = hi
+    cnt = np.cumsum(cnt.cpu().numpy().astype(np.uint64), 0, dtype=np.uint64)
+    hist = np.cumsum(hist.cpu().numpy().astype(np.uint64), 0, dtype=np.uint64)
+    return cnt[:, :T], hist
+
+
+def megaface_evaluate(probes, labels, distractors, sizes, nbins=8192, chunk_rows=None):
+    """The MegaFace protocol (fte.h "MegaFace") on normalised device rows: FaceScrub probes [m, d] with int labels against the
+    first N kept distractor rows for each N of `sizes` (already capped, ascending: megaface_sizes).  Returns a dict: pairs,
+    singletons, scores float32 [pairs] and rank int64 [len(sizes), pairs] in genuine-pair order (megaface_pairs), genuine_hist
+    uint64 [nbins] (the unordered same-label pairs of the probe set) and impostor_hist uint64 [len(sizes), nbins]."""
+    if len(labels) != probes.shape[0]:
+        raise ValueError('megaface: %d labels for %d probe rows' % (len(labels), probes.shape[0]))
+    ip, ig, off, singles = megaface_pairs(labels)
+    if len(ip):
+        scores = megaface_pair_scores(probes, ip, ig).cpu().numpy()
+    else:
+        scores = np.zeros(0, np.float32)
+    thr, perm = megaface_thresholds(scores, off)
+    counts, hist = megaface_scan(probes, distractors, sizes, off, thr, nbins, chunk_rows)
+    rank = np.empty((len(sizes), len(ip)), np.int64)
+    rank[:, perm] = counts.astype(np.int64) + 1
+    hg, _ = score_histograms(probes, labels, nbins, chunk_rows)
+    return {'pairs': len(ip), 'singletons': singles, 'scores': scores, 'rank': rank, 'genuine_hist': hg, 'impostor_hist': hist}
 
 
 # ------------------------------------------------------------------ host side: protocols
@@ -522,3 +611,97 @@ def open_set_identification(top_scores, top_index, probe_subjects, gallery_subje
         tpir = float(np.mean((first[mated] == 0) & (top1[mated] > thr)))
         tp.append({'fpir': fpir, 'tpir': tpir, 'achieved_fpir': float(np.mean(neg > thr)), 'threshold': float(thr)})
     return {'mated': nm, 'non_mated': int((~mated).sum()), 'cmc': cmc_, 'tpir_at_fpir': tp}
+
+
+# ------------------------------------------------------------------ host side: MegaFace (challenge 1 style)
+MEGAFACE_SIZES = (10, 100, 1000, 10000, 100000, 1000000)
+MEGAFACE_RANKS = (1, 5, 10, 100, 1000, 10000, 100000, 1000000)
+
+
+def megaface_pairs(labels):
+    """The genuine pairs: every ordered pair (p, g) of distinct rows with the same label, probe-major, targets ascending.
+    Returns (ip int64, ig int64, off int64 [n + 1]: probe p's pairs are off[p] .. off[p + 1] - 1, singletons: the number of
+    labels with a single row, which add no pair)."""
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    n = len(labels)
+    _, inv, cnt = np.unique(labels, return_inverse=True, return_counts=True)
+    order = np.argsort(inv, kind='stable')                  # rows grouped by label, ascending within a label
+    start = np.concatenate([[0], np.cumsum(cnt)])
+    per = cnt[inv] - 1                                      # pairs of each probe
+    off = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    ip = np.repeat(np.arange(n, dtype=np.int64), per)
+    ig = np.empty(off[-1], np.int64)
+    for p in range(n):
+        grp = order[start[inv[p]]:start[inv[p] + 1]]
+        ig[off[p]:off[p + 1]] = grp[grp != p]
+    return ip, ig, off, int(np.sum(cnt == 1))
+
+
+def megaface_thresholds(scores, off):
+    """The scan's CSR thresholds: each probe's genuine scores (pair order of megaface_pairs) sorted descending, ties in pair
+    order.  Returns (thr float32 [T], perm int64 [T]): thr[j] = scores[perm[j]]; thr_off is `off`."""
+    scores = np.asarray(scores, np.float32).reshape(-1)
+    off = np.asarray(off, np.int64)
+    probe = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    perm = np.lexsort((np.arange(len(scores)), -scores.astype(np.float64), probe)).astype(np.int64)
+    return scores[perm], perm
+
+
+def _path_key(p):
+    return p.replace('\\', '/').strip()
+
+
+def megaface_exclude(paths, exclude):
+    """Noise removal: a keep mask over the distractor list.  Row i goes when paths[i] equals a listed path or ends with '/' +
+    a listed path."""
+    ex = set(_path_key(e) for e in exclude if _path_key(e))
+    keep = np.ones(len(paths), bool)
+    for i, p in enumerate(paths):
+        p = _path_key(p)
+        if p in ex:
+            keep[i] = False
+            continue
+        j = p.find('/')
+        while j >= 0:
+            if p[j + 1:] in ex:
+                keep[i] = False
+                break
+            j = p.find('/', j + 1)
+    return keep
+
+
+def megaface_sizes(sizes, kept):
+    """The distractor sizes to report: each requested size capped to the kept count, ascending, each once.  Returns
+    [(N, capped)]; capped is True when N stands for a larger request."""
+    req = sorted(set(int(v) for v in sizes))
+    if not req or req[0] < 1:
+        raise ValueError('megaface: distractor sizes must be positive, got %s' % (list(sizes),))
+    if kept < 1:
+        raise ValueError('megaface: no distractor row is left')
+    out = []
+    for v in req:
+        N, capped = min(v, kept), v > kept
+        if out and out[-1][0] == N:
+            continue
+        out.append((N, capped))
+    return out
+
+
+def megaface_cmc(rank, ranks):
+    """CMC(k) = the fraction of genuine pairs with rank <= k, for each k of ranks: {k: fraction} ('n/a' with no pair)"""
+    rank = np.asarray(rank, np.int64)
+    return {int(k): (float(np.mean(rank <= k)) if rank.size else 'n/a') for k in ranks}
+
+
+def megaface_report_ranks(N, extra=()):
+    """The ranks reported at size N: MEGAFACE_RANKS (and `extra`) up to N + 1, the largest rank a pair can have"""
+    return tuple(sorted(set(k for k in tuple(MEGAFACE_RANKS) + tuple(extra) if k <= N + 1)))
+
+
+def megaface_tar_table(hist_genuine, impostor_hists, sizes, fars=(1e-6, 1e-5, 1e-4, 1e-3)):
+    """Per size N: tar_at_far of the genuine histogram against that size's impostor histogram.  Returns [{'size': N, 'impostor':
+    n_imp, 'tar_at_far': [...]}]."""
+    out = []
+    for N, hi in zip(sizes, impostor_hists):
+        out.append({'size': int(N), 'impostor': int(np.asarray(hi, np.uint64).sum()), 'tar_at_far': tar_at_far(hist_genuine, hi, fars)})
+    return out

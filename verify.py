@@ -8,9 +8,14 @@
                         templates of --template_metadata compared by pooled features (--fusion pool) or by set-to-set softmax
                         score fusion (--fusion softmax);
   --protocol template_search  IJB-style open-set 1:N search of pooled probe templates (--template_metadata) against pooled
-                        gallery templates (--gallery_metadata): rank-1 / 5 / 10, the CMC and TPIR at FPIR 0.01 / 0.1.
+                        gallery templates (--gallery_metadata): rank-1 / 5 / 10, the CMC and TPIR at FPIR 0.01 / 0.1;
+  --protocol megaface   MegaFace challenge-1 style: the labelled set (FaceScrub) against the first N rows of
+                        --distractor_feature_path / --distractor_list_path for each N of --distractor_sizes (after removing the
+                        rows of --distractor_exclude): per size the rank-1 rate and CMC of every ordered same-label pair (ties
+                        count against the pair) and TAR at FAR 1e-6 .. 1e-3 with set x distractor impostors.
 A `{split}` in any path with --splits (e.g. 1-10) runs every split and reports the mean and std over them.
-The products, top-k, histograms, pooling and fusion run on the GPU (tf_face_toolbox_amd.verification)."""
+The products, top-k, histograms, pooling, fusion and the MegaFace scan run on the GPU (tf_face_toolbox_amd.verification,
+DESIGN.md 4.10 - 4.12)."""
 import argparse
 import json
 import os
@@ -26,14 +31,14 @@ if ROOT not in sys.path:
 
 def build_parser():
     parser = argparse.ArgumentParser(description='Face verification / identification scoring of evaluate.py features.')
-    parser.add_argument('--protocol', type=str, required=True, choices=('pairs', 'all_pairs', 'identify', 'templates', 'template_search'), help='Scoring protocol.')
+    parser.add_argument('--protocol', type=str, required=True, choices=('pairs', 'all_pairs', 'identify', 'templates', 'template_search', 'megaface'), help='Scoring protocol.')
     parser.add_argument('--feature_path', type=str, required=True, help='.mat file written by evaluate.py (variable wfea).')
     parser.add_argument('--data_list_path', type=str, required=True, help='The list evaluate.py extracted the features from.')
     parser.add_argument('--pairs_path', type=str, help='pairs.txt of the pairs protocol.')
     parser.add_argument('--folds', type=int, default=0, help='Folds of the pairs protocol (default: the pairs.txt header).')
     parser.add_argument('--gallery_feature_path', type=str, help='identify: .mat of the gallery (default: leave-one-out).')
     parser.add_argument('--gallery_list_path', type=str, help='identify: list of the gallery.')
-    parser.add_argument('--nbins', type=int, default=8192, help='all_pairs: histogram bins over [-1, 1].')
+    parser.add_argument('--nbins', type=int, default=8192, help='all_pairs / megaface: histogram bins over [-1, 1].')
     parser.add_argument('--chunk_rows', type=int, default=0, help='Rows per chunk handed to the library (default: below 2 GiB).')
     parser.add_argument('--template_metadata', type=str, help='templates / template_search: IJB-style metadata CSV of the set '
                         '(columns TEMPLATE_ID, SUBJECT_ID, FILE, MEDIA_ID; the probe set of template_search).')
@@ -44,6 +49,12 @@ def build_parser():
                         'a comma list; 1..32 values in [0, 40].')
     parser.add_argument('--weight_column', type=str, help='templates / template_search: metadata column of per-image pooling weights.')
     parser.add_argument('--gallery_metadata', type=str, help='template_search: metadata CSV of the gallery templates.')
+    parser.add_argument('--distractor_feature_path', type=str, help='megaface: .mat of the distractor features (wfea).')
+    parser.add_argument('--distractor_list_path', type=str, help='megaface: the distractor list (paths only; row i = line i).')
+    parser.add_argument('--distractor_exclude', type=str, help='megaface: noise list, one path per line; a distractor whose path '
+                        'equals one or ends with / + one is dropped before anything else.')
+    parser.add_argument('--distractor_sizes', type=str, default='10,100,1000,10000,100000,1000000',
+                        help='megaface: distractor set sizes N (the first N kept rows); a size above the kept count is capped.')
     parser.add_argument('--splits', type=str, help='Values of {split} in the paths: `1-10` or a comma list (default: one run).')
     parser.add_argument('--output_json', type=str, help='Also write the results as JSON to this path.')
     return parser
@@ -163,6 +174,58 @@ def run_template_search(FLAGS, split):
             'non_mated': res['non_mated'], 'cmc': {str(r): v for r, v in res['cmc'].items()}, 'tpir_at_fpir': res['tpir_at_fpir']}
 
 
+def run_megaface(FLAGS):
+    """--protocol megaface"""
+    from tf_face_toolbox_amd import verification as V
+    from tf_face_toolbox_amd.data import get_image_paths
+    if not FLAGS.distractor_feature_path or not FLAGS.distractor_list_path:
+        raise SystemExit('--protocol megaface needs --distractor_feature_path and --distractor_list_path')
+    feats = _features(FLAGS.feature_path)
+    _, labels = _labels(FLAGS.data_list_path)
+    if len(labels) != feats.shape[0]:
+        raise SystemExit('%s has %d rows, %s lists %d images' % (FLAGS.feature_path, feats.shape[0], FLAGS.data_list_path, len(labels)))
+    dfeats = _features(FLAGS.distractor_feature_path)
+    dpaths, nd = get_image_paths(FLAGS.distractor_list_path)
+    if nd != dfeats.shape[0]:
+        raise SystemExit('%s has %d rows, %s lists %d paths' % (FLAGS.distractor_feature_path, dfeats.shape[0], FLAGS.distractor_list_path, nd))
+    if dfeats.shape[1] != feats.shape[1]:
+        raise SystemExit('megaface: the probe features are %d wide, the distractors %d' % (feats.shape[1], dfeats.shape[1]))
+    excluded = 0
+    if FLAGS.distractor_exclude:
+        keep = V.megaface_exclude(dpaths, get_image_paths(FLAGS.distractor_exclude)[0])
+        excluded = int((~keep).sum())
+        dfeats = dfeats[keep]
+    print('megaface: %d distractors listed, %d removed by %s, %d kept' % (nd, excluded, FLAGS.distractor_exclude or 'no noise list',
+                                                                         dfeats.shape[0]))
+    try:
+        sizes = V.megaface_sizes([int(v) for v in FLAGS.distractor_sizes.split(',') if v.strip()], dfeats.shape[0])
+    except ValueError as e:
+        raise SystemExit('verify.py: %s' % e)
+    Ns = [N for N, _ in sizes]
+    probes = _device_rows(feats)
+    r = V.megaface_evaluate(probes, labels, _device_rows(dfeats[:Ns[-1]]), Ns, FLAGS.nbins, FLAGS.chunk_rows or None)
+    ids = len(np.unique(labels))
+    print('%d probes of %d identities (%d with a single image add no pair), %d genuine pairs' % (len(labels), ids, r['singletons'], r['pairs']))
+    table = V.megaface_tar_table(r['genuine_hist'], r['impostor_hist'], Ns)
+    out = []
+    for b, (N, capped) in enumerate(sizes):
+        shown = V.megaface_cmc(r['rank'][b], V.megaface_report_ranks(N))
+        full = V.megaface_cmc(r['rank'][b], V.megaface_report_ranks(N, range(1, 11)))
+        print('size %d%s: rank-1 %s' % (N, ' (capped: fewer distractors kept than requested)' if capped else '', _fmt(shown[1])))
+        print('  CMC: ' + '  '.join('%d: %s' % (k, _fmt(v)) for k, v in shown.items()))
+        print('  %10s %10s %14s %10s' % ('FAR', 'TAR', 'achieved FAR', 'threshold'))
+        for t in table[b]['tar_at_far']:
+            if t['tar'] == 'n/a':
+                print('  %10.0e %10s %14s %10s' % (t['far'], 'n/a', 'n/a', 'n/a'))
+            else:
+                print('  %10.0e %10.4f %14.3e %10.4f' % (t['far'], t['tar'], t['achieved_far'], t['threshold']))
+        out.append({'size': N, 'capped': capped, 'rank1': full[1], 'cmc': {str(k): v for k, v in full.items()},
+                    'impostor': table[b]['impostor'], 'tar_at_far': table[b]['tar_at_far']})
+    return {'probes': len(labels), 'identities': ids, 'singletons': r['singletons'], 'genuine_pairs': r['pairs'],
+            'genuine': int(r['genuine_hist'].sum()), 'distractors': nd, 'excluded': excluded, 'kept': int(dfeats.shape[0]),
+            'sizes': out}
+
+
 def _fmt(v):
     return v if isinstance(v, str) else '%.4f' % v
 
@@ -217,6 +280,8 @@ def run(FLAGS):
     try:
         if FLAGS.protocol in ('templates', 'template_search'):
             res.update(run_template_protocol(FLAGS))
+        elif FLAGS.protocol == 'megaface':
+            res.update(run_megaface(FLAGS))
         elif FLAGS.protocol == 'pairs':
             feats = _features(FLAGS.feature_path)
             if not FLAGS.pairs_path:
