@@ -190,6 +190,20 @@ int fte_im2col_first_s16(const float* x, uint16_t* cols16, int n, int h, int wd,
  * (tf_face_toolbox_amd/_decode_worker.py).  The random draws stay on the host (they are the workers' seeded draws). */
 int fte_preprocess_u8(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
                       void* stream);
+/* The same transform followed by the colour augmentation of preprocessing.py:22-38 of the reference (train.py --augmentation 1)
+ * before the final (x - 0.5) / 0.5.  Same arguments, same refusals, same slots; the header words that fte_preprocess_u8 ignores
+ * carry the worker's draws:
+ *   hd[0..5]  {mode, h0, w0, y0, x0, flip}, as above
+ *   hd[6]     flag bits: 1 = brightness, 2 = hue, 4 = saturation (the host's `draw < 0.1 / 0.2 / 1.0` decisions, taken in float64)
+ *   hd[7]     float32 bits of the brightness delta   (x - delta; no clip of its own)
+ *   hd[8]     float32 bits of the hue delta          (clip to [0, 1], RGB -> HSV, h = (h - delta) mod 1, HSV -> RGB)
+ *   hd[9]     float32 bits of the saturation factor  (clip to [0, 1], RGB -> HSV, s = clip(s * factor, 0, 1), HSV -> RGB)
+ *   hd[10..15] 0
+ * Words 6..9 steer arithmetic only, never an address.  channels == 1: bits 2 and 4 are ignored.  Mode 1 slots hold the crop the
+ * worker finished, augmentation included, and are copied.  With hd[6] == 0 the output is fte_preprocess_u8's; every value is
+ * bit-equal to the host transform with augmentation = 1 (tf_face_toolbox_amd/preprocessing.py, float32 element by element). */
+int fte_preprocess_u8_aug(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
+                          int crop_w, void* stream);
 
 /* ---------------------------------------------------------------------------
  * layers.batch_norm(scale=True, center=True, fused=True, decay=0.999, epsilon=1e-3) in TRAINING mode

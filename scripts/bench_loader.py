@@ -3,9 +3,11 @@ crop / flip -> normalise -> NHWC float32 batch) in images/s at 112x112, on this 
 rate the GPU step consumes (~10 k images/s per MI355X in fp32, ~30 k in the bf16 mode).
 
     python scripts/bench_loader.py [--images 2048] [--batch 512] [--batches 60] [--warmup 24] [--src 250] [--device cpu|cuda]
+                                   [--augmentation 0|1]
 
 Writes N synthetic JPEGs of src x src pixels (CASIA-WebFace crops are 250 x 250) to a temporary directory, then times
-`data.train_inputs(...)` batches (resize to 128 x 128, random crop 112 x 112, flip): the same call train.py makes."""
+`data.train_inputs(...)` batches (resize to 128 x 128, random crop 112 x 112, flip; --augmentation 1: the colour augmentation of
+train.py --augmentation 1 as well): the same call train.py makes."""
 import argparse
 import os
 import sys
@@ -27,6 +29,7 @@ def main():
     ap.add_argument('--src', type=int, default=250)
     ap.add_argument('--device', default=None, help="default: cuda when a GPU is present (the training path: pinned staging ring + async copy), else cpu")
     ap.add_argument('--workers', type=int, default=None, help='decode worker processes (default: data.train_inputs picks; 0 = threads)')
+    ap.add_argument('--augmentation', type=int, choices=[0, 1], default=0, help='1: flip + brightness / hue / saturation (train.py --augmentation 1)')
     args = ap.parse_args()
     from tf_face_toolbox_amd import data
     if args.device is None:
@@ -42,7 +45,7 @@ def main():
             lines.append('%s %d' % (p, i % 100))
         lst = os.path.join(d, 'list.txt')
         open(lst, 'w').write('\n'.join(lines) + '\n')
-        inp = data.train_inputs(lst, 128, 128, 112, 112, is_color=1, batch_size=args.batch, device=args.device, seed=0, num_workers=args.workers)
+        inp = data.train_inputs(lst, 128, 128, 112, 112, is_color=1, augmentation=args.augmentation, batch_size=args.batch, device=args.device, seed=0, num_workers=args.workers)
         for _ in range(max(1, args.warmup)):             # warm-up: worker start, page cache -- and the prefetched batches (a short run
             inp['images'](); inp['labels']()             # timed right after start-up is served out of the filled pipe and reads 1.5-4x high)
         t0 = time.time()
@@ -53,9 +56,10 @@ def main():
             import torch
             torch.cuda.synchronize()
         el = time.time() - t0
-        print('loader: %.0f images/s sustained (%d batches of %d after %d untimed, %dx%d JPEG -> 128x128 -> crop 112x112, workers %s, os.cpu_count=%d, usable CPUs (affinity / cgroup quota) %d, device %s), batch %s %s'
+        print('loader: %.0f images/s sustained (%d batches of %d after %d untimed, %dx%d JPEG -> 128x128 -> crop 112x112, workers %s, os.cpu_count=%d, usable CPUs (affinity / cgroup quota) %d, device %s%s), batch %s %s'
               % (args.batches * args.batch / el, args.batches, args.batch, args.warmup, args.src, args.src,
-                 'auto' if args.workers is None else args.workers, os.cpu_count(), data.usable_cpus(), args.device, tuple(x.shape), x.dtype))
+                 'auto' if args.workers is None else args.workers, os.cpu_count(), data.usable_cpus(), args.device,
+                 ', augmentation 1, gpu_transform %s' % bool(inp['gpu_transform']) if args.augmentation else '', tuple(x.shape), x.dtype))
 
 
 if __name__ == '__main__':

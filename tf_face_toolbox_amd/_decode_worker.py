@@ -100,14 +100,16 @@ def train_example(path, num_channels, input_height, input_width, crop_height, cr
     return _finish(_load(path, num_channels), input_height, input_width, crop_height, crop_width, augmentation, rng)
 
 
-HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip} + padding (include/fte.h: fte_preprocess_u8)
+HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip}, the augmentation's {flags, float32 brightness,
+#                              hue, saturation} + padding (include/fte.h: fte_preprocess_u8, fte_preprocess_u8_aug)
 
 
-def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng):
+def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0):
     """The DECODED image and the draws of train_example() (seeded the same way, drawn in the same order) into one slot of a raw
     batch buffer -- resize / crop / flip / normalise then run on the GPU (fte_preprocess_u8) and give the bits train_example()
     gives.  rng None: the evaluation transform (full window, no flip).  An image too large for its slot is transformed here
-    and stored finished (mode 1)."""
+    and stored finished (mode 1).  augmentation: the draws of preprocessing.data_augmentation as well (header words 6..9: flag
+    bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug."""
     raw = _load(path, num_channels)
     h0, w0 = raw.shape[:2]
     cropped = crop_height != -1 and crop_width != -1
@@ -117,7 +119,7 @@ def raw_example(slot, path, num_channels, input_height, input_width, crop_height
         if rng is None:
             image = (resize_window(raw, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
         else:
-            image = _finish(raw, input_height, input_width, crop_height, crop_width, 0, rng)
+            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng)
         slot[HEADER_BYTES:HEADER_BYTES + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
         hd[:6] = (1, out_h, out_w, 0, 0, 0)
         return
@@ -126,7 +128,13 @@ def raw_example(slot, path, num_channels, input_height, input_width, crop_height
         if cropped:
             y0 = int(rng.integers(0, input_height - crop_height + 1))
             x0 = int(rng.integers(0, input_width - crop_width + 1))
-        flip = int(rng.random() < 0.5)
+        if augmentation:
+            from .preprocessing import augmentation_draws
+            flip, flags, brightness, hue, saturation = augmentation_draws(rng, num_channels)
+            hd[6] = flags
+            hd[7:10].view(np.float32)[:] = (brightness, hue, saturation)
+        else:
+            flip = int(rng.random() < 0.5)
     slot[HEADER_BYTES:HEADER_BYTES + raw.size] = raw.reshape(-1)
     hd[:6] = (0, h0, w0, y0, x0, flip)
 
@@ -149,15 +157,15 @@ def _buffer(name, shape, dtype):
 def fill_rows(task):
     """(buffer, batch shape, [(row, path, seed), ...], num_channels, in_h, in_w, crop_h, crop_w, augmentation[, raw]): decode the
     listed images (seed None: the evaluation transform) into rows of the shared batch buffer -- a float32 array of finished
-    examples, or with raw = 1 a uint8 array [rows, slot bytes] of decoded images + draws for the GPU transform.  Returns the
-    number of rows written (errors propagate)."""
+    examples, or with raw = 1 a uint8 array [rows, slot bytes] of decoded images + draws (the colour augmentation's included) for
+    the GPU transform.  Returns the number of rows written (errors propagate)."""
     name, shape, rows, num_channels, in_h, in_w, crop_h, crop_w, augmentation = task[:9]
     raw = len(task) > 9 and task[9]
     if raw:
-        assert not augmentation, 'the colour augmentation runs on the host: no raw slots'
         batch = _buffer(name, shape, np.uint8)
         for row, path, seed in rows:
-            raw_example(batch[row], path, num_channels, in_h, in_w, crop_h, crop_w, None if seed is None else np.random.default_rng(seed))
+            raw_example(batch[row], path, num_channels, in_h, in_w, crop_h, crop_w, None if seed is None else np.random.default_rng(seed),
+                        augmentation)
         return len(rows)
     batch = _buffer(name, shape, np.float32)
     for row, path, seed in rows:

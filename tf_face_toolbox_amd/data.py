@@ -1,7 +1,8 @@
 """Input pipeline: host-side mirror of the reference's data.py (Caffe-style `path label` lists,
 random / class-balanced PxK sampling, decode -> [0,1] -> bilinear resize -> random crop -> flip or
 augmentation -> (x-0.5)/0.5, batches in NHWC).  This is the caller side of the hot path (SURVEY.md
-8f next-1): JPEG decode and augmentation stay on the host (PIL + numpy worker threads), a prefetch
+8f next-1): the JPEG decode and the random draws stay on the host (PIL + numpy workers); resize, crop, flip,
+colour augmentation and normalisation run on the GPU when worker processes feed one (_raw_slots), a prefetch
 thread keeps one batch ahead and hands over float32 NHWC CUDA tensors -- exactly the `inputs` dict
 data.py:275-279 returns, with tensors replaced by callables that yield the next batch.
 
@@ -395,11 +396,13 @@ class _BatchSource(object):
 def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmentation, device):
     """(slot bytes, transform) when the decode workers hand over DECODED uint8 images and the resize / crop / flip / normalise
     runs on the GPU (fte_preprocess_u8: the same bits as the host transform, tests/test_gpu_loader.py), else (0, None).  The
-    host transform is 0.6 of the 1.7 ms a 250 x 250 JPEG costs a worker; the decode stays.  FTE_LOADER_GPU=0 keeps everything on
-    the host; the colour augmentation (preprocessing.py) always does.  A slot holds an image of FTE_LOADER_RAW_SIDE^2 pixels
+    host transform is 0.6 of the 1.7 ms a 250 x 250 JPEG costs a worker; the decode stays.  With `augmentation` the colour
+    augmentation (preprocessing.py) runs there too, from the workers' draws (fte_preprocess_u8_aug, tests/test_gpu_augment.py).
+    FTE_LOADER_GPU=0 keeps everything on the host.  A slot holds an image of FTE_LOADER_RAW_SIDE^2 pixels
     (default 256; CASIA-WebFace crops are 250 x 250) -- a larger image is transformed by its worker and handed over finished."""
-    if num_workers <= 0 or augmentation or torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0':
+    if num_workers <= 0 or torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0':
         return 0, None
+    entry = 'fte_preprocess_u8_aug' if augmentation else 'fte_preprocess_u8'
     from . import _lib
     from ._decode_worker import HEADER_BYTES
     side = int(os.environ.get('FTE_LOADER_RAW_SIDE', '256'))
@@ -408,7 +411,7 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
 
     def transform(raw):
         out = torch.empty((rows, out_h, out_w, num_channels), dtype=torch.float32, device=raw.device)
-        _lib.call('fte_preprocess_u8', raw.data_ptr(), out.data_ptr(), rows, slot, num_channels, in_h, in_w, out_h, out_w,
+        _lib.call(entry, raw.data_ptr(), out.data_ptr(), rows, slot, num_channels, in_h, in_w, out_h, out_w,
                   torch.cuda.current_stream().cuda_stream)
         return out
     return slot, transform

@@ -42,19 +42,42 @@ def adjust_saturation(image, factor):
     return _hsv_to_rgb(hsv)
 
 
+BRIGHTNESS, HUE, SATURATION = 1, 2, 4        # flag bits of augmentation_draws (and of the slot header, include/fte.h)
+
+
+def augmentation_draws(rng, num_channels):
+    """The random draws of data_augmentation, in its order, ALL of them consumed whether applied or not:
+    (flip, flags, brightness delta, hue delta, saturation factor).  `flags` holds the decisions
+    delta < 0.1 / < 0.2 / < 1.0, taken on the float64 draws; gray images draw neither hue nor saturation."""
+    flip = int(rng.random() < 0.5)
+    brightness = rng.uniform(0, 0.2)
+    flags = BRIGHTNESS if brightness < 0.1 else 0
+    hue, saturation = 0.0, 1.0
+    if num_channels == 3:
+        hue = rng.uniform(0, 0.4)
+        if hue < 0.2:
+            flags |= HUE
+        saturation = rng.uniform(0.6, 1.4)
+        if saturation < 1.0:
+            flags |= SATURATION
+    return flip, flags, brightness, hue, saturation
+
+
+def apply_augmentation(image, flip, flags, brightness, hue, saturation):
+    """data_augmentation with the draws given: flip; darken; RGB only: hue shift by -hue, desaturate."""
+    if flip:
+        image = image[:, ::-1, :]
+    if flags & BRIGHTNESS:
+        image = image - brightness
+    if image.shape[-1] == 3:
+        if flags & HUE:
+            image = adjust_hue(np.clip(image, 0, 1), -hue)
+        if flags & SATURATION:
+            image = adjust_saturation(np.clip(image, 0, 1), saturation)
+    return np.ascontiguousarray(image, dtype=np.float32)
+
+
 def data_augmentation(image, rng):
     """preprocessing.py:22-38: flip; with prob 1/2 darken by delta in [0,0.1); RGB only: with prob 1/2
     hue shift by -delta (delta in [0,0.2)), with prob 1/2 desaturate by a factor in [0.6,1)."""
-    if rng.random() < 0.5:
-        image = image[:, ::-1, :]
-    delta = rng.uniform(0, 0.2)
-    if delta < 0.1:
-        image = image - delta
-    if image.shape[-1] == 3:
-        delta = rng.uniform(0, 0.4)
-        if delta < 0.2:
-            image = adjust_hue(np.clip(image, 0, 1), -delta)
-        delta = rng.uniform(0.6, 1.4)
-        if delta < 1.0:
-            image = adjust_saturation(np.clip(image, 0, 1), delta)
-    return np.ascontiguousarray(image, dtype=np.float32)
+    return apply_augmentation(image, *augmentation_draws(rng, image.shape[-1]))
