@@ -784,6 +784,38 @@ size_t fte_megaface_scan_ws_bytes(int m, int nthr);
 int fte_megaface_scan(const float* probes, int m, const float* rows, int n, int d, const int32_t* thr_off, const float* thr, int nthr,
                       int nbins, uint64_t* counts, uint64_t* hist, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Partial FC: the additive-margin head over a per-step sample of the classes (An et al., "Partial FC: Training 10 Million
+ * Identities on a Single Machine"; loss.py partial_fc_margin_loss, SphereNet-ArcFace / -CosFace with a sample rate) ----
+ * The sample of a step.  With seed `seed`, step number `step`, labels y[0..n), C classes and a fixed sample size S (n <= S <= C):
+ *   fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16       (uint32, wrap-around)
+ *   base = fmix32(fmix32(seed) + step);  class j gets h_j = fmix32(j + base)
+ *   order all classes by the triple (j is not a label of this batch, h_j, j), ascending; the sample is the first S classes: every
+ *   class present in the batch, then the other classes with the smallest hashes.  The triple is a total order (and fmix32 a
+ *   bijection, so the h_j alone are distinct): the set is unique, whatever the thread scheduling.
+ *   index[0..S) = the sample sorted by class id; index[S..Spad) = -1, Spad = S rounded up to 64.
+ *   inverse[j] (j < C) = the position of class j in index, -1 for a class outside the sample.
+ *   labels_out[i] = inverse[y[i]]; a label outside [0, C) takes no part in the sample and gives labels_out[i] = -1, which the head
+ *   kernel answers with a NaN row as for any out-of-range label.
+ * The head is fte_margin_softmax_fwd_bwd, unchanged, over the S gathered columns (c = S, ld = Spad) with labels_out: loss_i =
+ * logsumexp_{k < S} z_ik - z_i,labels_out[i].  The gradient with respect to x and to the sampled columns of W is the exact one
+ * (rowcoef / colcoef as for the dense head); with respect to every other column it is exactly 0.0.
+ *
+ * fte_pfc_sample: index [Spad], inverse [C], labels_out [n], all int32 and 16-byte aligned; ws >= fte_pfc_sample_ws_bytes(C),
+ * cleared by the call (hipMemsetAsync on the stream).  Integer histograms and a compaction in class order: two calls with the same
+ * arguments write the same bytes.  Nothing is read back to the host.
+ * FTE_EINVAL: a NULL pointer, n < 1, C < 1, S < n or S > C, or a misaligned pointer.  FTE_EWORKSPACE: ws NULL or short. */
+size_t fte_pfc_sample_ws_bytes(int C);
+int fte_pfc_sample(const int32_t* labels, int n, int C, int S, uint32_t seed, uint32_t step, int32_t* index, int32_t* inverse,
+                   int32_t* labels_out, void* ws, size_t ws_bytes, void* stream);
+/* Ws[d, k] = W[d, index[k]] for k < S, 0 for S <= k < Spad (and for an index outside [0, C)).  W [D, cpad], Ws [D, Spad], row-major.
+ * The sampled column norms are fte_col_norms of Ws.
+ * FTE_EINVAL: a NULL pointer, D < 1, C < 1, cpad < C, S < 1, Spad < S, Spad % 4, or index / Ws not 16-byte aligned. */
+int fte_pfc_gather_cols(const float* W, const int32_t* index, float* Ws, int D, int C, int cpad, int S, int Spad, void* stream);
+/* dW[d, j] = dWs[d, inverse[j]] where 0 <= inverse[j] < S, else 0.0 (j >= C: 0.0), for every j < cpad: one pass that writes each
+ * element of dW exactly once, so whatever dW held before (NaNs included) is gone.  dWs [D, Spad], dW [D, cpad].
+ * FTE_EINVAL: a NULL pointer, D < 1, C < 1, cpad < C, cpad % 4, S < 1, Spad < S, or dW not 16-byte aligned. */
+int fte_pfc_scatter_cols(const float* dWs, const int32_t* inverse, float* dW, int D, int C, int cpad, int S, int Spad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,10 @@ _SIGS = {
     'fte_megaface_pair_scores': (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
     'fte_megaface_scan_ws_bytes': (c_size_t, [c_int] * 2),
     'fte_megaface_scan': (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    'fte_pfc_sample_ws_bytes': (c_size_t, [c_int]),
+    'fte_pfc_sample': (c_int, [_P] + [c_int] * 5 + [_P] * 4 + [c_size_t, _P]),
+    'fte_pfc_gather_cols': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
+    'fte_pfc_scatter_cols': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_fwd': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_dgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_wgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P, c_size_t, _P]),

@@ -17,6 +17,7 @@
 #include "layers.h"
 #include "wino.h"
 #include "search.h"
+#include "partial_fc.h"
 
 namespace {
 
@@ -1903,5 +1904,26 @@ int fte_megaface_scan(const float* probes, int m, const float* rows, int n, int 
     if (!ws || ws_bytes < s_mf_scan_ws_bytes(nthr)) return FTE_EWORKSPACE;
     return rc(s_mf_scan(probes, m, rows, n, d, thr_off, thr, nthr, nbins, (unsigned long long*)counts, (unsigned long long*)hist, ws,
                         (hipStream_t)stream));
+}
+
+// ---- Partial FC (partial_fc.hip) ----
+size_t fte_pfc_sample_ws_bytes(int C) { return C < 1 ? 0 : p_sample_ws_bytes(C); }
+int fte_pfc_sample(const int32_t* labels, int n, int C, int S, uint32_t seed, uint32_t step, int32_t* index, int32_t* inverse,
+                   int32_t* labels_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!labels || !index || !inverse || !labels_out || n < 1 || C < 1 || S < n || S > C ||
+        (((uintptr_t)index | (uintptr_t)inverse | (uintptr_t)labels_out) & 15))
+        return FTE_EINVAL;
+    if (!ws || ws_bytes < p_sample_ws_bytes(C)) return FTE_EWORKSPACE;
+    if ((uintptr_t)ws & 15) return FTE_EINVAL;
+    return rc(p_sample(labels, n, C, S, seed, step, index, inverse, labels_out, ws, (hipStream_t)stream));
+}
+int fte_pfc_gather_cols(const float* W, const int32_t* index, float* Ws, int D, int C, int cpad, int S, int Spad, void* stream) {
+    if (!W || !index || !Ws || D < 1 || C < 1 || cpad < C || S < 1 || Spad < S || Spad % 4 || (((uintptr_t)index | (uintptr_t)Ws) & 15))
+        return FTE_EINVAL;
+    return rc(p_gather_cols(W, index, Ws, D, C, cpad, S, Spad, (hipStream_t)stream));
+}
+int fte_pfc_scatter_cols(const float* dWs, const int32_t* inverse, float* dW, int D, int C, int cpad, int S, int Spad, void* stream) {
+    if (!dWs || !inverse || !dW || D < 1 || C < 1 || cpad < C || cpad % 4 || S < 1 || Spad < S || ((uintptr_t)dW & 15)) return FTE_EINVAL;
+    return rc(p_scatter_cols(dWs, inverse, dW, D, C, cpad, S, Spad, (hipStream_t)stream));
 }
 }  // extern "C"

@@ -213,6 +213,10 @@ class DataParallel(Singular):
         is per-tower state there (loss.py:34-39) and the towers' tables drift apart; True all-gathers every step's scatter rows
         so that all replicas keep ONE table, equal to the single-tower update of the global batch (nets/graph.py)."""
         assert num_gpus > 1, 'DataParallel objects are only used for multi-gpu training tasks.'
+        if getattr(model, 'sample_rate', None) is not None:
+            # each rank sees other labels, so the ranks' samples would differ and the all-reduce would average gradients of
+            # different column sets
+            raise ValueError('a sampled-class head (sample_rate %g) runs on one GPU only: num_gpus = %d' % (model.sample_rate, num_gpus))
         super(DataParallel, self).__init__(model, lr, optimizer, weight_decay)
         self.num_gpus = num_gpus
         self.pretrained_param = []

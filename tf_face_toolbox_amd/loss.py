@@ -1,9 +1,11 @@
 """Host-side mirror of the reference's loss.py: focal_loss (:18-27), center_loss (:29-45), batch_hard_triplet_loss
-(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference).  Same names, argument meaning and defaults.  There is no autograd here, so every function
+(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference) and its sampled-class form partial_fc_margin_loss.  Same names, argument meaning and defaults.  There is no autograd here, so every function
 also returns the gradient of ITS OWN loss value with respect to its first argument (what tf.gradients would have
 produced for that term); the graph nets wire them as heads (nets/graph.py), a caller can combine them freely.
 
 All tensors are float32 / int32 CUDA tensors; logits may carry padding columns (ld = logits.shape[1] >= num_classes)."""
+import math
+
 import torch
 
 from . import _lib
@@ -110,3 +112,65 @@ def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, marg
     call('fte_gemm_nt', G, weights, None, None, 0, None, dx, None, n, ld, d, ws, wsb, st)
     call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
     return _scaled_sum(rows, 1.0 / n), dx, dw
+
+
+def sample_size(num_classes, sample_rate):
+    """S = ceil(sample_rate * num_classes) of the sampled-class head (fte.h "Partial FC"); None or a rate of 1 = every class."""
+    c = int(num_classes)
+    if sample_rate is None:
+        return c
+    r = float(sample_rate)
+    if not 0.0 < r <= 1.0:
+        raise ValueError('sample_rate must lie in (0, 1] (got %r)' % (sample_rate,))
+    return min(c, int(math.ceil(r * c)))
+
+
+def partial_fc_margin_loss(features, weights, labels, sample_rate, seed, step, scale=64.0, margin=0.5, margin_cos=0.0, num_classes=None):
+    """additive_margin_loss over a per-step sample of the classes (Partial FC): the batch's own classes plus the other classes with
+    the smallest hashes under (seed, step), S = ceil(sample_rate * num_classes) in all; the contract is fte.h's "Partial FC".
+    Arguments as additive_margin_loss; `seed` / `step` are taken modulo 2^32.
+    -> (loss, dfeatures [N, D], dweights [D, ld], index [S] int32): the sampled classes in ascending order; dweights is the dense
+    gradient, exactly 0.0 in every column outside `index`.  sample_rate None or 1 is additive_margin_loss itself (the same calls,
+    bit-identical; index = every class).  S < N raises ValueError: with S >= N all of a batch's classes always fit."""
+    ld = weights.shape[1]
+    c = ld if num_classes is None else int(num_classes)
+    S = sample_size(c, sample_rate)
+    if S >= c:
+        loss, dx, dw = additive_margin_loss(features, weights, labels, scale, margin, margin_cos, num_classes)
+        return loss, dx, dw, torch.arange(c, dtype=torch.int32, device=weights.device)
+    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
+    weights = _check(weights, torch.float32, 'weights')
+    n, d = features.shape
+    if weights.shape[0] != d or labels.shape != (n,):
+        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
+                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
+    if S < n:
+        raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows' % (S, sample_rate, c, n))
+    spad = (S + 63) // 64 * 64
+    st = _stream()
+    dev = features.device
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    wsb = max(_lib.query('fte_gemm_ws_bytes', n, spad, d), _lib.query('fte_pfc_sample_ws_bytes', c), 4096)
+    ws = torch.empty(wsb // 4 + 1024, **f32)
+    wsb = ws.numel() * 4
+    index, inverse, ys = torch.empty(spad, **i32), torch.empty(c, **i32), torch.empty(n, **i32)
+    Ws, dWs = torch.empty(d, spad, **f32), torch.empty(d, spad, **f32)
+    s, G = torch.empty(n, spad, **f32), torch.empty(n, spad, **f32)
+    xn, rowcoef, rows = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
+    wn, colcoef = torch.empty(spad, **f32), torch.empty(spad, **f32)
+    dx, dw = torch.empty_like(features), torch.empty_like(weights)
+    call = _lib.call
+    call('fte_pfc_sample', labels, n, c, S, int(seed) & 0xffffffff, int(step) & 0xffffffff, index, inverse, ys, ws, wsb, st)
+    call('fte_pfc_gather_cols', weights, index, Ws, d, c, ld, S, spad, st)
+    call('fte_gemm_nn', features, Ws, None, s, n, spad, d, ws, wsb, st)
+    call('fte_row_norms', features, xn, n, d, d, st)
+    call('fte_col_norms', Ws, wn, d, S, spad, st)
+    call('fte_margin_softmax_fwd_bwd', s, xn, wn, ys, float(scale), float(margin), float(margin_cos), None, rows, G, rowcoef,
+         n, S, spad, 1.0 / n, st)
+    call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, S, spad, st)
+    call('fte_gemm_tn', features, G, dWs, n, spad, d, ws, wsb, st)
+    call('fte_add_scaled_rows_cols', dWs, Ws, None, colcoef, d, spad, spad, st)
+    call('fte_pfc_scatter_cols', dWs, inverse, dw, d, c, ld, S, spad, st)
+    call('fte_gemm_nt', G, Ws, None, None, 0, None, dx, None, n, spad, d, ws, wsb, st)
+    call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
+    return _scaled_sum(rows, 1.0 / n), dx, dw, index[:S]

@@ -121,6 +121,11 @@ class Network(abc.ABC):
             head, self.margin_scale if scale is None else scale, self.margin if margin is None else margin,
             self.margin_cos if margin_cos is None else margin_cos)
 
+    def set_sample_rate(self, rate, seed=0):
+        """Nets with a sampled-class (Partial FC) head only -- SphereNet-ArcFace / -CosFace; train.py --sample_rate / --sample_seed.
+        Every other net (the graph nets and the A-softmax head included) refuses."""
+        raise ValueError('%s has no sampled-class head (--sample_rate: SphereNet-ArcFace / SphereNet-CosFace only)' % self.name)
+
     def mult_lr_list(self, scope=None):
         return [1.0 for _ in self.param_list(is_training=True, trainable=True, scope=scope)]
 

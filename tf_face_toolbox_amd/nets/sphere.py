@@ -23,6 +23,7 @@ from collections import OrderedDict
 import torch
 
 from .. import _lib
+from ..loss import sample_size
 from .net_base import MARGIN_PRESETS, Network, margin_params, side_stream
 
 NUM_BLOCKS = (1, 2, 4, 1)     # nets/sphere.py:58,62,66,70
@@ -213,14 +214,15 @@ class SphereNet(Network):
         if s16:
             self.z16 = [torch.empty(n, c.hout, c.wout, c.cout, **i16) for c in self.convs]
         self.emb = torch.empty(n, EMBED, **f32)
-        self.s_raw = torch.empty(n, self.cpad, **f32)
-        self.G = torch.empty(n, self.cpad, **f32)
-        self.logits_buf = torch.empty(n, self.cpad, **f32) if self.head == 'asoftmax' or self.head in MARGIN_PRESETS else self.s_raw
+        hw = self._head_width()                           # cpad; the sampled-class head: its Spad columns
+        self.s_raw = torch.empty(n, hw, **f32)
+        self.G = torch.empty(n, hw, **f32)
+        self.logits_buf = torch.empty(n, hw, **f32) if self.head == 'asoftmax' or self.head in MARGIN_PRESETS else self.s_raw
         self.loss_rows = torch.empty(n, **f32)
         self.xn = torch.empty(n, **f32)
-        self.wn = torch.empty(self.cpad, **f32)
+        self.wn = torch.empty(hw, **f32)
         self.rowcoef = torch.empty(n, **f32)
-        self.colcoef = torch.empty(self.cpad, **f32)
+        self.colcoef = torch.empty(hw, **f32)
         self.demb = torch.empty(n, EMBED, **f32)
         self.bwd = {}
         for si in range(4):
@@ -250,15 +252,23 @@ class SphereNet(Network):
                        q('fte_conv3x3_dgrad_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride))
         c0 = self.convs[0]
         need = max(need, q('fte_conv3x3_first_wgrad_ws_bytes', n, c0.hin, c0.win, c0.cin, c0.cout, c0.stride),
-                   q('fte_gemm_ws_bytes', n, EMBED, self.fin), q('fte_gemm_ws_bytes', n, self.cpad, EMBED))
+                   q('fte_gemm_ws_bytes', n, EMBED, self.fin), q('fte_gemm_ws_bytes', n, hw, EMBED))
         self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
         self.ws_bytes = self.ws.numel() * 4
         # filter gradients run on a second stream beside the data gradient of the same layer (_body_walk); their split-K slabs
         # need a workspace of their own
         self.side = side_stream(self.device) if os.environ.get('FTE_SIDE_STREAM', '1') != '0' else None
         self.ws_side = torch.empty_like(self.ws) if self.side is not None else self.ws
+        self._alloc_head(n)
         self._act_n = n
         self.y16 = None                                   # allocated on first use (_alloc_copies)
+
+    def _head_width(self):
+        """columns of the head's [n, .] buffers (s_raw, G, logits_buf)"""
+        return self.cpad
+
+    def _alloc_head(self, n):
+        """further head buffers of a subclass, sized with the activations"""
 
     def _use_copies(self):
         return self.bf16_copies and _lib.get_mfma_dtype() == 'bf16'
@@ -756,15 +766,87 @@ class SphereNetAdditiveMargin(SphereNetMargin):
     not applied under no_grad.  The variables and their names are SphereNet's."""
 
     def __init__(self, weight_decay=0.0005, data_format='NCHW', name='SphereNet', seed=0, head='arcface',
-                 scale=None, margin=None, margin_cos=None):
+                 scale=None, margin=None, margin_cos=None, sample_rate=None, sample_seed=0):
         super(SphereNetAdditiveMargin, self).__init__(weight_decay, data_format, name, seed)
         self.margin_scale, self.margin, self.margin_cos = margin_params(head, scale, margin, margin_cos)
         self.head = head
+        self.set_sample_rate(sample_rate, sample_seed)
 
     def _margin_head(self, labels, n, st):
         _lib.call('fte_margin_softmax_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.margin_scale, self.margin,
                   self.margin_cos, self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
                   self._grad_scale(n), st)
+
+    # ---- the sampled-class head (Partial FC; fte.h "Partial FC", DESIGN.md 4.13) -----------------------------------------------
+    def set_sample_rate(self, rate, seed=0):
+        """rate in (0, 1): every training step runs the head over S = ceil(rate * num_classes) classes, the batch's own plus the
+        other classes with the smallest hashes under (seed, global_step); None or 1: the dense head.  The variables, the dense
+        [D, cpad] classifier gradient (0.0 in the unsampled columns), the optimizer and the checkpoints stay as they are."""
+        sample_size(1, rate)                              # validates the rate
+        self.sample_rate = None if rate is None or float(rate) >= 1.0 else float(rate)
+        self.sample_seed = int(seed)
+        self._act_n = None                                # the head buffers change width
+
+    @property
+    def sample_size(self):
+        """S, the classes per step (num_classes for the dense head)"""
+        return sample_size(self.num_classes, self.sample_rate)
+
+    def _head_width(self):
+        return self.cpad if self.sample_rate is None else (self.sample_size + 63) // 64 * 64
+
+    def _alloc_head(self, n):
+        if self.sample_rate is None:
+            return
+        S, spad = self.sample_size, self._head_width()
+        f32, i32 = dict(dtype=torch.float32, device=self.device), dict(dtype=torch.int32, device=self.device)
+        self.class_index = torch.empty(spad, **i32)
+        self.class_inverse = torch.empty(self.num_classes, **i32)
+        self.sampled_labels = torch.empty(n, **i32)
+        self.Ws = torch.empty(EMBED, spad, **f32)
+        self.dWs = torch.empty(EMBED, spad, **f32)
+        self.pfc_ws = torch.empty(_lib.query('fte_pfc_sample_ws_bytes', self.num_classes) // 4 + 16, **f32)
+
+    def forward(self, images, labels=None, num_classes=None, is_training=True):
+        if not is_training or self.sample_rate is None:
+            return super(SphereNetAdditiveMargin, self).forward(images, labels, num_classes=num_classes, is_training=is_training)
+        assert num_classes is not None, 'num_classes must be given when is_training=True'
+        assert labels is not None, 'margin nets take labels in forward (data_parallel.py:220)'
+        self._ensure_built(images, num_classes)
+        n = images.shape[0]
+        S = self.sample_size
+        if S < n:
+            raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows'
+                             % (S, self.sample_rate, self.num_classes, n))
+        labels = self._check_labels(labels)
+        self._labels = labels
+        st = _stream()
+        call = _lib.call
+        self.backbone(images, is_training=True)
+        spad = self._head_width()
+        wc = self.view('classifier/fc_classifier/weights')
+        call('fte_pfc_sample', labels, n, self.num_classes, S, self.sample_seed & 0xffffffff, int(self.global_step) & 0xffffffff,
+             self.class_index, self.class_inverse, self.sampled_labels, self.pfc_ws, self.pfc_ws.numel() * 4, st)
+        call('fte_pfc_gather_cols', wc, self.class_index, self.Ws, EMBED, self.num_classes, self.cpad, S, spad, st)
+        call('fte_gemm_nn', self.emb, self.Ws, None, self.s_raw, n, spad, EMBED, self.ws, self.ws_bytes, st)
+        call('fte_row_norms', self.emb, self.xn, n, EMBED, EMBED, st)
+        call('fte_col_norms', self.Ws, self.wn, EMBED, S, spad, st)
+        call('fte_margin_softmax_fwd_bwd', self.s_raw, self.xn, self.wn, self.sampled_labels, self.margin_scale, self.margin,
+             self.margin_cos, self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, S, spad, self._grad_scale(n), st)
+        call('fte_asoftmax_colcoef', self.G, self.s_raw, self.wn, self.colcoef, n, S, spad, st)
+        return {'logits': self.logits_buf[:, :S], 'class_index': self.class_index[:S]}
+
+    def _head_backward(self, n, st):
+        if self.sample_rate is None:
+            return super(SphereNetAdditiveMargin, self)._head_backward(n, st)
+        call = _lib.call
+        S, spad = self.sample_size, self._head_width()
+        gwc = self.view('classifier/fc_classifier/weights', self.grads)
+        call('fte_gemm_tn', self.emb, self.G, self.dWs, n, spad, EMBED, self.ws, self.ws_bytes, st)
+        call('fte_add_scaled_rows_cols', self.dWs, self.Ws, None, self.colcoef, EMBED, spad, spad, st)
+        call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, gwc, EMBED, self.num_classes, self.cpad, S, spad, st)
+        call('fte_gemm_nt', self.G, self.Ws, None, None, 0, None, self.demb, None, n, spad, EMBED, self.ws, self.ws_bytes, st)
+        call('fte_add_scaled_rows_cols', self.demb, self.emb, self.rowcoef, None, n, EMBED, EMBED, st)
 
     def _others(self):
         return OrderedDict()

@@ -67,7 +67,26 @@ def build_parser():
         parser.add_argument(flag, type=float, default=None,
                             help='additive-margin nets (SphereNet-ArcFace / -CosFace, ResNet-50-arcface / -cosface) only: the %s; '
                                  "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35)" % what)
+    parser.add_argument('--sample_rate', type=float, default=1.0,
+                        help='SphereNet-ArcFace / SphereNet-CosFace on one GPU only: the fraction of the classes the margin head runs over per '
+                             "step (Partial FC: the batch's own classes plus a seeded random sample of the others; 0.1 is the usual value). "
+                             'A float in (0, 1]; 1 (default) = the dense head.')
+    parser.add_argument('--sample_seed', type=int, default=0, help='seed of the per-step class sample of --sample_rate.')
     return parser
+
+
+SAMPLED_NETS = ('SphereNet-ArcFace', 'SphereNet-CosFace')
+
+
+def sample_flags_check(FLAGS):
+    """--sample_rate / --sample_seed: refuse what the sampled-class head does not do, before anything is built"""
+    if not 0.0 < FLAGS.sample_rate <= 1.0:
+        raise SystemExit('--sample_rate must lie in (0, 1]: got %g' % FLAGS.sample_rate)
+    if FLAGS.sample_rate < 1.0 and FLAGS.net_name not in SAMPLED_NETS:
+        raise SystemExit('--sample_rate %g: only %s have a sampled-class head, not %s'
+                         % (FLAGS.sample_rate, ' / '.join(SAMPLED_NETS), FLAGS.net_name))
+    if FLAGS.sample_rate < 1.0 and FLAGS.num_gpus > 1:
+        raise SystemExit('--sample_rate %g: the sampled-class head runs on one GPU only (--num_gpus %d)' % (FLAGS.sample_rate, FLAGS.num_gpus))
 
 
 def FLAGS_assertion(FLAGS):
@@ -180,6 +199,8 @@ def train(FLAGS):
         margins = (FLAGS.margin_scale, FLAGS.margin, FLAGS.margin_cos)
         if getattr(network, 'margin_scale', None) is not None and margins != (None, None, None):
             network.set_margin(*margins)
+        if FLAGS.sample_rate < 1.0:
+            network.set_sample_rate(FLAGS.sample_rate, FLAGS.sample_seed)
         lr = lr_config(FLAGS, FLAGS.lr_decay_method, batches_per_epoch)                              # train.py:176
         if FLAGS.num_gpus > 1:                                                                        # train.py:178-183
             model = DataParallel_margin(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay, num_gpus=FLAGS.num_gpus,
@@ -187,6 +208,9 @@ def train(FLAGS):
         else:
             model = Singular(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay)
         train_ops, losses, losses_name, others = model(inputs)
+        if FLAGS.sample_rate < 1.0:
+            print('Sampled-class head: sample_rate = %g, sample_seed = %d, S = %d of %d classes per step'
+                  % (FLAGS.sample_rate, FLAGS.sample_seed, network.sample_size, network.num_classes))
 
         tag = FLAGS.net_name + '_' + FLAGS.model_name
         ckpt_dir = os.path.join(FLAGS.model_dir, tag)
@@ -264,6 +288,7 @@ def train(FLAGS):
 def main(argv=None):
     FLAGS = build_parser().parse_args(argv)
     FLAGS_assertion(FLAGS)
+    sample_flags_check(FLAGS)
     os.makedirs(os.path.join(FLAGS.train_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     os.makedirs(os.path.join(FLAGS.model_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     train(FLAGS)
