@@ -557,13 +557,24 @@ size_t fte_gemm_ws_bytes(int m, int n, int k);
  * (tf.losses.sparse_softmax_cross_entropy, nets/sphere.py:109):
  *   loss_rows[i] = -log softmax(logits[i,:c])[labels[i]]
  *   dlogits[i,j] = (softmax - onehot) * grad_scale   (columns c..ld-1 get 0)
- * logits/dlogits are [n, ld] with ld >= c (padded classifier width). */
+ * logits/dlogits are [n, ld] with ld >= c (padded classifier width); pad columns of `logits` are never read.
+ * Bad labels, the rule of every head of this section (softmax-CE, focal, A-softmax, additive margin): a label outside
+ * [0, c) -- negative, >= c, a pad column c <= y < ld included -- gives a NaN row: loss_rows[i] and the row's gradient
+ * (dlogits / G, and f, rowcoef where the head has them) are NaN in columns 0..c-1 and 0 in the pad columns c..ld-1, exactly as a
+ * good row's pads.  Nothing is read or written out of bounds, the other rows are bitwise what they are without the bad
+ * row, and the caller's non-finite-loss check trips (TF's sparse_softmax_cross_entropy gives NaN loss rows on GPU too).
+ * Which kernel runs is decided by ld alone (row in registers up to ld = 2048 and up to 12288, three passes over the row
+ * above); the three give bit-identical results for the same [n, c] logits.
+ * FTE_EINVAL: a null pointer, n < 1, c < 1, ld < c. */
 int fte_softmax_ce_fwd_bwd(const float* logits, const int32_t* labels, float* loss_rows,
                            float* dlogits, int n, int c, int ld, float grad_scale, void* stream);
 
 /* focal_loss (loss.py:18-27; note the reference's swapped-looking defaults gamma = 1.0, alpha = 2.0 are kept as named):
  * loss_rows[i] = gamma * (1 - p_y)^alpha * CE_i, dlogits = grad_scale * d(loss_rows[i])/dlogits (through BOTH the
- * cross-entropy and the softmax-score factor, as tf.gradients does).  alpha >= 1.  Same layout rules as above. */
+ * cross-entropy and the softmax-score factor, as tf.gradients does).  Same layout, pad and bad-label rules as above.
+ * alpha >= 1 (FTE_EINVAL otherwise, nothing written): below 1 the factor (1 - p_y)^(alpha - 1) of the gradient is unbounded
+ * as p_y -> 1.  A saturated row (1 - p_y rounds to 0 in fp32) has loss 0 and gradient 0, never NaN: (1 - p_y)^(alpha - 1) is
+ * taken as 1 at alpha == 1 and the factor log p_y next to it is 0 there. */
 int fte_focal_loss_fwd_bwd(const float* logits, const int32_t* labels, float* loss_rows, float* dlogits,
                            int n, int c, int ld, float gamma, float alpha, float grad_scale, void* stream);
 
@@ -572,7 +583,11 @@ int fte_focal_loss_fwd_bwd(const float* logits, const int32_t* labels, float* lo
  * product [n, ld]; xn = |x_i| (n), wn = |W_j| (c).  Produces the margin logits
  * f (optional), the per-row loss, G = dLoss/ds (the matrix that feeds the two
  * gradient GEMMs), rowcoef (dx += rowcoef_i * x_i) and, via
- * fte_asoftmax_colcoef, colcoef (dw[:,j] += colcoef_j * w[:,j]). */
+ * fte_asoftmax_colcoef, colcoef (dw[:,j] += colcoef_j * w[:,j]).  f may be NULL (G, loss_rows and rowcoef do not
+ * depend on it).  Columns c..ld-1 of f and G get 0; the bad-label rule of fte_softmax_ce_fwd_bwd holds (NaN loss, rowcoef, and
+ * f / G below c).  psi is continuous in cos(theta_y) but its derivative is not at the branch thresholds 0, +-sqrt(1/2): a
+ * target cosine within fp32 rounding of a threshold may take either neighbouring branch.
+ * FTE_EINVAL: a null pointer (f excepted), n < 1, c < 1, ld < c. */
 int fte_asoftmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels,
                          float lambda, float* f, float* loss_rows, float* G, float* rowcoef,
                          int n, int c, int ld, float grad_scale, void* stream);
@@ -609,10 +624,11 @@ int fte_row_norms(const float* a, float* out, int rows, int cols, int ld, void* 
 int fte_col_norms(const float* a, float* out, int rows, int cols, int ld, void* stream);
 /* The flip-averaged inference path (nets/sphere.py:97-101, evaluate.py:62-63): y[n,h,w',c] = x[n,h,wd-1-w',c] replaces
  * tf.reverse(images, axis=[2]) (x != y; 16-byte aligned when c % 4 == 0) and out = a*x + b*y the mean of the two embeddings
- * (a = b = 0.5; out may alias x or y). */
+ * (a = b = 0.5; out may alias x or y; n >= 1). */
 int fte_flip_width(const float* x, float* y, int n, int h, int wd, int c, void* stream);
 int fte_axpby(float a, const float* x, float b, const float* y, float* out, long n, void* stream);
-/* a[i,j] += rc[i] * b[i,j]   (rc NULL -> skip) ;  a[i,j] += cc[j] * b[i,j]  (cc NULL -> skip) */
+/* a[i,j] += rc[i] * b[i,j]   (rc NULL -> skip) ;  a[i,j] += cc[j] * b[i,j]  (cc NULL -> skip), a and b [rows, ld], ld >= cols;
+ * columns cols..ld-1 are neither read nor written. */
 int fte_add_scaled_rows_cols(float* a, const float* b, const float* rc, const float* cc,
                              int rows, int cols, int ld, void* stream);
 
@@ -621,8 +637,10 @@ int fte_add_scaled_rows_cols(float* a, const float* b, const float* rc, const fl
  * (scatter_sub).  Every gather is served from the centers as they were BEFORE the update
  * (loss.py:37 before :39).  In place on `centers` [num_classes, d]; ws >= n*d floats, and after the call
  * ws[0 : n*d] holds diff = f - c_y (what fte_center_scatter_update consumes).  alpha == 1 evaluates loss and gradient
- * only (no update launch).  A label outside [0, num_classes) gives a NaN loss / gradient row and no update -- never an
- * out-of-bounds access. */
+ * only (no update launch).  A label outside [0, num_classes) gives a NaN loss / gradient row, a zero diff row and no
+ * update -- never an out-of-bounds access; such a sample is skipped by the update as if it were not in the batch (it
+ * does not own a row of the table either).  The update is deterministic: rows of one label are summed in sample order.
+ * FTE_EINVAL: a null pointer, n, d or num_classes < 1; FTE_EWORKSPACE: ws NULL or ws_bytes < n*d*sizeof(float). */
 int fte_center_loss_fwd_bwd_update(const float* feat, const int32_t* labels, float* centers,
                                    float* loss_rows, float* dfeat, int n, int d, int num_classes, float alpha,
                                    float grad_scale, void* ws, size_t ws_bytes, void* stream);
@@ -635,7 +653,14 @@ int fte_center_scatter_update(const float* diff, const int32_t* labels, float* c
 
 /* batch-hard triplet (loss.py:47-78): per-sample loss [n] and d(sum w_i*loss_i)/dfeat.
  * soft_margin != 0 selects softplus(pos - neg) (margin=None in the reference, loss.py:74-75) and `margin` is ignored; otherwise
- * max(0, pos - neg + margin) for ANY margin, negative ones included (loss.py:76-77).  ws >= 3*n*n floats. */
+ * max(0, pos - neg + margin) for ANY margin, negative ones included (loss.py:76-77).
+ * ws >= 2*n*n floats (the distance and the coefficient matrix; FTE_EWORKSPACE below that).  1 <= n <= 8192 (a coefficient
+ * row lives in LDS) and d >= 1, FTE_EINVAL otherwise, before anything is launched.
+ * As in the reference, an anchor without a positive takes pos = 0 and one without a negative neg = 1e6, and neither
+ * contributes a gradient; distances are sqrt(|f_i - f_j|^2 + 1e-12).
+ * Ties: of several equidistant hardest positives (or negatives) the one with the LOWEST index takes the whole gradient
+ * (numpy argmax / argmin).  The reference's tf.reduce_max / reduce_min divide the gradient evenly among tied entries; only
+ * exact ties differ, i.e. duplicated images in one batch, and the loss values are the same either way. */
 int fte_batch_hard_triplet_fwd_bwd(const float* feat, const int32_t* labels, float margin, int soft_margin,
                                    float loss_weight, float* loss_rows, float* dfeat,
                                    int n, int d, void* ws, size_t ws_bytes, void* stream);
@@ -649,15 +674,16 @@ int fte_batch_hard_triplet_fwd_bwd(const float* feat, const int32_t* labels, flo
  * If fold > 1, column j of `out` (cols/fold of them) sums in[r, j + t*(cols/fold)] over t too. */
 int fte_reduce_rows(const float* in, float* out, const float* bias, int bmod,
                     long rows, long cols, int fold, float scale, void* stream);
-/* out[0] = scale * sum_i a[i]^2   (ws >= 1024 floats) */
+/* out[0] = scale * sum_i a[i]^2   (ws >= 1024 floats; a 16-byte aligned, n >= 1, any remainder n % 4) */
 int fte_sumsq(const float* a, long n, float scale, float* out, void* ws, size_t ws_bytes, void* stream);
-/* out[0] = scale * sum_i a[i]     (ws >= 1024 floats) */
+/* out[0] = scale * sum_i a[i]     (ws >= 1024 floats; a 16-byte aligned, n >= 1, any remainder n % 4) */
 int fte_sum(const float* a, long n, float scale, float* out, void* ws, size_t ws_bytes, void* stream);
 
-/* acc = mom*acc + (gscale*g + wd*w) ; w -= lr*acc      (MomentumOptimizer, Appendix A.7) */
+/* acc = mom*acc + (gscale*g + wd*w) ; w -= lr*acc      (MomentumOptimizer, Appendix A.7); w, acc, g 16-byte aligned, n >= 1,
+ * any remainder n % 4 */
 int fte_momentum_update(float* w, float* acc, const float* g, long n,
                         float lr, float mom, float wd, float gscale, void* stream);
-/* TF AdamOptimizer (epsilon outside the bias correction); t = 1-based step */
+/* TF AdamOptimizer (epsilon outside the bias correction) on gscale*g + wd*w; t = 1-based step (t < 1: FTE_EINVAL) */
 int fte_adam_update(float* w, float* m, float* v, const float* g, long n,
                     float lr, float b1, float b2, float eps, float wd, float gscale, int t, void* stream);
 

@@ -261,3 +261,85 @@ def test_focal_loss_matches_torch_autograd():
         ref.backward()
         assert abs(loss - ref.item()) < 1e-12
         np.testing.assert_allclose(d, t.grad.numpy(), atol=1e-14)
+
+
+# The inputs of tests/test_gpu_heads_edges.py lean on branches of the references that nothing above reaches: anchors without a
+# positive or without a negative, a duplicated anchor, saturated focal rows, a single center row taking every sample.
+def _triplet_autograd(f, y, margin):
+    n = len(y)
+    tf_ = torch.tensor(f, requires_grad=True)
+    diff = tf_[:, None, :] - tf_[None, :, :]
+    dist = torch.sqrt((diff ** 2).sum(-1) + 1e-12)
+    same = torch.tensor(y[:, None] == y[None, :])
+    hp = (dist * (same ^ torch.eye(n, dtype=torch.bool)).double()).max(dim=1).values
+    hn = (dist * (~same).double() + 1e6 * same.double()).min(dim=1).values
+    tl = F.softplus(hp - hn) if margin is None else torch.clamp(hp - hn + margin, min=0)
+    tl.sum().backward()
+    return tl.detach().numpy(), tf_.grad.numpy()
+
+
+@pytest.mark.parametrize('margin', [None, 0.3, -1.0, 0.0])
+@pytest.mark.parametrize('layout', ['no_positives', 'no_negatives', 'duplicated_anchor', 'one_sample'])
+def test_triplet_degenerate_batches_match_torch_restatement(layout, margin):
+    """the literal masked formula of loss.py:47-78 under autograd.  Inputs are untied (autograd's rule for a tied max is its own):
+    without positives the masked maximum is a constant 0 in every column and carries no gradient in either implementation only
+    because the mask multiplies it away, without negatives the minimum is the constant 1e6."""
+    rng = np.random.default_rng(11)
+    n = 1 if layout == 'one_sample' else 7
+    f = rng.standard_normal((n, 5))
+    y = {'no_positives': np.arange(7), 'no_negatives': np.zeros(7, np.int64), 'duplicated_anchor': np.array([0, 0, 1, 2, 3, 4, 5]),
+         'one_sample': np.zeros(1, np.int64)}[layout]
+    if layout == 'duplicated_anchor':
+        f[0] += 50.0                              # far from the rest: the equal rows 0, 1 are nobody's hardest negative (no tie)
+        f[1] = f[0]
+    loss, df = ops.batch_hard_triplet(f, y, margin)
+    want_loss, want_df = _triplet_autograd(f, y, margin)
+    assert np.isfinite(df).all() and np.isfinite(want_df).all()
+    np.testing.assert_allclose(loss, want_loss, atol=1e-12)
+    np.testing.assert_allclose(df, want_df, atol=1e-10)
+    if layout in ('no_negatives', 'one_sample'):
+        assert np.abs(df).max() == 0 or margin is None          # hinge far below zero: exactly no gradient
+        assert np.abs(df).max() < 1e-300
+    if layout == 'duplicated_anchor':
+        assert np.abs(loss[0] - loss[1]) == 0 and np.sqrt(1e-12) * 0.99 < 1e-6
+
+
+@pytest.mark.parametrize('alpha', [1.0, 1.5])
+def test_focal_loss_saturated_rows_match_torch_autograd(alpha):
+    """target logit 20 above the rest (1 - q ~ 2e-8) and 20 below (q ~ 2e-10), c = 10: finite, and equal to autograd of the formula"""
+    rng = np.random.default_rng(1)
+    z = rng.standard_normal((6, 10)) * 0.5
+    y = rng.integers(0, 10, 6)
+    for i, gap in enumerate((20, 20, -20, -20)):
+        rest = np.delete(z[i], y[i])
+        z[i, y[i]] = rest.max() + gap if gap > 0 else rest.min() + gap
+    loss, d = ops.focal_loss(z, y, 1.0, alpha)
+    t = torch.tensor(z, requires_grad=True)
+    ce = F.cross_entropy(t, torch.tensor(y), reduction='none')
+    sc = torch.softmax(t, 1)[torch.arange(6), torch.tensor(y)]
+    ref = ((1 - sc) ** alpha * ce).mean()
+    ref.backward()
+    assert np.isfinite(d).all() and np.isfinite(loss)
+    assert abs(loss - ref.item()) < 1e-12
+    np.testing.assert_allclose(d, t.grad.numpy(), atol=1e-12)
+    assert np.abs(d[:2]).max() < 1e-6 and np.abs(d[2:4]).max() > 0.1 / 6
+    # a gap of 40: 1 - q is exactly 0 in float64 and the reference stays finite (0 ** 0 = 1 times log q = 0 at alpha 1)
+    z[0, y[0]] += 20
+    loss40, d40 = ops.focal_loss(z, y, 1.0, alpha)
+    assert np.isfinite(d40).all() and np.isfinite(loss40) and np.abs(d40[0]).max() == 0
+
+
+def test_center_loss_one_class_and_one_sample():
+    rng = np.random.default_rng(2)
+    f = rng.standard_normal((9, 4)); cen = rng.standard_normal((3, 4))
+    y = np.full(9, 2)
+    loss, df, newc = ops.center_loss(f, y, cen, 0.9)
+    assert abs(loss - ((f - cen[2]) ** 2).mean()) < 1e-15
+    np.testing.assert_allclose(df, 2 * (f - cen[2]) / 36, atol=1e-15)
+    np.testing.assert_array_equal(newc[:2], cen[:2])
+    np.testing.assert_allclose(newc[2], cen[2] + 0.1 * (f - cen[2]).sum(0), atol=1e-14)       # nine updates from the OLD center, summed
+    loss, df, newc = ops.center_loss(f[:1], np.array([1]), cen, 0.9)
+    assert abs(loss - ((f[0] - cen[1]) ** 2).mean()) < 1e-15
+    np.testing.assert_allclose(df, 2 * (f[:1] - cen[1]) / 4, atol=1e-15)
+    np.testing.assert_allclose(newc[1], 0.9 * cen[1] + 0.1 * f[0], atol=1e-15)
+    np.testing.assert_array_equal(newc[[0, 2]], cen[[0, 2]])

@@ -1214,15 +1214,15 @@ int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn,
     return rc(k_margin_softmax(s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
 }
 int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int n, int c, int ld, void* stream) {
-    if (!G || !s || !wn || !colcoef) return FTE_EINVAL;
+    if (!G || !s || !wn || !colcoef || n <= 0 || c <= 0 || ld < c) return FTE_EINVAL;
     return rc(k_asoftmax_colcoef(G, s, wn, colcoef, n, c, ld, (hipStream_t)stream));
 }
 int fte_row_norms(const float* a, float* out, int rows, int cols, int ld, void* stream) {
-    if (!a || !out || rows <= 0) return FTE_EINVAL;
+    if (!a || !out || rows <= 0 || cols <= 0 || ld < cols) return FTE_EINVAL;
     return rc(k_row_norms(a, out, rows, cols, ld, (hipStream_t)stream));
 }
 int fte_col_norms(const float* a, float* out, int rows, int cols, int ld, void* stream) {
-    if (!a || !out || rows <= 0) return FTE_EINVAL;
+    if (!a || !out || rows <= 0 || cols <= 0 || ld < cols) return FTE_EINVAL;
     return rc(k_col_norms(a, out, rows, cols, ld, (hipStream_t)stream));
 }
 int fte_flip_width(const float* x, float* y, int n, int h, int wd, int c, void* stream) {
@@ -1235,7 +1235,7 @@ int fte_axpby(float a, const float* x, float b, const float* y, float* out, long
     return rc(k_axpby(a, x, b, y, out, n, (hipStream_t)stream));
 }
 int fte_add_scaled_rows_cols(float* a, const float* b, const float* rcf, const float* cc, int rows, int cols, int ld, void* stream) {
-    if (!a || !b || rows <= 0) return FTE_EINVAL;
+    if (!a || !b || rows <= 0 || cols <= 0 || ld < cols) return FTE_EINVAL;
     return rc(k_add_scaled(a, b, rcf, cc, rows, cols, ld, (hipStream_t)stream));
 }
 int fte_center_loss_fwd_bwd_update(const float* feat, const int32_t* labels, float* centers, float* loss_rows, float* dfeat,
@@ -1250,7 +1250,8 @@ int fte_center_scatter_update(const float* diff, const int32_t* labels, float* c
 }
 int fte_batch_hard_triplet_fwd_bwd(const float* feat, const int32_t* labels, float margin, int soft_margin, float loss_weight,
                                    float* loss_rows, float* dfeat, int n, int d, void* ws, size_t ws_bytes, void* stream) {
-    if (!feat || !labels || !loss_rows || !dfeat || n <= 0) return FTE_EINVAL;
+    // n <= 8192: triplet_grad_kernel keeps a coefficient row of n floats in LDS (and 2*n*n floats of workspace stay below 2 GiB)
+    if (!feat || !labels || !loss_rows || !dfeat || n <= 0 || n > 8192 || d <= 0) return FTE_EINVAL;
     if (!ws || ws_bytes < (size_t)2 * n * n * sizeof(float)) return FTE_EWORKSPACE;
     return rc(k_triplet(feat, labels, margin, soft_margin != 0, loss_weight, loss_rows, dfeat, n, d, (float*)ws, (hipStream_t)stream));
 }
@@ -1262,12 +1263,12 @@ int fte_reduce_rows(const float* in, float* out, const float* bias, int bmod, lo
     return rc(k_reduce_rows(in, out, bias, bmod > 0 ? bmod : 1, rows, cols, fold, scale, nullptr, (hipStream_t)stream));
 }
 int fte_sumsq(const float* a, long n, float scale, float* out, void* ws, size_t ws_bytes, void* stream) {
-    if (!a || !out || ((uintptr_t)a & 15)) return FTE_EINVAL;
+    if (!a || !out || n <= 0 || ((uintptr_t)a & 15)) return FTE_EINVAL;
     if (!ws || ws_bytes < 1024 * sizeof(float)) return FTE_EWORKSPACE;
     return rc(k_sum(a, n, scale, out, (float*)ws, true, (hipStream_t)stream));
 }
 int fte_sum(const float* a, long n, float scale, float* out, void* ws, size_t ws_bytes, void* stream) {
-    if (!a || !out || ((uintptr_t)a & 15)) return FTE_EINVAL;
+    if (!a || !out || n <= 0 || ((uintptr_t)a & 15)) return FTE_EINVAL;
     if (!ws || ws_bytes < 1024 * sizeof(float)) return FTE_EWORKSPACE;
     return rc(k_sum(a, n, scale, out, (float*)ws, false, (hipStream_t)stream));
 }
@@ -1678,7 +1679,7 @@ int fte_gconv3x3_wgrad(const float* x, const float* dz, float* dw, int n, int h,
     return rc(k_reduce_rows((const float*)ws, dw, nullptr, 1, chunks, 9L * c * gw, 1, 1.f, (float*)((char*)ws + need), (hipStream_t)stream));
 }
 int fte_bcast_add(float* dx, const float* v, int n, int hw, int c, float scale, void* stream) {
-    if (!dx || !v || n <= 0 || c % 4) return FTE_EINVAL;
+    if (!dx || !v || n <= 0 || hw <= 0 || c <= 0 || c % 4) return FTE_EINVAL;
     return rc(l_bcast_add(dx, v, n, hw, c, scale, (hipStream_t)stream));
 }
 int fte_act_fwd(const float* x, float* y, long n, int kind, void* stream) {

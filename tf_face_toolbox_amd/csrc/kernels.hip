@@ -385,7 +385,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     for (int j = threadIdx.x; j < ld; j += 256) {
         float g = 0.f;
         if (j < c) g = (expf(z[j] - mx) * inv - (j == y ? 1.f : 0.f)) * gscale;
-        d[j] = bad ? NAN : g;
+        d[j] = (bad && j < c) ? NAN : g;                    // pad columns of a NaN row stay 0, as in the focal and margin heads
     }
     if (threadIdx.x == 0) loss_rows[row] = bad ? NAN : logf(s) - (z[y] - mx);
 }
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256) void softmax_ce_reg_kernel(const float* __rest
         const int j = threadIdx.x + 256 * i;
         if (j < ld) {
             const float g = j < c ? (v[i] * inv - (j == y ? 1.f : 0.f)) * gscale : 0.f;
-            d[j] = bad ? NAN : g;
+            d[j] = (bad && j < c) ? NAN : g;
         }
     }
     if (threadIdx.x == 0) loss_rows[row] = bad ? NAN : logf(s) - (z[y] - mx);
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(256) void asoftmax_kernel(const float* __restrict__
             }
         }
         gr[j] = g;
-        if (f) f[(long)row * ld + j] = fv;
+        if (f) f[(long)row * ld + j] = (bad && j < c) ? NAN : fv;      // the whole row below c is NaN, not only the columns the NaN reached
     }
     if (threadIdx.x == 0) loss_rows[row] = logf(se) - (fy - mx);
 }
