@@ -618,6 +618,28 @@ int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float*
 int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels,
                                float scale, float m, float m3, float* f, float* loss_rows, float* G, float* rowcoef,
                                int n, int c, int ld, float grad_scale, void* stream);
+/* Additive-margin softmax with a margin per row (the AdaFace head; Kim et al., CVPR 2022).  The contract is that of
+ * fte_margin_softmax_fwd_bwd above -- c_ij, z_ij for j != y, loss_rows, G, rowcoef, the optional f, columns c..ld-1, the NaN row
+ * of an out-of-range label -- with the target term of row i taken from a = a_rows[i], b = b_rows[i] (c = c_iy, E = 1e-3):
+ *   theta = acos(c),  theta' = min(max(theta + a, E), pi - E),  z_iy = S * t,  t = cos(theta') - b
+ *   t' = sin(theta') / max(sin_t, 1e-6), sin_t = sqrt(max((1 - c)(1 + c), 0)), where the clip of theta' does not bind
+ *   t' = 0 where it binds (the logit is the constant cos(E) - b or -cos(E) - b there: AdaFace's clip under autograd)
+ * a may be negative.  A NaN or infinite a or b gives a NaN row like an out-of-range label.  a_i = 0, b_i = m3 is CosFace and
+ * a_i = m, b_i = 0 is ArcFace on the rows with c_iy > cos(pi - m) whose theta' stays inside the clip.
+ * FTE_EINVAL: a null pointer (f excepted), n < 1, c < 1, ld < c, scale <= 0 (or NaN). */
+int fte_margin_softmax_rows_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale,
+                                    const float* a_rows, const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef,
+                                    int n, int c, int ld, float grad_scale, void* stream);
+/* AdaFace's margins from the embedding norms xn [n] (fte_row_norms) and the running statistics stats = [mean, std]:
+ *   q_i = min(max(xn_i, 1e-3), 100),  mean_b = sum q / n,  std_b = sqrt(sum (q - mean_b)^2 / (n - 1))   (two passes)
+ *   mu = t_alpha * mean_b + (1 - t_alpha) * stats[0],  sd = t_alpha * std_b + (1 - t_alpha) * stats[1]
+ *   k_i = min(max((q_i - mu) / (sd + 1e-3) * h, -1), 1),  a_rows[i] = -m * k_i,  b_rows[i] = m + m * k_i
+ * update != 0: stats is overwritten with (mu, sd); update == 0: stats is left alone (the margins use (mu, sd) either way).
+ * One block, one launch, no host read-back; the sums run in a fixed order: two calls on the same data are bit-identical.  The
+ * norm enters the margins as a constant (no gradient flows through k_i), as in the paper.
+ * FTE_EINVAL: a null pointer, n < 2, m < 0, h <= 0, t_alpha outside [0, 1] (or any of them NaN). */
+int fte_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats,
+                        float* a_rows, float* b_rows, void* stream);
 /* out[i] = sqrt(sum_j a[i,j]^2) over rows of [rows, ld] (cols used) */
 int fte_row_norms(const float* a, float* out, int rows, int cols, int ld, void* stream);
 /* out[j] = sqrt(sum_i a[i,j]^2) over columns */

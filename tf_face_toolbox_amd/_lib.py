@@ -152,6 +152,8 @@ _SIGS = {
     'fte_asoftmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
     'fte_asoftmax_colcoef': (c_int, [_P] * 4 + [c_int] * 3 + [_P]),
     'fte_margin_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] * 3 + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
+    'fte_margin_softmax_rows_fwd_bwd': (c_int, [_P] * 4 + [c_float] + [_P] * 6 + [c_int] * 3 + [c_float, _P]),
+    'fte_adaface_margins': (c_int, [_P, c_int] + [c_float] * 3 + [c_int] + [_P] * 4),
     'fte_row_norms': (c_int, [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_col_norms': (c_int, [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_add_scaled_rows_cols': (c_int, [_P] * 4 + [c_int] * 3 + [_P]),

@@ -1213,6 +1213,19 @@ int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn,
         return FTE_EINVAL;
     return rc(k_margin_softmax(s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
 }
+int fte_margin_softmax_rows_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale,
+                                    const float* a_rows, const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef,
+                                    int n, int c, int ld, float grad_scale, void* stream) {
+    if (!s || !xn || !wn || !labels || !a_rows || !b_rows || !loss_rows || !G || !rowcoef || n <= 0 || c <= 0 || ld < c || !(scale > 0.f))
+        return FTE_EINVAL;
+    return rc(k_margin_softmax_rows(s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, n, c, ld, grad_scale,
+                                    (hipStream_t)stream));
+}
+int fte_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats, float* a_rows, float* b_rows,
+                        void* stream) {
+    if (!xn || !stats || !a_rows || !b_rows || n < 2 || !(m >= 0.f) || !(h > 0.f) || !(t_alpha >= 0.f && t_alpha <= 1.f)) return FTE_EINVAL;
+    return rc(k_adaface_margins(xn, n, m, h, t_alpha, update, stats, a_rows, b_rows, (hipStream_t)stream));
+}
 int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int n, int c, int ld, void* stream) {
     if (!G || !s || !wn || !colcoef || n <= 0 || c <= 0 || ld < c) return FTE_EINVAL;
     return rc(k_asoftmax_colcoef(G, s, wn, colcoef, n, c, ld, (hipStream_t)stream));

@@ -25,6 +25,11 @@ hipError_t k_asoftmax(const float* s, const float* xn, const float* wn, const in
                       float* G, float* rowcoef, int n, int c, int ld, float gs, hipStream_t st);
 hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m, float m3,
                             float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs, hipStream_t st);
+hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, const float* a_rows,
+                                 const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
+                                 hipStream_t st);
+hipError_t k_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats, float* a_rows, float* b_rows,
+                             hipStream_t st);
 hipError_t k_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* cc, int n, int c, int ld, hipStream_t st);
 hipError_t k_row_norms(const float* a, float* out, int rows, int cols, int ld, hipStream_t st);
 hipError_t k_col_norms(const float* a, float* out, int rows, int cols, int ld, hipStream_t st);

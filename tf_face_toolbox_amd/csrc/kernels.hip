@@ -705,6 +705,183 @@ __global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __rest
     }
 }
 
+// The same head with the margin of each row its own (AdaFace; fte.h fte_margin_softmax_rows_fwd_bwd): theta' = theta + a_i clipped
+// to [E, pi - E], t = cos(theta') - b_i.  Inside the clip cos(theta + a) and sin(theta + a) come from c, sin_t and one
+// sincos(a) -- no error of acos enters the logit; acos only decides whether the clip binds.  The per-row work is two scalar
+// loads and one acosf / sincosf; the two passes are margin_softmax_kernel's, statement for statement.  A kernel of its own and
+// not a shared body: with the passes in one inlined function the compiler allocated margin_softmax_kernel's registers
+// differently (2163 -> 2142 instructions for VEC), and that kernel's code is to stay as it is.
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_softmax_rows_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                  const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                  float S, const float* __restrict__ a_rows,
+                                                                  const float* __restrict__ b_rows, float* __restrict__ f,
+                                                                  float* __restrict__ loss_rows, float* __restrict__ G,
+                                                                  float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    constexpr int U = 4;                                        // chunks in flight per thread and trip
+    constexpr float EPS = 1e-12f, E = 1e-3f, PI = 3.14159265358979323846f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * ld;
+    float* gr = G + (long)row * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const int yl = labels[row];
+    const float am = a_rows[row], bm = b_rows[row];
+    // out-of-range label or a NaN / infinite margin: NaN row, no out-of-bounds access
+    const bool bad = (unsigned)yl >= (unsigned)c || !(fabsf(am) <= 3.4028234664e38f) || !(fabsf(bm) <= 3.4028234664e38f);
+    const int y = (unsigned)yl >= (unsigned)c ? 0 : yl;
+    const float xr = xn[row];
+    MarginRow R;
+    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
+    R.S = S;
+    R.y = y;
+    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
+    const float th = acosf(cy) + am;
+    float ty, tp;
+    if (th < E) {                                               // the clip binds: constant logit, zero derivative
+        ty = cosf(E) - bm; tp = 0.f;
+    } else if (th > PI - E) {
+        ty = -cosf(E) - bm; tp = 0.f;
+    } else {
+        float sa, ca;
+        sincosf(am, &sa, &ca);
+        const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+        ty = cy * ca - st * sa - bm;                            // cos(theta + a) - b
+        tp = (st * ca + cy * sa) / fmaxf(st, 1e-6f);            // sin(theta + a) / max(sin_t, 1e-6)
+    }
+    R.zy = S * ty;
+
+    // pass 1: online max / sum of exp
+    float mx = -INFINITY, se = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < c; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    float z[4], r;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
+                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
+                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < c; j += 256) {
+            float r;
+            const float z = R.z(sr[j], wn[j], j, r);
+            if (z > mx) { se *= __expf(mx - z); mx = z; }
+            se += __expf(z - mx);
+        }
+    }
+    const float M = block_max(mx, sh);
+    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
+    const float inv = 1.f / se;
+    const float gS = gscale * S, gT = gscale * S * tp;
+
+    // pass 2: G (and f), sum of G * s
+    float acc = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < ld; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < ld) {
+                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
+                    if (j < c) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (j + k < c) {
+                                float r;
+                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
+                                const float p = __expf(z - M) * inv;
+                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
+                                acc += g * sv[u][k];
+                                gv[k] = g;
+                                fv[k] = z;
+                            }
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(gr + j) = gv;
+                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < ld; j += 256) {
+            float g = 0.f, fv = 0.f;
+            if (j < c) {
+                float r;
+                const float sv = sr[j];
+                const float z = R.z(sv, wn[j], j, r);
+                const float p = __expf(z - M) * inv;
+                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
+                acc += g * sv;
+                fv = z;
+            }
+            gr[j] = g;
+            if (fr) fr[j] = fv;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (t == 0) {
+        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
+        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
+    }
+}
+
+// AdaFace margins from the embedding norms (fte.h fte_adaface_margins).  ONE block: every thread sums its strided elements in
+// index order, the partials merge through block_sum in a fixed order (two calls on the same data are bit-identical); two passes
+// (mean, then squared deviations), the running statistics blended on the device -- no host read-back.
+__global__ __launch_bounds__(256) void adaface_margins_kernel(const float* __restrict__ xn, int n, float m, float h, float t_alpha,
+                                                              int update, float* __restrict__ stats, float* __restrict__ a_rows,
+                                                              float* __restrict__ b_rows) {
+    __shared__ float sh[4];
+    const int t = threadIdx.x;
+    float acc = 0.f;
+    for (int i = t; i < n; i += 256) acc += fminf(fmaxf(xn[i], 1e-3f), 100.f);
+    const float mean_b = block_sum(acc, sh) / (float)n;
+    acc = 0.f;
+    for (int i = t; i < n; i += 256) {
+        const float d = fminf(fmaxf(xn[i], 1e-3f), 100.f) - mean_b;
+        acc += d * d;
+    }
+    const float std_b = sqrtf(block_sum(acc, sh) / (float)(n - 1));
+    const float mu = t_alpha * mean_b + (1.f - t_alpha) * stats[0];
+    const float sd = t_alpha * std_b + (1.f - t_alpha) * stats[1];
+    const float inv = h / (sd + 1e-3f);
+    for (int i = t; i < n; i += 256) {
+        const float q = fminf(fmaxf(xn[i], 1e-3f), 100.f);
+        const float k = fminf(fmaxf((q - mu) * inv, -1.f), 1.f);
+        a_rows[i] = -m * k;
+        b_rows[i] = m + m * k;
+    }
+    __syncthreads();                                            // every thread has read stats
+    if (update && t == 0) { stats[0] = mu; stats[1] = sd; }
+}
+
 __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict__ a, float* __restrict__ out, int cols, int ld) {
     __shared__ float sh[4];
     const float* r = a + (long)blockIdx.x * ld;
@@ -1201,6 +1378,19 @@ hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, co
     const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
     if (vec) hipLaunchKernelGGL(margin_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(margin_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, const float* a_rows,
+                                 const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
+                                 hipStream_t st) {
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    if (vec) hipLaunchKernelGGL(margin_softmax_rows_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
+    else hipLaunchKernelGGL(margin_softmax_rows_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats, float* a_rows, float* b_rows,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(adaface_margins_kernel, dim3(1), dim3(256), 0, st, xn, n, m, h, t_alpha, update, stats, a_rows, b_rows);
     return hipGetLastError();
 }
 hipError_t k_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* cc, int n, int c, int ld, hipStream_t st) {

@@ -1,5 +1,5 @@
 """Host-side mirror of the reference's loss.py: focal_loss (:18-27), center_loss (:29-45), batch_hard_triplet_loss
-(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference) and its sampled-class form partial_fc_margin_loss.  Same names, argument meaning and defaults.  There is no autograd here, so every function
+(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference), its sampled-class form partial_fc_margin_loss and adaface_loss (the margin per row from the feature norms).  Same names, argument meaning and defaults.  There is no autograd here, so every function
 also returns the gradient of ITS OWN loss value with respect to its first argument (what tf.gradients would have
 produced for that term); the graph nets wire them as heads (nets/graph.py), a caller can combine them freely.
 
@@ -106,6 +106,48 @@ def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, marg
     call('fte_col_norms', weights, wn, d, c, ld, st)
     call('fte_margin_softmax_fwd_bwd', s, xn, wn, labels, float(scale), float(margin), float(margin_cos), None, rows, G, rowcoef,
          n, c, ld, 1.0 / n, st)
+    call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, c, ld, st)
+    call('fte_gemm_tn', features, G, dw, n, ld, d, ws, wsb, st)
+    call('fte_add_scaled_rows_cols', dw, weights, None, colcoef, d, ld, ld, st)
+    call('fte_gemm_nt', G, weights, None, None, 0, None, dx, None, n, ld, d, ws, wsb, st)
+    call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
+    return _scaled_sum(rows, 1.0 / n), dx, dw
+
+
+def adaface_loss(features, weights, labels, stats, scale=64.0, margin=0.4, h=0.333, t_alpha=0.01, update=True, num_classes=None):
+    """AdaFace (Kim et al., CVPR 2022): additive_margin_loss with the margin of each row set from the norm of its feature vector against
+    running statistics of the norms; the contract is fte.h's fte_adaface_margins / fte_margin_softmax_rows_fwd_bwd.  `stats` is the
+    float32 CUDA tensor [mean, std] (the paper's code starts it at [20, 100]); with `update` it is moved in place by the batch's
+    statistics (weight t_alpha), otherwise left alone -- the margins use the blended values either way.  The other arguments, the
+    shapes and the result (loss, dfeatures, dweights) are additive_margin_loss's; the norm enters the margins as a constant."""
+    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
+    weights = _check(weights, torch.float32, 'weights')
+    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2):
+        raise TypeError('stats must be a contiguous float32 CUDA tensor of 2 elements [mean, std]')
+    n, d = features.shape
+    ld = weights.shape[1]
+    if weights.shape[0] != d or labels.shape != (n,):
+        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
+                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
+    c = ld if num_classes is None else int(num_classes)
+    st = _stream()
+    dev = features.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    wsb = max(_lib.query('fte_gemm_ws_bytes', n, ld, d), 4096)
+    ws = torch.empty(wsb // 4 + 1024, **f32)
+    wsb = ws.numel() * 4
+    s = torch.empty(n, ld, **f32)
+    xn, rowcoef, rows = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
+    a_rows, b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
+    wn, colcoef = torch.empty(ld, **f32), torch.empty(ld, **f32)
+    G = torch.empty(n, ld, **f32)
+    dx, dw = torch.empty_like(features), torch.empty_like(weights)
+    call = _lib.call
+    call('fte_gemm_nn', features, weights, None, s, n, ld, d, ws, wsb, st)
+    call('fte_row_norms', features, xn, n, d, d, st)
+    call('fte_adaface_margins', xn, n, float(margin), float(h), float(t_alpha), int(bool(update)), stats, a_rows, b_rows, st)
+    call('fte_col_norms', weights, wn, d, c, ld, st)
+    call('fte_margin_softmax_rows_fwd_bwd', s, xn, wn, labels, float(scale), a_rows, b_rows, None, rows, G, rowcoef, n, c, ld, 1.0 / n, st)
     call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, c, ld, st)
     call('fte_gemm_tn', features, G, dw, n, ld, d, ws, wsb, st)
     call('fte_add_scaled_rows_cols', dw, weights, None, colcoef, d, ld, ld, st)

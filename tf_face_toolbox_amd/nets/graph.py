@@ -13,7 +13,7 @@ from collections import OrderedDict
 import torch
 
 from .. import _lib
-from .net_base import MARGIN_PRESETS, Network, margin_params, side_stream
+from .net_base import MARGIN_PRESETS, NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
 from .sphere import Variable, same_pads
 
 BN_EPS = 1e-3          # nets/resnet.py:97-99 via layers.batch_norm defaults
@@ -82,7 +82,10 @@ class GraphNet(Network):
     unpadded net's while all kernels keep their float4 / MFMA-tile granularity.  Heads: 'softmax' (CE on the classifier), 'focal' (loss.py:18-27 instead of CE), 'softmax+center' (CE + weight * center loss
     on the pooled features, loss.py:29-45), 'triplet' (batch-hard triplet on the pooled features, loss.py:47-78, no
     classifier) and 'arcface' / 'cosface' (additive-margin softmax on the normalised classifier input and columns, fte.h
-    fte_margin_softmax_fwd_bwd; (S, m, m3) in margin_scale / margin / margin_cos)."""
+    fte_margin_softmax_fwd_bwd; (S, m, m3) in margin_scale / margin / margin_cos) and 'adaface' (the same head with the margin of
+    each row set from the norm of the classifier's input against two running scalars, fte.h fte_adaface_margins /
+    fte_margin_softmax_rows_fwd_bwd; (S, m) in margin_scale / margin, h / t_alpha in adaface_h / adaface_t_alpha; the scalars are
+    state like the BN moving statistics and move under the same switch, update_moving_stats)."""
 
     head = 'softmax'
     channel_pad = 1
@@ -115,6 +118,11 @@ class GraphNet(Network):
         self.head = head
         if head in MARGIN_PRESETS:
             self.margin_scale, self.margin, self.margin_cos = margin_params(head, scale, margin, margin_cos)
+        elif head == 'adaface':
+            if margin_cos is not None:
+                raise ValueError('the adaface head has no margin_cos')
+            self.margin_scale, self.margin, self.adaface_h, self.adaface_t_alpha = adaface_params(scale, margin)
+            self.margin_cos = 0.0
         elif (scale, margin, margin_cos) != (None, None, None):
             raise ValueError('scale / margin / margin_cos belong to the arcface / cosface heads, not %r' % head)
 
@@ -179,6 +187,9 @@ class GraphNet(Network):
                 self.state[pre + '/moving_mean'] = torch.zeros(cp, dtype=torch.float32, device=dev)
                 self.state[pre + '/moving_variance'] = torch.ones(cp, dtype=torch.float32, device=dev)
                 self.state_ref[pre + '/moving_mean'] = self.state_ref[pre + '/moving_variance'] = s[0]
+        if self.head == 'adaface':                        # the head's running norm statistics: two more non-trainable variables
+            self.adaface_stats, extra = adaface_state(dev)
+            self.state.update(extra)
         self._init_params()
         self._compile()
         self.built = True
@@ -719,9 +730,11 @@ class GraphNet(Network):
         fdim = self.shapes[self.feature_name][0]
         self.dfeat = torch.empty(n, fdim, **f32)
         self.ones_n = torch.ones(n, **f32)
-        if self.head in MARGIN_PRESETS:
+        if self.head in NORMALISED_HEADS:
             self.xn, self.rowcoef = torch.empty(n, **f32), torch.empty(n, **f32)
             self.wn, self.colcoef = torch.empty(self.cpad, **f32), torch.empty(self.cpad, **f32)
+        if self.head == 'adaface':
+            self.a_rows, self.b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
         need = max(need, 4 * n * fdim, 12 * n * n)
         self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
         self.ws_bytes = self.ws.numel() * 4
@@ -1171,14 +1184,21 @@ class GraphNet(Network):
             if self.head == 'focal':                         # loss.py:18-27 on the classifier logits
                 call('fte_focal_loss_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.focal_gamma, self.focal_alpha, self.tower_scale / n, st)
-            elif self.head in MARGIN_PRESETS:                # the margin on the raw classifier output; backward_head adds the norm terms
+            elif self.head in NORMALISED_HEADS:              # the margin on the raw classifier output; backward_head adds the norm terms
                 op = self.plan[-1]
                 k = self.shapes[op[2]][0]
                 call('fte_row_norms', self.t[op[2]], self.xn, n, k, k, st)
                 call('fte_col_norms', self.view(op[3]), self.wn, k, self.num_classes, self.cpad, st)
-                call('fte_margin_softmax_fwd_bwd', self.t['logits'], self.xn, self.wn, labels, self.margin_scale, self.margin,
-                     self.margin_cos, None, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
-                     self.tower_scale / n, st)
+                if self.head == 'adaface':                   # per-row margins from the norms; the running statistics move with BN's
+                    call('fte_adaface_margins', self.xn, n, self.margin, self.adaface_h, self.adaface_t_alpha,
+                         int(self.update_moving_stats), self.adaface_stats, self.a_rows, self.b_rows, st)
+                    call('fte_margin_softmax_rows_fwd_bwd', self.t['logits'], self.xn, self.wn, labels, self.margin_scale, self.a_rows,
+                         self.b_rows, None, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
+                         self.tower_scale / n, st)
+                else:
+                    call('fte_margin_softmax_fwd_bwd', self.t['logits'], self.xn, self.wn, labels, self.margin_scale, self.margin,
+                         self.margin_cos, None, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
+                         self.tower_scale / n, st)
                 call('fte_asoftmax_colcoef', self.G, self.t['logits'], self.wn, self.colcoef, n, self.num_classes, self.cpad, st)
             else:
                 call('fte_softmax_ce_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
@@ -1283,7 +1303,7 @@ class GraphNet(Network):
         self._grad = {}
         gin = torch.empty(n, k, dtype=torch.float32, device=self.device)
         side = self.side if os.environ.get('FTE_HEAD_SIDE', '1') != '0' else None
-        margin = self.head in MARGIN_PRESETS
+        margin = self.head in NORMALISED_HEADS
         gw = self.view(op[3], self.grads)
         if side is not None:
             main = torch.cuda.current_stream()

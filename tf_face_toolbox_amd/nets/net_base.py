@@ -26,6 +26,32 @@ def margin_params(head, scale=None, margin=None, margin_cos=None):
     return S, m, m3
 
 
+# AdaFace (Kim et al. 2022: s = 64, m = 0.4, h = 0.333, t_alpha = 0.01): the margin of each image follows the norm of its embedding,
+# measured against running statistics of the norms -- two non-trainable variables, initialised to mean 20 and std 100
+ADAFACE_PRESET = (64.0, 0.4, 0.333, 0.01)
+ADAFACE_STATS_INIT = (20.0, 100.0)
+ADAFACE_STATE = ('classifier/adaface/batch_mean', 'classifier/adaface/batch_std')
+# heads on the normalised embedding and classifier columns: xn / wn / rowcoef / colcoef buffers and the norm-correction backward
+NORMALISED_HEADS = tuple(MARGIN_PRESETS) + ('adaface',)
+
+
+def adaface_params(scale=None, margin=None, h=None, t_alpha=None):
+    """(S, m, h, t_alpha) of the AdaFace head: the given values, the preset where an argument is None."""
+    vals = [float(p if v is None else v) for p, v in zip(ADAFACE_PRESET, (scale, margin, h, t_alpha))]
+    S, m, h_, ta = vals
+    if not (S > 0.0 and 0.0 <= m < 1.5707963267948966 and h_ > 0.0 and 0.0 <= ta <= 1.0):
+        raise ValueError('AdaFace head needs scale > 0, 0 <= margin < pi/2, h > 0 and 0 <= t_alpha <= 1 (got %r, %r, %r, %r)' % tuple(vals))
+    return S, m, h_, ta
+
+
+def adaface_state(device):
+    """-> (stats, state): the [mean, std] pair the kernel updates in place and its two one-element views under their variable names"""
+    import torch
+    from collections import OrderedDict
+    stats = torch.tensor(ADAFACE_STATS_INIT, dtype=torch.float32, device=device)
+    return stats, OrderedDict((name, stats[i:i + 1]) for i, name in enumerate(ADAFACE_STATE))
+
+
 def net_select(name, data_format='NCHW', weight_decay=5e-4):
     """nets/net_base.py:22-63.  Names kept verbatim; `SphereNet-ASoftmax` is the margin net the
     reference's `DataParallel_margin` (data_parallel.py:220) expects but whose code is missing
@@ -39,10 +65,13 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4):
     elif name in ('SphereNet-ArcFace', 'SphereNet-CosFace'):      # additive-margin heads (fte.h fte_margin_softmax_fwd_bwd)
         from .sphere import SphereNetAdditiveMargin
         network = SphereNetAdditiveMargin(data_format=data_format, weight_decay=weight_decay, head=name.split('-')[1].lower())
+    elif name == 'SphereNet-AdaFace':                             # quality-adaptive margin head (fte.h fte_adaface_margins)
+        from .sphere import SphereNetAdaFace
+        network = SphereNetAdaFace(data_format=data_format, weight_decay=weight_decay)
     elif name == 'ResNet-50':
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay)
-    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface'):
+    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface', 'ResNet-50-adaface'):
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay, head=name.split('-')[2])
     elif name == 'ResNet-26':                    # not a reference factory name; the class accepts 26 (nets/resnet.py:39-40)
@@ -115,6 +144,12 @@ class Network(abc.ABC):
         """Margin nets only: replace the head's (S, m, m3) -- train.py --margin_scale / --margin / --margin_cos; None keeps a
         value.  Takes effect from the next forward / loss_function."""
         head = getattr(self, 'head', None)
+        if head == 'adaface':                            # S and m; the head has no cosine margin of its own (b_i follows the norm)
+            if margin_cos is not None:
+                raise ValueError('%s: the AdaFace head has no margin_cos' % self.name)
+            self.margin_scale, self.margin, _, _ = adaface_params(self.margin_scale if scale is None else scale,
+                                                                  self.margin if margin is None else margin, self.adaface_h, self.adaface_t_alpha)
+            return
         if head not in MARGIN_PRESETS:
             raise ValueError('%s has no additive-margin head' % self.name)
         self.margin_scale, self.margin, self.margin_cos = margin_params(

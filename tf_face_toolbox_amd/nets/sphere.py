@@ -24,7 +24,7 @@ import torch
 
 from .. import _lib
 from ..loss import sample_size
-from .net_base import MARGIN_PRESETS, Network, margin_params, side_stream
+from .net_base import NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
 
 NUM_BLOCKS = (1, 2, 4, 1)     # nets/sphere.py:58,62,66,70
 EMBED = 512                   # nets/sphere.py:73
@@ -123,9 +123,14 @@ class SphereNet(Network):
         self.params = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grads = torch.zeros(off + 4, dtype=torch.float32, device=dev)      # +4: [ce, reg, -, -] loss slots
         self.loss_slots = self.grads[off:off + 4]
+        self.state = self._make_state()                   # non-trainable variables: outside the arena, never all-reduced
         self._init_params()
         self.built = True
         return self
+
+    def _make_state(self):
+        """name -> tensor of the head's non-trainable variables (saver.py writes them beside the weights); none for most heads"""
+        return OrderedDict()
 
     def view(self, name, arena=None):
         v = self.variables[name]
@@ -163,6 +168,8 @@ class SphereNet(Network):
 
     def get_variable(self, name, arena=None):
         """Value of a variable (or of its gradient / slot when `arena` is given) in the REFERENCE layout."""
+        if name in self.state:
+            return self.state[name].clone()
         v = self.variables[name]
         t = self.view(name, arena)
         if v.kind == 'cls_w':
@@ -173,6 +180,9 @@ class SphereNet(Network):
 
     def set_variable(self, name, value, arena=None):
         """Write a reference-layout value into the variable (or into its slot of another arena)."""
+        if name in self.state:
+            self.state[name].copy_(torch.as_tensor(value, dtype=torch.float32).reshape(self.state[name].shape))
+            return
         v = self.variables[name]
         t = torch.as_tensor(value, dtype=torch.float32).to(self.device)
         assert tuple(t.shape) == v.ref_shape, (name, tuple(t.shape), v.ref_shape)
@@ -217,7 +227,7 @@ class SphereNet(Network):
         hw = self._head_width()                           # cpad; the sampled-class head: its Spad columns
         self.s_raw = torch.empty(n, hw, **f32)
         self.G = torch.empty(n, hw, **f32)
-        self.logits_buf = torch.empty(n, hw, **f32) if self.head == 'asoftmax' or self.head in MARGIN_PRESETS else self.s_raw
+        self.logits_buf = torch.empty(n, hw, **f32) if self.head == 'asoftmax' or self.head in NORMALISED_HEADS else self.s_raw
         self.loss_rows = torch.empty(n, **f32)
         self.xn = torch.empty(n, **f32)
         self.wn = torch.empty(hw, **f32)
@@ -847,6 +857,41 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, gwc, EMBED, self.num_classes, self.cpad, S, spad, st)
         call('fte_gemm_nt', self.G, self.Ws, None, None, 0, None, self.demb, None, n, spad, EMBED, self.ws, self.ws_bytes, st)
         call('fte_add_scaled_rows_cols', self.demb, self.emb, self.rowcoef, None, n, EMBED, EMBED, st)
+
+    def _others(self):
+        return OrderedDict()
+
+
+class SphereNetAdaFace(SphereNetMargin):
+    """SphereNet-20 + the AdaFace head (Kim et al., CVPR 2022): the additive-margin softmax with the margin of each image set from
+    the norm of its embedding against running statistics of the norms -- low-norm (unrecognisable) images get a positive angular
+    margin and a small additive one, high-norm ones the reverse; fte.h fte_adaface_margins / fte_margin_softmax_rows_fwd_bwd state the contract.  `scale` /
+    `margin` / `h` / `t_alpha` = S / m / h / t_alpha, None = the preset (nets/net_base.py ADAFACE_PRESET).  The call order and the
+    norm-correction backward are SphereNetAdditiveMargin's; the norm enters the margins as a constant.  State: the two running
+    scalars `classifier/adaface/batch_mean` / `batch_std` (net.state; saved and restored by saver.py, not in the arena, not
+    all-reduced: per-tower state like the BN moving statistics); they move on every training forward unless `update_moving_stats`
+    is False (the parallel wrappers' construction pass)."""
+    head = 'adaface'
+
+    def __init__(self, weight_decay=0.0005, data_format='NCHW', name='SphereNet', seed=0, scale=None, margin=None, h=None, t_alpha=None):
+        super(SphereNetAdaFace, self).__init__(weight_decay, data_format, name, seed)
+        self.margin_scale, self.margin, self.adaface_h, self.adaface_t_alpha = adaface_params(scale, margin, h, t_alpha)
+        self.margin_cos = 0.0
+        self.update_moving_stats = True
+
+    def _make_state(self):
+        self.adaface_stats, state = adaface_state(self.device)
+        return state
+
+    def _alloc_head(self, n):
+        self.a_rows = torch.empty(n, dtype=torch.float32, device=self.device)
+        self.b_rows = torch.empty(n, dtype=torch.float32, device=self.device)
+
+    def _margin_head(self, labels, n, st):
+        _lib.call('fte_adaface_margins', self.xn, n, self.margin, self.adaface_h, self.adaface_t_alpha, int(self.update_moving_stats),
+                  self.adaface_stats, self.a_rows, self.b_rows, st)
+        _lib.call('fte_margin_softmax_rows_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.margin_scale, self.a_rows, self.b_rows,
+                  self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad, self._grad_scale(n), st)
 
     def _others(self):
         return OrderedDict()
