@@ -863,6 +863,20 @@ int fte_pfc_gather_cols(const float* W, const int32_t* index, float* Ws, int D, 
  * element of dW exactly once, so whatever dW held before (NaNs included) is gone.  dWs [D, Spad], dW [D, cpad].
  * FTE_EINVAL: a NULL pointer, D < 1, C < 1, cpad < C, cpad % 4, S < 1, Spad < S, or dW not 16-byte aligned. */
 int fte_pfc_scatter_cols(const float* dWs, const int32_t* inverse, float* dW, int D, int C, int cpad, int S, int Spad, void* stream);
+/* The optimizer update of the classifier straight from the compact gradient: fte_pfc_scatter_cols followed by fte_momentum_update /
+ * fte_adam_update over the D * cpad range, in one pass that never forms the dense dW.  For every d < D, j < cpad:
+ *   g = dWs[d, inverse[j]] where j < C and 0 <= inverse[j] < S, else 0.0 (the padding columns j >= C: 0.0; the padding columns
+ *   S <= k < Spad of dWs are never read), then fte_momentum_update's / fte_adam_update's arithmetic on W[d, j] and its slots with
+ *   the same scalars (Adam: the same double-precision lr_t computed on the host from lr, b1, b2, t).
+ * The bytes of W and of the slots after the call equal those after the two-call sequence (NaN and signed-zero patterns included):
+ * dense-optimizer semantics, so the unsampled columns still decay and still move by their momentum; only the traffic of the dense
+ * dW (one write, one read) is gone.  W, acc / m, v [D, cpad]; dWs [D, Spad]; inverse [C] as fte_pfc_sample writes it.
+ * FTE_EINVAL: a NULL pointer, D < 1, C < 1, cpad < C, cpad % 4, S < 1, Spad < S, t < 1 (Adam), or W, a slot or inverse not
+ * 16-byte aligned. */
+int fte_pfc_momentum_update_cols(float* W, float* acc, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S, int Spad,
+                                 float lr, float mom, float wd, float gscale, void* stream);
+int fte_pfc_adam_update_cols(float* W, float* m, float* v, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S,
+                             int Spad, float lr, float b1, float b2, float eps, float wd, float gscale, int t, void* stream);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,8 @@ _SIGS = {
     'fte_pfc_sample': (c_int, [_P] + [c_int] * 5 + [_P] * 4 + [c_size_t, _P]),
     'fte_pfc_gather_cols': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_pfc_scatter_cols': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
+    'fte_pfc_momentum_update_cols': (c_int, [_P] * 4 + [c_int] * 5 + [c_float] * 4 + [_P]),
+    'fte_pfc_adam_update_cols': (c_int, [_P] * 5 + [c_int] * 5 + [c_float] * 6 + [c_int, _P]),
     'fte_dwconv3x3_fwd': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_dgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_wgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P, c_size_t, _P]),

@@ -1940,4 +1940,19 @@ int fte_pfc_scatter_cols(const float* dWs, const int32_t* inverse, float* dW, in
     if (!dWs || !inverse || !dW || D < 1 || C < 1 || cpad < C || cpad % 4 || S < 1 || Spad < S || ((uintptr_t)dW & 15)) return FTE_EINVAL;
     return rc(p_scatter_cols(dWs, inverse, dW, D, C, cpad, S, Spad, (hipStream_t)stream));
 }
+int fte_pfc_momentum_update_cols(float* W, float* acc, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S, int Spad,
+                                 float lr, float mom, float wd, float gscale, void* stream) {
+    if (!W || !acc || !dWs || !inverse || D < 1 || C < 1 || cpad < C || cpad % 4 || S < 1 || Spad < S ||
+        (((uintptr_t)W | (uintptr_t)acc | (uintptr_t)inverse) & 15))
+        return FTE_EINVAL;
+    return rc(p_momentum_update_cols(W, acc, dWs, inverse, D, C, cpad, S, Spad, lr, mom, wd, gscale, (hipStream_t)stream));
+}
+int fte_pfc_adam_update_cols(float* W, float* m, float* v, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S,
+                             int Spad, float lr, float b1, float b2, float eps, float wd, float gscale, int t, void* stream) {
+    if (!W || !m || !v || !dWs || !inverse || D < 1 || C < 1 || cpad < C || cpad % 4 || S < 1 || Spad < S || t < 1 ||
+        (((uintptr_t)W | (uintptr_t)m | (uintptr_t)v | (uintptr_t)inverse) & 15))
+        return FTE_EINVAL;
+    const double lr_t = (double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t));      // fte_adam_update's
+    return rc(p_adam_update_cols(W, m, v, dWs, inverse, D, C, cpad, S, Spad, (float)lr_t, b1, b2, eps, wd, gscale, (hipStream_t)stream));
+}
 }  // extern "C"

@@ -13,6 +13,11 @@
 // the COMPACT side for the gather and of the DENSE side for the scatter, 16 rows per block: the wide side of each kernel is one
 // float4 per lane (fully coalesced), the other side reads sorted columns of one row, so every 128-byte line of that row is fetched
 // once.  The scatter writes every element of dW exactly once (value or 0.0): no clear pass before it.
+//
+// Fused classifier update.  k_momentum_cols / k_adam_cols are the scatter's thread map with the optimizer in place of the store: the
+// gradient of a lane's four columns is picked from the compact dWs (or is 0.0) and goes straight into W and its slots, so the dense
+// dW is neither written nor read back.  The arithmetic is momentum_kernel's / adam_kernel's (kernels.hip) with the FMA contraction
+// those kernels compile to written out (momentum_elem / adam_elem), so the bytes of W and the slots equal scatter + dense update.
 #include <hip/hip_runtime.h>
 
 #include "partial_fc.h"
@@ -255,6 +260,104 @@ __global__ void __launch_bounds__(TPB) k_scatter(const float* __restrict__ dWs, 
     }
 }
 
+// the four compact positions of the dense columns j4 .. j4 + 3 (k_scatter's rule): ok[i] <=> column j4 + i is in the sample
+__device__ __forceinline__ void cols_of(const int32_t* __restrict__ inverse, int j4, int C, int S, int (&ks)[4], bool (&ok)[4]) {
+    if (j4 + 3 < C) {
+        const int4 iv = *(const int4*)(inverse + j4);           // inverse is 16-byte aligned and j4 a multiple of 4
+        ks[0] = iv.x; ks[1] = iv.y; ks[2] = iv.z; ks[3] = iv.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ks[i] = j4 + i < C ? inverse[j4 + i] : -1;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        ok[i] = (unsigned)ks[i] < (unsigned)S;
+        if (!ok[i]) ks[i] = 0;                                  // a valid position: picked() loads without a branch, then drops it
+    }
+}
+
+// dWs[d, k] of a sampled column, 0.0 otherwise (whatever the row holds at position 0, a NaN included, is dropped)
+__device__ __forceinline__ float picked(const float* __restrict__ row, int k, bool ok) {
+    const float g = row[k];
+    return ok ? g : 0.f;
+}
+
+// One element of momentum_kernel (kernels.hip) as the compiler contracts `av = mom * av + (gs * gv + wd * wv); wv = wv - lr * av`
+// there (read off its gfx950 code): the product gs * g is rounded, the other three multiplies are fused.  Spelt out, with
+// contraction off, so that this kernel cannot drift from the dense one.
+__device__ __forceinline__ void momentum_elem(float& w, float& a, float g, float lr, float mom, float wd, float gs) {
+#pragma clang fp contract(off)
+    float t = gs * g;
+    t = __builtin_fmaf(wd, w, t);
+    a = __builtin_fmaf(mom, a, t);
+    w = __builtin_fmaf(-lr, a, w);
+}
+
+// One element of adam_kernel (kernels.hip), likewise: only gs * g + wd * w is fused there (onto the rounded wd * w); the moment
+// updates and the step are separate multiplies and adds, the division and the square root the correctly rounded ones.
+__device__ __forceinline__ void adam_elem(float& w, float& m, float& v, float g, float lr_t, float b1, float b2, float eps, float wd,
+                                          float gs) {
+#pragma clang fp contract(off)
+    const float gv = __builtin_fmaf(gs, g, wd * w);
+    const float mv = b1 * m + (1.f - b1) * gv;
+    const float vv = b2 * v + (1.f - b2) * gv * gv;
+    m = mv;
+    v = vv;
+    w = w - lr_t * mv / (sqrtf(vv) + eps);
+}
+
+// momentum_kernel with g[d, j] = dWs[d, inverse[j]] or 0.0: W, acc [D, cpad], one float4 of each per lane and row
+__global__ void __launch_bounds__(TPB) k_momentum_cols(float* __restrict__ W, float* __restrict__ acc, const float* __restrict__ dWs,
+                                                       const int32_t* __restrict__ inverse, int D, int C, int cpad, int S, int Spad,
+                                                       float lr, float mom, float wd, float gs) {
+    const int j4 = (blockIdx.x * TPB + threadIdx.x) * 4;
+    if (j4 >= cpad) return;
+    int ks[4];
+    bool ok[4];
+    cols_of(inverse, j4, C, S, ks, ok);
+    const int d0 = blockIdx.y * ROWS;
+#pragma unroll 4
+    for (int r = 0; r < ROWS; ++r) {
+        const int d = d0 + r;
+        if (d >= D) break;
+        const float* row = dWs + (size_t)d * Spad;
+        const size_t at = (size_t)d * cpad + j4;
+        const float4 w4 = *(const float4*)(W + at), a4 = *(const float4*)(acc + at);
+        float w[4] = {w4.x, w4.y, w4.z, w4.w}, a[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) momentum_elem(w[i], a[i], picked(row, ks[i], ok[i]), lr, mom, wd, gs);
+        *(float4*)(acc + at) = make_float4(a[0], a[1], a[2], a[3]);
+        *(float4*)(W + at) = make_float4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// adam_kernel on the same thread map
+__global__ void __launch_bounds__(TPB) k_adam_cols(float* __restrict__ W, float* __restrict__ m, float* __restrict__ v,
+                                                   const float* __restrict__ dWs, const int32_t* __restrict__ inverse, int D, int C,
+                                                   int cpad, int S, int Spad, float lr_t, float b1, float b2, float eps, float wd,
+                                                   float gs) {
+    const int j4 = (blockIdx.x * TPB + threadIdx.x) * 4;
+    if (j4 >= cpad) return;
+    int ks[4];
+    bool ok[4];
+    cols_of(inverse, j4, C, S, ks, ok);
+    const int d0 = blockIdx.y * ROWS;
+#pragma unroll 2
+    for (int r = 0; r < ROWS; ++r) {
+        const int d = d0 + r;
+        if (d >= D) break;
+        const float* row = dWs + (size_t)d * Spad;
+        const size_t at = (size_t)d * cpad + j4;
+        const float4 w4 = *(const float4*)(W + at), m4 = *(const float4*)(m + at), v4 = *(const float4*)(v + at);
+        float w[4] = {w4.x, w4.y, w4.z, w4.w}, mo[4] = {m4.x, m4.y, m4.z, m4.w}, vo[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) adam_elem(w[i], mo[i], vo[i], picked(row, ks[i], ok[i]), lr_t, b1, b2, eps, wd, gs);
+        *(float4*)(m + at) = make_float4(mo[0], mo[1], mo[2], mo[3]);
+        *(float4*)(v + at) = make_float4(vo[0], vo[1], vo[2], vo[3]);
+        *(float4*)(W + at) = make_float4(w[0], w[1], w[2], w[3]);
+    }
+}
+
 }  // namespace
 
 size_t p_sample_ws_bytes(int C) { return flags_word(C) * 4 + ((size_t)C + 15) / 16 * 16 + 16; }
@@ -296,5 +399,19 @@ hipError_t p_gather_cols(const float* W, const int32_t* index, float* Ws, int D,
 hipError_t p_scatter_cols(const float* dWs, const int32_t* inverse, float* dW, int D, int C, int cpad, int S, int Spad, hipStream_t st) {
     dim3 grid((cpad / 4 + TPB - 1) / TPB, (D + ROWS - 1) / ROWS);
     k_scatter<<<grid, TPB, 0, st>>>(dWs, inverse, dW, D, C, cpad, S, Spad);
+    return hipGetLastError();
+}
+
+hipError_t p_momentum_update_cols(float* W, float* acc, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S, int Spad,
+                                  float lr, float mom, float wd, float gs, hipStream_t st) {
+    dim3 grid((cpad / 4 + TPB - 1) / TPB, (D + ROWS - 1) / ROWS);
+    k_momentum_cols<<<grid, TPB, 0, st>>>(W, acc, dWs, inverse, D, C, cpad, S, Spad, lr, mom, wd, gs);
+    return hipGetLastError();
+}
+
+hipError_t p_adam_update_cols(float* W, float* m, float* v, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S,
+                              int Spad, float lr_t, float b1, float b2, float eps, float wd, float gs, hipStream_t st) {
+    dim3 grid((cpad / 4 + TPB - 1) / TPB, (D + ROWS - 1) / ROWS);
+    k_adam_cols<<<grid, TPB, 0, st>>>(W, m, v, dWs, inverse, D, C, cpad, S, Spad, lr_t, b1, b2, eps, wd, gs);
     return hipGetLastError();
 }

@@ -136,6 +136,11 @@ class Singular(object):
             raise ValueError('labels must lie in [0, num_classes): got [%d, %d] with num_classes = %d'
                              % (lo, hi, int(inputs['num_classes'])))
 
+    def _compact(self):
+        """the sampled-class head's compact classifier update (nets/sphere.py apply_compact_update) is on for this model"""
+        active = getattr(self.model, 'compact_active', None)
+        return active is not None and active()
+
     def _lr_value(self):
         return float(self.lr(self.global_step)) if callable(self.lr) else float(self.lr)
 
@@ -193,6 +198,8 @@ class Singular(object):
             self.model.backward()
             self.learning_rate = self._lr_value()
             self._opt.apply(self.learning_rate, self.global_step + 1, self.model.mult_lr_list())
+            if self._compact():                       # model.compact_head_update: arena_groups() left the classifier out
+                self.model.apply_compact_update(self._opt, self.learning_rate, self.global_step + 1, self.model.mult_lr_list())
             self.global_step += 1                     # data_parallel.py:75-77
             state['losses'], state['others'] = losses, others
             return losses, others
@@ -208,12 +215,16 @@ class Singular(object):
 class DataParallel(Singular):
     """data_parallel.py:81-166: synchronous data parallelism, one replica per GPU."""
 
-    def __init__(self, model, lr, optimizer, num_gpus=4, weight_decay=5e-4, comm=None, sync_centers=False):
+    def __init__(self, model, lr, optimizer, num_gpus=4, weight_decay=5e-4, comm=None, sync_centers=False, sync_sample=False):
         """`sync_centers` (not in the reference; default off = the reference's behaviour): the center loss's `centers` table
         is per-tower state there (loss.py:34-39) and the towers' tables drift apart; True all-gathers every step's scatter rows
-        so that all replicas keep ONE table, equal to the single-tower update of the global batch (nets/graph.py)."""
+        so that all replicas keep ONE table, equal to the single-tower update of the global batch (nets/graph.py).
+        `sync_sample` (default off): a sampled-class head (sample_rate) under data parallelism.  The ranks all-gather their labels
+        and draw ONE class sample from the global batch, the compact [D, Spad] classifier gradient is all-reduced instead of the
+        dense one and goes straight into the classifier; without it such a net is refused.  No effect on a dense
+        head."""
         assert num_gpus > 1, 'DataParallel objects are only used for multi-gpu training tasks.'
-        if getattr(model, 'sample_rate', None) is not None:
+        if getattr(model, 'sample_rate', None) is not None and not sync_sample:
             # each rank sees other labels, so the ranks' samples would differ and the all-reduce would average gradients of
             # different column sets
             raise ValueError('a sampled-class head (sample_rate %g) runs on one GPU only: num_gpus = %d' % (model.sample_rate, num_gpus))
@@ -222,6 +233,7 @@ class DataParallel(Singular):
         self.pretrained_param = []
         self.comm = comm
         self.sync_centers = bool(sync_centers)
+        self.sync_sample = bool(sync_sample)
         self._global_batch = None
 
     def _shard(self, t):
@@ -244,10 +256,21 @@ class DataParallel(Singular):
         m = self.model
         works = []
         buckets = m.grad_buckets()
+        compact = None
         for stage, (a, b) in zip(m.backward_stages(), buckets):
             stage()
+            if self._compact() and compact is None:
+                # the sampled-class head with one shared sample: behind backward_head the classifier gradient is the compact
+                # [D, Spad] buffer, the same columns on every rank, so its sum is the dense sum (the zeros of the other columns add
+                # exactly); the head bucket is the FC range alone, and the four loss slots behind the arena, no longer next to it,
+                # get a 16-byte all-reduce of their own
+                compact = (self.comm.all_reduce_async(m.compact_grad()), self.comm.all_reduce_async(m.loss_slots))
             works.append(self.comm.all_reduce_async(m.grads[a:b]))
         self.learning_rate = self._lr_value()
+        if compact is not None:
+            compact[0].wait()
+            m.apply_compact_update(self._opt, self.learning_rate, self.global_step + 1, m.mult_lr_list())
+            compact[1].wait()
         if getattr(self._opt, 'supports_ranges', False):
             # bucket by bucket, in completion order: the head bucket (73 of the 120 MB) is updated while the later, smaller
             # all-reduces are still crossing xGMI -- the kernel stream only ever waits for the bucket it is about to update
@@ -267,6 +290,9 @@ class DataParallel(Singular):
         self._setup(inputs)
         if hasattr(self.model, 'center_comm'):
             self.model.center_comm = self.comm if self.sync_centers else None
+        if self.sync_sample and getattr(self.model, 'sample_rate', None) is not None:
+            self.model.sample_comm = self.comm
+            self.model.compact_head_update = True
         num_classes = inputs['num_classes']
         self._global_batch = inputs.get('batch_size')
         scope = 'TOWER_%d' % self.comm.rank()

@@ -780,6 +780,9 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         super(SphereNetAdditiveMargin, self).__init__(weight_decay, data_format, name, seed)
         self.margin_scale, self.margin, self.margin_cos = margin_params(head, scale, margin, margin_cos)
         self.head = head
+        # the sampled-class head under data parallelism and its compact classifier update; the dense head ignores both
+        self.sample_comm = None           # set by DataParallel(sync_sample=True): the ranks all-gather their labels, one sample for all
+        self.compact_head_update = False  # True: no dense classifier gradient; the wrapper ends the step with apply_compact_update
         self.set_sample_rate(sample_rate, sample_seed)
 
     def _margin_head(self, labels, n, st):
@@ -825,9 +828,14 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         self._ensure_built(images, num_classes)
         n = images.shape[0]
         S = self.sample_size
-        if S < n:
-            raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows'
-                             % (S, self.sample_rate, self.num_classes, n))
+        comm = self.sample_comm
+        world = 1 if comm is None else comm.world_size()
+        if S < world * n:
+            if comm is None:
+                raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows'
+                                 % (S, self.sample_rate, self.num_classes, n))
+            raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows (the global batch: '
+                             '%d ranks of %d rows)' % (S, self.sample_rate, self.num_classes, world * n, world, n))
         labels = self._check_labels(labels)
         self._labels = labels
         st = _stream()
@@ -835,8 +843,21 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         self.backbone(images, is_training=True)
         spad = self._head_width()
         wc = self.view('classifier/fc_classifier/weights')
-        call('fte_pfc_sample', labels, n, self.num_classes, S, self.sample_seed & 0xffffffff, int(self.global_step) & 0xffffffff,
-             self.class_index, self.class_inverse, self.sampled_labels, self.pfc_ws, self.pfc_ws.numel() * 4, st)
+        if comm is None:
+            every, mine = labels, self.sampled_labels
+        else:
+            # one sample for all ranks: the labels of the global batch, in rank order, through the unchanged sampler; a rank's own
+            # remapped labels are its rows of the result
+            if getattr(self, '_all_labels', None) is None or self._all_labels.numel() != world * n:
+                self._all_labels = torch.empty(world * n, dtype=torch.int32, device=self.device)
+                self._all_sampled = torch.empty(world * n, dtype=torch.int32, device=self.device)
+            comm.all_gather(self._all_labels, labels)
+            every, mine = self._all_labels, self._all_sampled
+        call('fte_pfc_sample', every, world * n, self.num_classes, S, self.sample_seed & 0xffffffff, int(self.global_step) & 0xffffffff,
+             self.class_index, self.class_inverse, mine, self.pfc_ws, self.pfc_ws.numel() * 4, st)
+        if comm is not None:
+            r = comm.rank()
+            self.sampled_labels = mine[r * n:(r + 1) * n]
         call('fte_pfc_gather_cols', wc, self.class_index, self.Ws, EMBED, self.num_classes, self.cpad, S, spad, st)
         call('fte_gemm_nn', self.emb, self.Ws, None, self.s_raw, n, spad, EMBED, self.ws, self.ws_bytes, st)
         call('fte_row_norms', self.emb, self.xn, n, EMBED, EMBED, st)
@@ -854,9 +875,52 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         gwc = self.view('classifier/fc_classifier/weights', self.grads)
         call('fte_gemm_tn', self.emb, self.G, self.dWs, n, spad, EMBED, self.ws, self.ws_bytes, st)
         call('fte_add_scaled_rows_cols', self.dWs, self.Ws, None, self.colcoef, EMBED, spad, spad, st)
-        call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, gwc, EMBED, self.num_classes, self.cpad, S, spad, st)
+        if not self.compact_head_update:
+            call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, gwc, EMBED, self.num_classes, self.cpad, S, spad, st)
+        # else: the classifier range of `grads` is NOT written (it holds whatever an earlier step or mode left there); the gradient is
+        # compact_grad(), and apply_compact_update takes it into the classifier
         call('fte_gemm_nt', self.G, self.Ws, None, None, 0, None, self.demb, None, n, spad, EMBED, self.ws, self.ws_bytes, st)
         call('fte_add_scaled_rows_cols', self.demb, self.emb, self.rowcoef, None, n, EMBED, EMBED, st)
+
+    # ---- the compact classifier update (fte.h fte_pfc_momentum_update_cols / fte_pfc_adam_update_cols) -------------------------------
+    def compact_active(self):
+        """True when the step ends with apply_compact_update instead of a dense classifier gradient: the sampled head, switched on"""
+        return self.sample_rate is not None and bool(self.compact_head_update)
+
+    def compact_grad(self):
+        """The [D, Spad] gradient of the sampled classifier columns, as backward_head leaves it (columns in class_index order).  Under
+        data parallelism every rank holds the same columns (one shared sample), so its sum over the ranks is the dense gradient's sum:
+        this buffer is what crosses the wire."""
+        return self.dWs
+
+    def arena_groups(self):
+        groups = super(SphereNetAdditiveMargin, self).arena_groups()
+        return groups[:-1] if self.compact_active() else groups      # the classifier is updated by apply_compact_update
+
+    def grad_buckets(self):
+        buckets = super(SphereNetAdditiveMargin, self).grad_buckets()
+        if self.compact_active():
+            # the head bucket shrinks to the FC range: the classifier gradient travels as compact_grad(), the four loss slots behind the
+            # arena in an all-reduce of their own (data_parallel.py)
+            buckets[0] = (self.fc_start, self.cls_start)
+        return buckets
+
+    def apply_compact_update(self, opt, lr, step_1based, mult_lr_list):
+        """The classifier's share of _DeviceOptimizer.apply -- group 1 of the dense arena_groups(), with the same lr, wd * gs, gs and t
+        and the optimizer's own slots for the range -- taken straight from compact_grad(): the same bytes as the scatter followed by the
+        dense update, without the dense gradient."""
+        opt._ensure()
+        a, b = self.cls_start, self.arena_size
+        gs = float(mult_lr_list[1])
+        wd = self.weight_decay
+        S, spad = self.sample_size, self._head_width()
+        shape = (EMBED, self.num_classes, self.cpad, S, spad)
+        if opt.kind == 'Momentum':
+            _lib.call('fte_pfc_momentum_update_cols', self.params[a:b], opt.slots[0][a:b], self.dWs, self.class_inverse, *shape,
+                      float(lr), 0.9, wd * gs, gs, _stream())
+        else:
+            _lib.call('fte_pfc_adam_update_cols', self.params[a:b], opt.slots[0][a:b], opt.slots[1][a:b], self.dWs, self.class_inverse,
+                      *shape, float(lr), 0.5, 0.999, 1e-8, wd * gs, gs, int(step_1based), _stream())
 
     def _others(self):
         return OrderedDict()

@@ -69,10 +69,18 @@ def build_parser():
                             help='additive-margin nets (SphereNet-ArcFace / -CosFace / -AdaFace, ResNet-50-arcface / -cosface / -adaface) only: the %s; '
                                  "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35; AdaFace S = 64, m = 0.4)" % what)
     parser.add_argument('--sample_rate', type=float, default=1.0,
-                        help='SphereNet-ArcFace / SphereNet-CosFace on one GPU only: the fraction of the classes the margin head runs over per '
+                        help='SphereNet-ArcFace / SphereNet-CosFace (one GPU; --num_gpus > 1 with --sync_sample 1): the fraction of the classes the margin head runs over per '
                              "step (Partial FC: the batch's own classes plus a seeded random sample of the others; 0.1 is the usual value). "
                              'A float in (0, 1]; 1 (default) = the dense head.')
     parser.add_argument('--sample_seed', type=int, default=0, help='seed of the per-step class sample of --sample_rate.')
+    parser.add_argument('--sync_sample', type=int, default=0,
+                        help='--sample_rate < 1 under --num_gpus > 1 (refused without it): 1 = the ranks all-gather their labels and draw ONE '
+                             'class sample per step from the global batch; the compact gradient of the sampled classifier columns is '
+                             'all-reduced instead of the dense one.  Implies --compact_head_update 1.')
+    parser.add_argument('--compact_head_update', type=int, default=0,
+                        help='--sample_rate < 1: 1 = the classifier and its optimizer slots are updated straight from the compact gradient '
+                             'of the sampled columns (one fused kernel, the same values bit for bit); the dense classifier gradient is '
+                             'never written.')
     return parser
 
 
@@ -86,7 +94,7 @@ def sample_flags_check(FLAGS):
     if FLAGS.sample_rate < 1.0 and FLAGS.net_name not in SAMPLED_NETS:
         raise SystemExit('--sample_rate %g: only %s have a sampled-class head, not %s'
                          % (FLAGS.sample_rate, ' / '.join(SAMPLED_NETS), FLAGS.net_name))
-    if FLAGS.sample_rate < 1.0 and FLAGS.num_gpus > 1:
+    if FLAGS.sample_rate < 1.0 and FLAGS.num_gpus > 1 and not getattr(FLAGS, 'sync_sample', 0):
         raise SystemExit('--sample_rate %g: the sampled-class head runs on one GPU only (--num_gpus %d)' % (FLAGS.sample_rate, FLAGS.num_gpus))
 
 
@@ -205,13 +213,19 @@ def train(FLAGS):
         lr = lr_config(FLAGS, FLAGS.lr_decay_method, batches_per_epoch)                              # train.py:176
         if FLAGS.num_gpus > 1:                                                                        # train.py:178-183
             model = DataParallel_margin(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay, num_gpus=FLAGS.num_gpus,
-                                        sync_centers=bool(FLAGS.sync_centers))
+                                        sync_centers=bool(FLAGS.sync_centers), sync_sample=bool(FLAGS.sync_sample))
         else:
             model = Singular(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay)
+        compact = FLAGS.sample_rate < 1.0 and bool(FLAGS.compact_head_update or (FLAGS.sync_sample and FLAGS.num_gpus > 1))
+        if compact:
+            network.compact_head_update = True
         train_ops, losses, losses_name, others = model(inputs)
         if FLAGS.sample_rate < 1.0:
             print('Sampled-class head: sample_rate = %g, sample_seed = %d, S = %d of %d classes per step'
                   % (FLAGS.sample_rate, FLAGS.sample_seed, network.sample_size, network.num_classes))
+            if compact:
+                print('Sampled-class head mode: %s, compact classifier update (no dense classifier gradient)'
+                      % ('one shared sample over %d ranks' % FLAGS.num_gpus if FLAGS.num_gpus > 1 else 'one GPU'))
 
         tag = FLAGS.net_name + '_' + FLAGS.model_name
         ckpt_dir = os.path.join(FLAGS.model_dir, tag)
