@@ -5,10 +5,11 @@ produced for that term); the graph nets wire them as heads (nets/graph.py), a ca
 
 All tensors are float32 / int32 CUDA tensors; logits may carry padding columns (ld = logits.shape[1] >= num_classes)."""
 import math
+from types import SimpleNamespace
 
 import torch
 
-from . import _lib
+from . import _lib, heads
 
 
 def _stream():
@@ -73,6 +74,38 @@ def batch_hard_triplet_loss(features, labels, margin=None, metric='euclidean'):
     return rows, df
 
 
+def _head_args(features, weights, labels, num_classes):
+    """the checked arguments of a margin head and its sizes -> (features, weights, labels, n, d, ld, c)"""
+    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
+    weights = _check(weights, torch.float32, 'weights')
+    n, d = features.shape
+    ld = weights.shape[1]
+    if weights.shape[0] != d or labels.shape != (n,):
+        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
+                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
+    return features, weights, labels, n, d, ld, ld if num_classes is None else int(num_classes)
+
+
+def _head_scratch(features, n, d, ld, ws_bytes=0, **more):
+    """workspace, stream and the scratch buffers of one head call over ld columns, under the names heads.py reads"""
+    f32 = dict(dtype=torch.float32, device=features.device)
+    ws = torch.empty(max(_lib.query('fte_gemm_ws_bytes', n, ld, d), ws_bytes, 4096) // 4 + 1024, **f32)
+    return SimpleNamespace(st=_stream(), ws=ws, wsb=ws.numel() * 4, s=torch.empty(n, ld, **f32), G=torch.empty(n, ld, **f32),
+                           xn=torch.empty(n, **f32), rowcoef=torch.empty(n, **f32), loss_rows=torch.empty(n, **f32),
+                           wn=torch.empty(ld, **f32), colcoef=torch.empty(ld, **f32), dx=torch.empty_like(features), **more)
+
+
+def _head_run(b, features, W, dW, labels, head, n, d, c, ld, after_dw=None):
+    """the head `head` (heads.margin_forward) on the columns W [d, ld] and both classifier gradients -> (mean loss, dfeatures)"""
+    _lib.call('fte_gemm_nn', features, W, None, b.s, n, ld, d, b.ws, b.wsb, b.st)
+    heads.margin_forward(b, features, W, b.s, labels, None, head, n, d, c, ld, 1.0 / n, b.st)
+    heads.classifier_dw(b, features, W, dW, n, d, ld, b.ws, b.wsb, b.st)
+    if after_dw is not None:
+        after_dw()
+    heads.classifier_dx(b, features, W, b.dx, n, d, ld, b.ws, b.wsb, b.st)
+    return _scaled_sum(b.loss_rows, 1.0 / n), b.dx
+
+
 def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, margin_cos=0.0, num_classes=None):
     """Additive-margin softmax on the normalised features and weight columns: ArcFace (angular margin `margin`, cos(theta + m))
     and CosFace (cosine margin `margin_cos`, cos(theta) - m3), scale S = `scale`; the contract is fte.h's
@@ -81,37 +114,10 @@ def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, marg
     D % 64 == 0 and ld % 64 == 0 (the classifier products' tiling: pad with zero columns).
     -> (loss [0-d] = mean over the rows, dfeatures [N, D], dweights [D, ld]): the exact gradient of the mean through both
     normalisations; padding columns get 0."""
-    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
-    weights = _check(weights, torch.float32, 'weights')
-    n, d = features.shape
-    ld = weights.shape[1]
-    if weights.shape[0] != d or labels.shape != (n,):
-        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
-                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
-    c = ld if num_classes is None else int(num_classes)
-    st = _stream()
-    dev = features.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    wsb = max(_lib.query('fte_gemm_ws_bytes', n, ld, d), 4096)
-    ws = torch.empty(wsb // 4 + 1024, **f32)
-    wsb = ws.numel() * 4
-    s = torch.empty(n, ld, **f32)
-    xn, rowcoef, rows = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
-    wn, colcoef = torch.empty(ld, **f32), torch.empty(ld, **f32)
-    G = torch.empty(n, ld, **f32)
-    dx, dw = torch.empty_like(features), torch.empty_like(weights)
-    call = _lib.call
-    call('fte_gemm_nn', features, weights, None, s, n, ld, d, ws, wsb, st)
-    call('fte_row_norms', features, xn, n, d, d, st)
-    call('fte_col_norms', weights, wn, d, c, ld, st)
-    call('fte_margin_softmax_fwd_bwd', s, xn, wn, labels, float(scale), float(margin), float(margin_cos), None, rows, G, rowcoef,
-         n, c, ld, 1.0 / n, st)
-    call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, c, ld, st)
-    call('fte_gemm_tn', features, G, dw, n, ld, d, ws, wsb, st)
-    call('fte_add_scaled_rows_cols', dw, weights, None, colcoef, d, ld, ld, st)
-    call('fte_gemm_nt', G, weights, None, None, 0, None, dx, None, n, ld, d, ws, wsb, st)
-    call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
-    return _scaled_sum(rows, 1.0 / n), dx, dw
+    features, weights, labels, n, d, ld, c = _head_args(features, weights, labels, num_classes)
+    dw = torch.empty_like(weights)
+    head = ('arcface', float(scale), float(margin), float(margin_cos))
+    return _head_run(_head_scratch(features, n, d, ld), features, weights, dw, labels, head, n, d, c, ld) + (dw,)
 
 
 def adaface_loss(features, weights, labels, stats, scale=64.0, margin=0.4, h=0.333, t_alpha=0.01, update=True, num_classes=None):
@@ -120,40 +126,14 @@ def adaface_loss(features, weights, labels, stats, scale=64.0, margin=0.4, h=0.3
     float32 CUDA tensor [mean, std] (the paper's code starts it at [20, 100]); with `update` it is moved in place by the batch's
     statistics (weight t_alpha), otherwise left alone -- the margins use the blended values either way.  The other arguments, the
     shapes and the result (loss, dfeatures, dweights) are additive_margin_loss's; the norm enters the margins as a constant."""
-    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
-    weights = _check(weights, torch.float32, 'weights')
     if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2):
         raise TypeError('stats must be a contiguous float32 CUDA tensor of 2 elements [mean, std]')
-    n, d = features.shape
-    ld = weights.shape[1]
-    if weights.shape[0] != d or labels.shape != (n,):
-        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
-                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
-    c = ld if num_classes is None else int(num_classes)
-    st = _stream()
-    dev = features.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    wsb = max(_lib.query('fte_gemm_ws_bytes', n, ld, d), 4096)
-    ws = torch.empty(wsb // 4 + 1024, **f32)
-    wsb = ws.numel() * 4
-    s = torch.empty(n, ld, **f32)
-    xn, rowcoef, rows = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
-    a_rows, b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
-    wn, colcoef = torch.empty(ld, **f32), torch.empty(ld, **f32)
-    G = torch.empty(n, ld, **f32)
-    dx, dw = torch.empty_like(features), torch.empty_like(weights)
-    call = _lib.call
-    call('fte_gemm_nn', features, weights, None, s, n, ld, d, ws, wsb, st)
-    call('fte_row_norms', features, xn, n, d, d, st)
-    call('fte_adaface_margins', xn, n, float(margin), float(h), float(t_alpha), int(bool(update)), stats, a_rows, b_rows, st)
-    call('fte_col_norms', weights, wn, d, c, ld, st)
-    call('fte_margin_softmax_rows_fwd_bwd', s, xn, wn, labels, float(scale), a_rows, b_rows, None, rows, G, rowcoef, n, c, ld, 1.0 / n, st)
-    call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, c, ld, st)
-    call('fte_gemm_tn', features, G, dw, n, ld, d, ws, wsb, st)
-    call('fte_add_scaled_rows_cols', dw, weights, None, colcoef, d, ld, ld, st)
-    call('fte_gemm_nt', G, weights, None, None, 0, None, dx, None, n, ld, d, ws, wsb, st)
-    call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
-    return _scaled_sum(rows, 1.0 / n), dx, dw
+    features, weights, labels, n, d, ld, c = _head_args(features, weights, labels, num_classes)
+    rows = dict(dtype=torch.float32, device=features.device)
+    b = _head_scratch(features, n, d, ld, adaface_stats=stats, a_rows=torch.empty(n, **rows), b_rows=torch.empty(n, **rows))
+    dw = torch.empty_like(weights)
+    head = ('adaface', float(scale), float(margin), float(h), float(t_alpha), int(bool(update)))
+    return _head_run(b, features, weights, dw, labels, head, n, d, c, ld) + (dw,)
 
 
 def sample_size(num_classes, sample_rate):
@@ -180,39 +160,15 @@ def partial_fc_margin_loss(features, weights, labels, sample_rate, seed, step, s
     if S >= c:
         loss, dx, dw = additive_margin_loss(features, weights, labels, scale, margin, margin_cos, num_classes)
         return loss, dx, dw, torch.arange(c, dtype=torch.int32, device=weights.device)
-    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
-    weights = _check(weights, torch.float32, 'weights')
-    n, d = features.shape
-    if weights.shape[0] != d or labels.shape != (n,):
-        raise ValueError('features [N, D], weights [D, ld] and labels [N] do not fit: %s %s %s'
-                         % (tuple(features.shape), tuple(weights.shape), tuple(labels.shape)))
+    features, weights, labels, n, d, ld, c = _head_args(features, weights, labels, num_classes)
     if S < n:
         raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows' % (S, sample_rate, c, n))
     spad = (S + 63) // 64 * 64
-    st = _stream()
-    dev = features.device
-    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-    wsb = max(_lib.query('fte_gemm_ws_bytes', n, spad, d), _lib.query('fte_pfc_sample_ws_bytes', c), 4096)
-    ws = torch.empty(wsb // 4 + 1024, **f32)
-    wsb = ws.numel() * 4
-    index, inverse, ys = torch.empty(spad, **i32), torch.empty(c, **i32), torch.empty(n, **i32)
-    Ws, dWs = torch.empty(d, spad, **f32), torch.empty(d, spad, **f32)
-    s, G = torch.empty(n, spad, **f32), torch.empty(n, spad, **f32)
-    xn, rowcoef, rows = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
-    wn, colcoef = torch.empty(spad, **f32), torch.empty(spad, **f32)
-    dx, dw = torch.empty_like(features), torch.empty_like(weights)
-    call = _lib.call
-    call('fte_pfc_sample', labels, n, c, S, int(seed) & 0xffffffff, int(step) & 0xffffffff, index, inverse, ys, ws, wsb, st)
-    call('fte_pfc_gather_cols', weights, index, Ws, d, c, ld, S, spad, st)
-    call('fte_gemm_nn', features, Ws, None, s, n, spad, d, ws, wsb, st)
-    call('fte_row_norms', features, xn, n, d, d, st)
-    call('fte_col_norms', Ws, wn, d, S, spad, st)
-    call('fte_margin_softmax_fwd_bwd', s, xn, wn, ys, float(scale), float(margin), float(margin_cos), None, rows, G, rowcoef,
-         n, S, spad, 1.0 / n, st)
-    call('fte_asoftmax_colcoef', G, s, wn, colcoef, n, S, spad, st)
-    call('fte_gemm_tn', features, G, dWs, n, spad, d, ws, wsb, st)
-    call('fte_add_scaled_rows_cols', dWs, Ws, None, colcoef, d, spad, spad, st)
-    call('fte_pfc_scatter_cols', dWs, inverse, dw, d, c, ld, S, spad, st)
-    call('fte_gemm_nt', G, Ws, None, None, 0, None, dx, None, n, spad, d, ws, wsb, st)
-    call('fte_add_scaled_rows_cols', dx, features, rowcoef, None, n, d, d, st)
-    return _scaled_sum(rows, 1.0 / n), dx, dw, index[:S]
+    f32, i32 = dict(dtype=torch.float32, device=features.device), dict(dtype=torch.int32, device=features.device)
+    b = _head_scratch(features, n, d, spad, _lib.query('fte_pfc_sample_ws_bytes', c), class_index=torch.empty(spad, **i32),
+                      class_inverse=torch.empty(c, **i32), sampled_labels=torch.empty(n, **i32), Ws=torch.empty(d, spad, **f32))
+    dWs, dw = torch.empty(d, spad, **f32), torch.empty_like(weights)
+    heads.sample_classes(b, labels, weights, n, d, c, ld, S, spad, seed, step, b.ws, b.wsb, b.st)
+    loss, dx = _head_run(b, features, b.Ws, dWs, b.sampled_labels, ('arcface', float(scale), float(margin), float(margin_cos)), n, d, S, spad,
+                         lambda: _lib.call('fte_pfc_scatter_cols', dWs, b.class_inverse, dw, d, c, ld, S, spad, b.st))
+    return loss, dx, dw, b.class_index[:S]

@@ -12,7 +12,7 @@ from collections import OrderedDict
 
 import torch
 
-from .. import _lib
+from .. import _lib, heads
 from .net_base import MARGIN_PRESETS, NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
 from .sphere import Variable, same_pads
 
@@ -1162,9 +1162,7 @@ class GraphNet(Network):
     def loss_function(self, scope, labels, **logits):
         """nets/resnet.py:163-176 + Network._regularize; the center / triplet terms are loss.py's functions wired to
         the pooled features (the reference leaves that wiring to the caller)."""
-        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32):
-            raise TypeError('labels must be an int32 CUDA tensor (data.py:259)')
-        labels = labels.contiguous()
+        labels = heads.check_labels(labels)
         n = labels.shape[0]
         st = _stream()
         call = _lib.call
@@ -1185,21 +1183,9 @@ class GraphNet(Network):
                 call('fte_focal_loss_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.focal_gamma, self.focal_alpha, self.tower_scale / n, st)
             elif self.head in NORMALISED_HEADS:              # the margin on the raw classifier output; backward_head adds the norm terms
-                op = self.plan[-1]
-                k = self.shapes[op[2]][0]
-                call('fte_row_norms', self.t[op[2]], self.xn, n, k, k, st)
-                call('fte_col_norms', self.view(op[3]), self.wn, k, self.num_classes, self.cpad, st)
-                if self.head == 'adaface':                   # per-row margins from the norms; the running statistics move with BN's
-                    call('fte_adaface_margins', self.xn, n, self.margin, self.adaface_h, self.adaface_t_alpha,
-                         int(self.update_moving_stats), self.adaface_stats, self.a_rows, self.b_rows, st)
-                    call('fte_margin_softmax_rows_fwd_bwd', self.t['logits'], self.xn, self.wn, labels, self.margin_scale, self.a_rows,
-                         self.b_rows, None, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
-                         self.tower_scale / n, st)
-                else:
-                    call('fte_margin_softmax_fwd_bwd', self.t['logits'], self.xn, self.wn, labels, self.margin_scale, self.margin,
-                         self.margin_cos, None, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
-                         self.tower_scale / n, st)
-                call('fte_asoftmax_colcoef', self.G, self.t['logits'], self.wn, self.colcoef, n, self.num_classes, self.cpad, st)
+                op = self.plan[-1]                           # (the running statistics of AdaFace move with BN's: heads.describe)
+                heads.margin_forward(self, self.t[op[2]], self.view(op[3]), self.t['logits'], labels, None, heads.describe(self), n,
+                                     self.shapes[op[2]][0], self.num_classes, self.cpad, self.tower_scale / n, st)
             else:
                 call('fte_softmax_ce_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.tower_scale / n, st)
@@ -1303,20 +1289,15 @@ class GraphNet(Network):
         self._grad = {}
         gin = torch.empty(n, k, dtype=torch.float32, device=self.device)
         side = self.side if os.environ.get('FTE_HEAD_SIDE', '1') != '0' else None
-        margin = self.head in NORMALISED_HEADS
-        gw = self.view(op[3], self.grads)
+        norm = self.head in NORMALISED_HEADS             # their norm corrections ride on the stream of the product they correct
+        x, W = self.t[op[2]], self.view(op[3])
+        wst, wws = st, self.ws
         if side is not None:
             main = torch.cuda.current_stream()
             side.wait_event(main.record_event())         # G (the loss head's gradient) and the features are complete
-            _lib.call('fte_gemm_tn', self.t[op[2]], self.G, gw, n, self.cpad, k, self.ws_side, self.ws_bytes, side.cuda_stream)
-        else:
-            _lib.call('fte_gemm_tn', self.t[op[2]], self.G, gw, n, self.cpad, k, self.ws, self.ws_bytes, st)
-        if margin:                                       # dW += colcoef (.) W, on the stream of the product, before the bucket is reduced
-            _lib.call('fte_add_scaled_rows_cols', gw, self.view(op[3]), None, self.colcoef, k, self.cpad, self.cpad,
-                      side.cuda_stream if side is not None else st)
-        _lib.call('fte_gemm_nt', self.G, self.view(op[3]), None, None, 0, None, gin, None, n, self.cpad, k, self.ws, self.ws_bytes, st)
-        if margin:                                       # dx += rowcoef (.) x
-            _lib.call('fte_add_scaled_rows_cols', gin, self.t[op[2]], self.rowcoef, None, n, k, k, st)
+            wst, wws = side.cuda_stream, self.ws_side
+        heads.classifier_dw(self, x, W, self.view(op[3], self.grads), n, k, self.cpad, wws, self.ws_bytes, wst, norm)      # (before the bucket is reduced)
+        heads.classifier_dx(self, x, W, gin, n, k, self.cpad, self.ws, self.ws_bytes, st, norm)
         if side is not None and join:
             torch.cuda.current_stream().wait_stream(side)
         self._grad[op[2]] = gin

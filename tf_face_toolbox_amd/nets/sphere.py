@@ -22,7 +22,7 @@ from collections import OrderedDict
 
 import torch
 
-from .. import _lib
+from .. import _lib, heads
 from ..loss import sample_size
 from .net_base import NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
 
@@ -426,9 +426,14 @@ class SphereNet(Network):
              self.view(self.name + '/fully_connected/biases'), self.emb, n, EMBED, self.fin, self.ws, self.ws_bytes, st)
         return self.emb
 
+    def _head_cols(self):
+        """(W, dW, live columns, leading dimension) of the classifier columns the head runs on: here all of them, in the arenas"""
+        cls = 'classifier/fc_classifier/weights'
+        return self.view(cls), self.view(cls, self.grads), self.num_classes, self.cpad
+
     def _classifier_raw(self, n):
-        _lib.call('fte_gemm_nn', self.emb, self.view('classifier/fc_classifier/weights'), None, self.s_raw,
-                  n, self.cpad, EMBED, self.ws, self.ws_bytes, _stream())
+        W, _, _, ld = self._head_cols()
+        _lib.call('fte_gemm_nn', self.emb, W, None, self.s_raw, n, ld, EMBED, self.ws, self.ws_bytes, _stream())
 
     def _ensure_built(self, images, num_classes):
         if not self.built:
@@ -481,26 +486,24 @@ class SphereNet(Network):
         Returns ([cross_entropy, reg_loss], names, others): the losses are 0-d device tensors
         (views of the loss slots that ride on the gradient arena); read them after the step."""
         n = labels.shape[0]
-        labels = self._check_labels(labels)
+        labels = heads.check_labels(labels)
         self._labels = labels
         _lib.call('fte_softmax_ce_fwd_bwd', self.s_raw, labels, self.loss_rows, self.G, n, self.num_classes, self.cpad,
                   self._grad_scale(n), _stream())
         self._finish_losses(n)
         return [self.loss_slots[0], self.loss_slots[1]], ['cross_entropy', 'reg_loss'], OrderedDict()
 
-    @staticmethod
-    def _check_labels(labels):
-        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32):
-            raise TypeError('labels must be an int32 CUDA tensor (data.py:259)')
-        return labels.contiguous()
-
     # ------------------------------------------------------------------ backward (replaces tf.gradients)
     def _head_backward(self, n, st):
-        call = _lib.call
-        wc = self.view('classifier/fc_classifier/weights')
-        gwc = self.view('classifier/fc_classifier/weights', self.grads)
-        call('fte_gemm_tn', self.emb, self.G, gwc, n, self.cpad, EMBED, self.ws, self.ws_bytes, st)
-        call('fte_gemm_nt', self.G, wc, None, None, 0, None, self.demb, None, n, self.cpad, EMBED, self.ws, self.ws_bytes, st)
+        """the classifier's two products on the columns of _head_cols; the margin heads add the norm corrections (heads.py)"""
+        W, dW, _, ld = self._head_cols()
+        norm = self.head != 'softmax'
+        heads.classifier_dw(self, self.emb, W, dW, n, EMBED, ld, self.ws, self.ws_bytes, st, norm)
+        self._scatter_dw(st)
+        heads.classifier_dx(self, self.emb, W, self.demb, n, EMBED, ld, self.ws, self.ws_bytes, st, norm)
+
+    def _scatter_dw(self, st):
+        """what a head on a subset of the columns does with its dW before the input side runs; nothing for all columns"""
 
     def backward_head(self):
         """Classifier + FC gradients: the first (and largest) all-reduce bucket."""
@@ -725,29 +728,36 @@ class SphereNetMargin(SphereNet):
         return max(self.lambda_min, self.lambda_base * (1.0 + self.gamma * self.global_step) ** (-self.power))
 
     def forward(self, images, labels=None, num_classes=None, is_training=True):
+        """backbone, then the head on the columns of _head_cols (heads.margin_forward); a sampled-class head picks them first"""
         if not is_training:
             return self._eval_features(images)
         assert num_classes is not None, 'num_classes must be given when is_training=True'
         assert labels is not None, 'margin nets take labels in forward (data_parallel.py:220)'
         self._ensure_built(images, num_classes)
         n = images.shape[0]
-        labels = self._check_labels(labels)
+        self._check_sample(n)
+        labels = heads.check_labels(labels)
         self._labels = labels
         st = _stream()
         self.backbone(images, is_training=True)
+        labels, extra = self._sample_classes(labels, n, st)
         self._classifier_raw(n)
-        wc = self.view('classifier/fc_classifier/weights')
-        _lib.call('fte_row_norms', self.emb, self.xn, n, EMBED, EMBED, st)
-        _lib.call('fte_col_norms', wc, self.wn, EMBED, self.num_classes, self.cpad, st)
-        self._margin_head(labels, n, st)
-        _lib.call('fte_asoftmax_colcoef', self.G, self.s_raw, self.wn, self.colcoef, n, self.num_classes, self.cpad, st)
-        return {'logits': self.logits_buf[:, :self.num_classes]}
+        W, _, c, ld = self._head_cols()
+        heads.margin_forward(self, self.emb, W, self.s_raw, labels, self.logits_buf, self._head_spec(), n, EMBED, c, ld,
+                             self._grad_scale(n), st)
+        return dict({'logits': self.logits_buf[:, :c]}, **extra)
 
-    def _margin_head(self, labels, n, st):
-        """margin logits, loss rows, G = dLoss/ds and rowcoef from s_raw and the norms"""
+    def _check_sample(self, n):
+        """a sampled-class head refuses a batch its sample cannot hold"""
+
+    def _sample_classes(self, labels, n, st):
+        """-> (the labels the head sees, further entries of forward's result); a sampled-class head draws its columns here"""
+        return labels, {}
+
+    def _head_spec(self):
+        """the head description of heads.margin_forward"""
         self.lam = self.current_lambda()
-        _lib.call('fte_asoftmax_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.lam, self.logits_buf, self.loss_rows,
-                  self.G, self.rowcoef, n, self.num_classes, self.cpad, self._grad_scale(n), st)
+        return ('asoftmax', self.lam)
 
     def _others(self):
         others = OrderedDict()
@@ -758,13 +768,6 @@ class SphereNetMargin(SphereNet):
         n = labels.shape[0]
         self._finish_losses(n)
         return [self.loss_slots[0], self.loss_slots[1]], ['cross_entropy', 'reg_loss'], self._others()
-
-    def _head_backward(self, n, st):
-        super(SphereNetMargin, self)._head_backward(n, st)
-        wc = self.view('classifier/fc_classifier/weights')
-        gwc = self.view('classifier/fc_classifier/weights', self.grads)
-        _lib.call('fte_add_scaled_rows_cols', gwc, wc, None, self.colcoef, EMBED, self.cpad, self.cpad, st)
-        _lib.call('fte_add_scaled_rows_cols', self.demb, self.emb, self.rowcoef, None, n, EMBED, EMBED, st)
 
 
 class SphereNetAdditiveMargin(SphereNetMargin):
@@ -785,10 +788,8 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         self.compact_head_update = False  # True: no dense classifier gradient; the wrapper ends the step with apply_compact_update
         self.set_sample_rate(sample_rate, sample_seed)
 
-    def _margin_head(self, labels, n, st):
-        _lib.call('fte_margin_softmax_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.margin_scale, self.margin,
-                  self.margin_cos, self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad,
-                  self._grad_scale(n), st)
+    def _head_spec(self):
+        return heads.describe(self)
 
     # ---- the sampled-class head (Partial FC; fte.h "Partial FC") -----------------------------------------------
     def set_sample_rate(self, rate, seed=0):
@@ -820,13 +821,9 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         self.dWs = torch.empty(EMBED, spad, **f32)
         self.pfc_ws = torch.empty(_lib.query('fte_pfc_sample_ws_bytes', self.num_classes) // 4 + 16, **f32)
 
-    def forward(self, images, labels=None, num_classes=None, is_training=True):
-        if not is_training or self.sample_rate is None:
-            return super(SphereNetAdditiveMargin, self).forward(images, labels, num_classes=num_classes, is_training=is_training)
-        assert num_classes is not None, 'num_classes must be given when is_training=True'
-        assert labels is not None, 'margin nets take labels in forward (data_parallel.py:220)'
-        self._ensure_built(images, num_classes)
-        n = images.shape[0]
+    def _check_sample(self, n):
+        if self.sample_rate is None:
+            return
         S = self.sample_size
         comm = self.sample_comm
         world = 1 if comm is None else comm.world_size()
@@ -836,51 +833,28 @@ class SphereNetAdditiveMargin(SphereNetMargin):
                                  % (S, self.sample_rate, self.num_classes, n))
             raise ValueError('the sample of %d classes (sample_rate %g of %d) is smaller than the batch of %d rows (the global batch: '
                              '%d ranks of %d rows)' % (S, self.sample_rate, self.num_classes, world * n, world, n))
-        labels = self._check_labels(labels)
-        self._labels = labels
-        st = _stream()
-        call = _lib.call
-        self.backbone(images, is_training=True)
-        spad = self._head_width()
-        wc = self.view('classifier/fc_classifier/weights')
-        if comm is None:
-            every, mine = labels, self.sampled_labels
-        else:
-            # one sample for all ranks: the labels of the global batch, in rank order, through the unchanged sampler; a rank's own
-            # remapped labels are its rows of the result
-            if getattr(self, '_all_labels', None) is None or self._all_labels.numel() != world * n:
-                self._all_labels = torch.empty(world * n, dtype=torch.int32, device=self.device)
-                self._all_sampled = torch.empty(world * n, dtype=torch.int32, device=self.device)
-            comm.all_gather(self._all_labels, labels)
-            every, mine = self._all_labels, self._all_sampled
-        call('fte_pfc_sample', every, world * n, self.num_classes, S, self.sample_seed & 0xffffffff, int(self.global_step) & 0xffffffff,
-             self.class_index, self.class_inverse, mine, self.pfc_ws, self.pfc_ws.numel() * 4, st)
-        if comm is not None:
-            r = comm.rank()
-            self.sampled_labels = mine[r * n:(r + 1) * n]
-        call('fte_pfc_gather_cols', wc, self.class_index, self.Ws, EMBED, self.num_classes, self.cpad, S, spad, st)
-        call('fte_gemm_nn', self.emb, self.Ws, None, self.s_raw, n, spad, EMBED, self.ws, self.ws_bytes, st)
-        call('fte_row_norms', self.emb, self.xn, n, EMBED, EMBED, st)
-        call('fte_col_norms', self.Ws, self.wn, EMBED, S, spad, st)
-        call('fte_margin_softmax_fwd_bwd', self.s_raw, self.xn, self.wn, self.sampled_labels, self.margin_scale, self.margin,
-             self.margin_cos, self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, S, spad, self._grad_scale(n), st)
-        call('fte_asoftmax_colcoef', self.G, self.s_raw, self.wn, self.colcoef, n, S, spad, st)
-        return {'logits': self.logits_buf[:, :S], 'class_index': self.class_index[:S]}
 
-    def _head_backward(self, n, st):
+    def _sample_classes(self, labels, n, st):
         if self.sample_rate is None:
-            return super(SphereNetAdditiveMargin, self)._head_backward(n, st)
-        call = _lib.call
-        S, spad = self.sample_size, self._head_width()
-        gwc = self.view('classifier/fc_classifier/weights', self.grads)
-        call('fte_gemm_tn', self.emb, self.G, self.dWs, n, spad, EMBED, self.ws, self.ws_bytes, st)
-        call('fte_add_scaled_rows_cols', self.dWs, self.Ws, None, self.colcoef, EMBED, spad, spad, st)
-        if not self.compact_head_update:
-            call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, gwc, EMBED, self.num_classes, self.cpad, S, spad, st)
-        # else: the classifier range of `grads` is NOT written (it holds whatever an earlier step or mode left there); the gradient is
-        # compact_grad(), and apply_compact_update takes it into the classifier
-        call('fte_gemm_nt', self.G, self.Ws, None, None, 0, None, self.demb, None, n, spad, EMBED, self.ws, self.ws_bytes, st)
-        call('fte_add_scaled_rows_cols', self.demb, self.emb, self.rowcoef, None, n, EMBED, EMBED, st)
+            return labels, {}
+        S = self.sample_size
+        heads.sample_classes(self, labels, self.view('classifier/fc_classifier/weights'), n, EMBED, self.num_classes, self.cpad, S,
+                             self._head_width(), self.sample_seed, self.global_step, self.pfc_ws, self.pfc_ws.numel() * 4, st,
+                             self.sample_comm)
+        return self.sampled_labels, {'class_index': self.class_index[:S]}
+
+    def _head_cols(self):
+        """the sampled head is the dense head on its S gathered columns and their compact gradient"""
+        if self.sample_rate is None:
+            return super(SphereNetAdditiveMargin, self)._head_cols()
+        return self.Ws, self.dWs, self.sample_size, self._head_width()
+
+    def _scatter_dw(self, st):
+        # under compact_head_update the classifier range of `grads` is NOT written (it holds whatever an earlier step or mode left there);
+        # the gradient is compact_grad(), and apply_compact_update takes it into the classifier
+        if self.sample_rate is not None and not self.compact_head_update:
+            _lib.call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, self.view('classifier/fc_classifier/weights', self.grads), EMBED,
+                      self.num_classes, self.cpad, self.sample_size, self._head_width(), st)
 
     # ---- the compact classifier update (fte.h fte_pfc_momentum_update_cols / fte_pfc_adam_update_cols) -------------------------------
     def compact_active(self):
@@ -951,11 +925,8 @@ class SphereNetAdaFace(SphereNetMargin):
         self.a_rows = torch.empty(n, dtype=torch.float32, device=self.device)
         self.b_rows = torch.empty(n, dtype=torch.float32, device=self.device)
 
-    def _margin_head(self, labels, n, st):
-        _lib.call('fte_adaface_margins', self.xn, n, self.margin, self.adaface_h, self.adaface_t_alpha, int(self.update_moving_stats),
-                  self.adaface_stats, self.a_rows, self.b_rows, st)
-        _lib.call('fte_margin_softmax_rows_fwd_bwd', self.s_raw, self.xn, self.wn, labels, self.margin_scale, self.a_rows, self.b_rows,
-                  self.logits_buf, self.loss_rows, self.G, self.rowcoef, n, self.num_classes, self.cpad, self._grad_scale(n), st)
+    def _head_spec(self):
+        return heads.describe(self)
 
     def _others(self):
         return OrderedDict()
