@@ -1371,7 +1371,7 @@ int fte_gap_fwd(const float* x, float* y, int n, int hw, int c, void* stream) {
     return rc(l_gap_fwd(x, y, n, hw, c, (hipStream_t)stream));
 }
 int fte_gap_bwd(const float* dy, float* dx, int n, int hw, int c, void* stream) {
-    if (!dy || !dx || n <= 0 || hw <= 0) return FTE_EINVAL;
+    if (!dy || !dx || n <= 0 || hw <= 0 || c <= 0) return FTE_EINVAL;
     return rc(l_gap_bwd(dy, dx, n, hw, c, (hipStream_t)stream));
 }
 // ---- bf16 STORAGE twins of the BN-net layers (fte.h): flags bit 0 (FTE_S16_Z) = z / dz are bf16, bit 1 (FTE_S16_A) = y / shortcut /
@@ -1574,7 +1574,7 @@ int fte_gap_fwd_s16(const uint16_t* x16, float* y, int n, int hw, int c, void* s
     return rc(l_gap_fwd(f32p(x16), y, n, hw, c, (hipStream_t)stream, 2));
 }
 int fte_gap_bwd_s16(const float* dy, uint16_t* dx16, int n, int hw, int c, void* stream) {
-    if (!dy || !dx16 || n <= 0 || hw <= 0) return FTE_EINVAL;
+    if (!dy || !dx16 || n <= 0 || hw <= 0 || c <= 0) return FTE_EINVAL;
     return rc(l_gap_bwd(dy, f32p(dx16), n, hw, c, (hipStream_t)stream, 2));
 }
 int fte_dropout_fwd(const float* x, float* mask, float* y, long n, float keep_prob, uint64_t seed, void* stream) {
@@ -1613,8 +1613,10 @@ int fte_preprocess_u8_aug(const uint8_t* slots, float* out, int n, long slot_str
 
 // ------------------------------------------------------------------------------------------------
 // grouped 3x3 conv, SE-gate pieces
+// fte.h: c / groups in {4, 8, 16, 32}; any other width is refused here, before a launcher sees it
+static inline bool gconv_width_ok(int gw) { return gw == 4 || gw == 8 || gw == 16 || gw == 32; }
 int fte_gconv3x3_fwd(const float* x, const float* w, float* y, int n, int h, int wd, int c, int groups, int stride, void* stream) {
-    if (!x || !w || !y || n <= 0 || groups <= 0 || c % groups || (stride != 1 && stride != 2)) return FTE_EINVAL;
+    if (!x || !w || !y || n <= 0 || groups <= 0 || c % groups || (stride != 1 && stride != 2) || !gconv_width_ok(c / groups)) return FTE_EINVAL;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     return rc(l_gconv_fwd(x, w, y, n, h, wd, c, groups, ph.out, pw.out, stride, ph.before, pw.before, (hipStream_t)stream));
 }
@@ -1670,7 +1672,7 @@ int fte_gconv3x3_wgrad_bf16_s16(const uint16_t* x16, const uint16_t* dz16, float
                               l_gconv_wgrad16_chunks((long)n * ph.out * pw.out, c), (hipStream_t)stream, 1));
 }
 int fte_gconv3x3_dgrad(const float* dz, const float* w, float* dx, int n, int h, int wd, int c, int groups, int stride, void* stream) {
-    if (!dz || !w || !dx || n <= 0 || groups <= 0 || c % groups || (stride != 1 && stride != 2)) return FTE_EINVAL;
+    if (!dz || !w || !dx || n <= 0 || groups <= 0 || c % groups || (stride != 1 && stride != 2) || !gconv_width_ok(c / groups)) return FTE_EINVAL;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     return rc(l_gconv_dgrad(dz, w, dx, n, h, wd, c, groups, ph.out, pw.out, stride, ph.before, pw.before, (hipStream_t)stream));
 }
@@ -1681,7 +1683,7 @@ size_t fte_gconv3x3_wgrad_ws_bytes(int n, int h, int wd, int c, int groups, int 
 }
 int fte_gconv3x3_wgrad(const float* x, const float* dz, float* dw, int n, int h, int wd, int c, int groups, int stride,
                        void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !dz || !dw || n <= 0 || groups <= 0 || c % groups || (stride != 1 && stride != 2)) return FTE_EINVAL;
+    if (!x || !dz || !dw || n <= 0 || groups <= 0 || c % groups || (stride != 1 && stride != 2) || !gconv_width_ok(c / groups)) return FTE_EINVAL;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     const int gw = c / groups;
     const int chunks = l_gconv_wgrad_chunks((long)n * ph.out * pw.out, c, gw);
