@@ -204,6 +204,27 @@ int fte_preprocess_u8(const uint8_t* slots, float* out, int n, long slot_stride,
  * bit-equal to the host transform with augmentation = 1 (tf_face_toolbox_amd/preprocessing.py, float32 element by element). */
 int fte_preprocess_u8_aug(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
                           int crop_w, void* stream);
+/* The same transform with the geometric pair of preprocessing.py:41-71 of the reference (train.py --augmentation 2 | 3) between
+ * the crop and the flip: resize + crop, ZOOM, AFFINE, flip, colour (words 6..9, as above), (x - 0.5) / 0.5.  Same slots, same
+ * arguments and refusals as fte_preprocess_u8_aug, plus FTE_EINVAL for a null affine_table and FTE_EWORKSPACE for a workspace
+ * smaller than fte_preprocess_u8_geo_ws_bytes() (0 when an image's two float planes fit in LDS).  Further header words:
+ *   hd[6]     bit 8 = zoom applied ((th, tw) != (crop_h, crop_w)), bit 16 = affine
+ *   hd[10..11] th, tw: the zoom's target shape     hd[12] rnd: row of affine_table     hd[13..15] 0
+ * affine_table: device copy of preprocessing.AFFINE_TABLE, float32 [729][6] = (a0, a1, a2, b0, b1, b2).
+ *   ZOOM    I = resize(resize(I, th, tw), crop_h, crop_w), both the TF-1.x bilinear of fte_preprocess_u8 on floats:
+ *           in = out * (n_in / n_out), lo = floor(in), hi = min(lo + 1, n_in - 1), blended along x, then along y.
+ *   AFFINE  output pixel (x, y), coordinates of the crop BEFORE the flip, reads
+ *           sx = (a0 x + a1 y) + a2, sy = (b0 x + b1 y) + b2;  fx = floor(sx), fy = floor(sy), cx = fx + 1, cy = fy + 1;
+ *           top = (cx - sx) R(fy, fx) + (sx - fx) R(fy, cx);  bot = (cx - sx) R(cy, fx) + (sx - fx) R(cy, cx);
+ *           out = (cy - sy) top + (sy - fy) bot;  R = 0 outside the image  (tf.contrib.image.transform, 'BILINEAR').
+ * Every operation is float32 and rounds on its own.  Words 10..12 steer addresses and are NOT trusted: th outside [1, crop_h] or
+ * tw outside [1, crop_w] -> bit 8 is taken as clear; rnd outside [0, 728] -> bit 16 is taken as clear; every tap of the two
+ * resizes is clamped into its plane and the warp's zero fill is decided on the float coordinates (a NaN reads 0).  Mode 1 slots
+ * are copied.  With neither bit the output is fte_preprocess_u8_aug's; every value is bit-equal to the host transform with
+ * augmentation = 2 | 3 (tf_face_toolbox_amd/preprocessing.py: zoom_in_out, affine_warp). */
+size_t fte_preprocess_u8_geo_ws_bytes(int n, int channels, int crop_h, int crop_w);
+int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
+                          int crop_w, const float* affine_table, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * layers.batch_norm(scale=True, center=True, fused=True, decay=0.999, epsilon=1e-3) in TRAINING mode

@@ -3,7 +3,7 @@ crop / flip -> normalise -> NHWC float32 batch) in images/s at 112x112, on this 
 rate the GPU step consumes (~10 k images/s per MI355X in fp32, ~30 k in the bf16 mode).
 
     python scripts/bench_loader.py [--images 2048] [--batch 512] [--batches 60] [--warmup 24] [--src 250] [--device cpu|cuda]
-                                   [--augmentation 0|1]
+                                   [--augmentation 0|1|2|3]
 
 Writes N synthetic JPEGs of src x src pixels (CASIA-WebFace crops are 250 x 250) to a temporary directory, then times
 `data.train_inputs(...)` batches (resize to 128 x 128, random crop 112 x 112, flip; --augmentation 1: the colour augmentation of
@@ -29,7 +29,8 @@ def main():
     ap.add_argument('--src', type=int, default=250)
     ap.add_argument('--device', default=None, help="default: cuda when a GPU is present (the training path: pinned staging ring + async copy), else cpu")
     ap.add_argument('--workers', type=int, default=None, help='decode worker processes (default: data.train_inputs picks; 0 = threads)')
-    ap.add_argument('--augmentation', type=int, choices=[0, 1], default=0, help='1: flip + brightness / hue / saturation (train.py --augmentation 1)')
+    ap.add_argument('--augmentation', type=int, choices=[0, 1, 2, 3], default=0,
+                    help='1: flip + brightness / hue / saturation; 2: zoom + affine warp + flip; 3: both (train.py --augmentation)')
     args = ap.parse_args()
     from tf_face_toolbox_amd import data
     if args.device is None:
@@ -59,7 +60,7 @@ def main():
         print('loader: %.0f images/s sustained (%d batches of %d after %d untimed, %dx%d JPEG -> 128x128 -> crop 112x112, workers %s, os.cpu_count=%d, usable CPUs (affinity / cgroup quota) %d, device %s%s), batch %s %s'
               % (args.batches * args.batch / el, args.batches, args.batch, args.warmup, args.src, args.src,
                  'auto' if args.workers is None else args.workers, os.cpu_count(), data.usable_cpus(), args.device,
-                 ', augmentation 1, gpu_transform %s' % bool(inp['gpu_transform']) if args.augmentation else '', tuple(x.shape), x.dtype))
+                 ', augmentation %d, gpu_transform %s' % (args.augmentation, bool(inp['gpu_transform'])) if args.augmentation else '', tuple(x.shape), x.dtype))
 
 
 if __name__ == '__main__':

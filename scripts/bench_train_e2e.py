@@ -2,7 +2,7 @@
 GPU step), to be read against bench.py's synthetic-input figure: does the loader keep the GPU busy?
 
     python scripts/bench_train_e2e.py [--net SphereNet-ASoftmax] [--batch 512] [--steps 60] [--images 4096] [--src 250]
-                                      [--augmentation 0|1]
+                                      [--augmentation 0|1|2|3]
 
 Writes N synthetic JPEGs (src x src, CASIA-WebFace crops are 250 x 250) and a list file to a temporary directory, then runs
 train.py (resize to 128 x 128, random crop 112 x 112, flip -- the reference's SphereFace recipe) as a child process and prints
@@ -27,7 +27,8 @@ def main():
     ap.add_argument('--images', type=int, default=4096)
     ap.add_argument('--src', type=int, default=250)
     ap.add_argument('--mfma_dtype', default='f32')
-    ap.add_argument('--augmentation', type=int, choices=[0, 1], default=0, help='passed to train.py: 1 = the colour augmentation')
+    ap.add_argument('--augmentation', type=int, choices=[0, 1, 2, 3], default=0,
+                    help='passed to train.py: 1 = the colour augmentation, 2 = the geometric pair, 3 = both')
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     with tempfile.TemporaryDirectory() as d:
@@ -43,7 +44,7 @@ def main():
                '--model_dir', os.path.join(d, 'models'), '--train_list_path', lst, '--input_height', '128', '--input_width', '128',
                '--crop_height', '112', '--crop_width', '112', '--batch_size', str(a.batch), '--num_gpus', '1', '--init_lr', '0.001',
                '--max_epoches', '1000', '--lr_decay_epoch', '400,800', '--max_steps', str(a.steps), '--display_interval', '20', '--save_interval', '100000',
-               '--mfma_dtype', a.mfma_dtype] + (['--augmentation', '1'] if a.augmentation else [])
+               '--mfma_dtype', a.mfma_dtype] + (['--augmentation', str(a.augmentation)] if a.augmentation else [])
         out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
         tail = [ln for ln in out.stdout.splitlines() if 'mean throughput' in ln or 'sustained' in ln or 'Error' in ln or 'error' in ln]
         print('\n'.join(tail[-4:]) if tail else out.stdout[-2000:])

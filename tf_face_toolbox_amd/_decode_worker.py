@@ -88,7 +88,10 @@ def _finish(raw, input_height, input_width, crop_height, crop_width, augmentatio
         image = resize_window(raw, input_height, input_width, y0, crop_height, x0, crop_width)
     else:
         image = resize_window(raw, input_height, input_width)
-    if augmentation:
+    if augmentation & 2:                                            # the geometric pair: zoom, then affine (draws u, rnd)
+        from .preprocessing import geometric_augmentation
+        image = geometric_augmentation(image, rng)
+    if augmentation & 1:
         from .preprocessing import data_augmentation
         image = data_augmentation(image, rng)
     elif rng.random() < 0.5:                                        # tf.image.random_flip_left_right
@@ -101,7 +104,8 @@ def train_example(path, num_channels, input_height, input_width, crop_height, cr
 
 
 HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip}, the augmentation's {flags, float32 brightness,
-#                              hue, saturation} + padding (include/fte.h: fte_preprocess_u8, fte_preprocess_u8_aug)
+#                              hue, saturation}, the geometric pair's {th, tw, rnd} + padding (include/fte.h: fte_preprocess_u8,
+#                              fte_preprocess_u8_aug, fte_preprocess_u8_geo)
 
 
 def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0):
@@ -109,7 +113,9 @@ def raw_example(slot, path, num_channels, input_height, input_width, crop_height
     batch buffer -- resize / crop / flip / normalise then run on the GPU (fte_preprocess_u8) and give the bits train_example()
     gives.  rng None: the evaluation transform (full window, no flip).  An image too large for its slot is transformed here
     and stored finished (mode 1).  augmentation: the draws of preprocessing.data_augmentation as well (header words 6..9: flag
-    bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug."""
+    bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug.
+    augmentation & 2: the geometric pair's draws too (word 6 bits 8 = zoom applied, 16 = affine; words 10..12 = the zoom's target
+    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo."""
     raw = _load(path, num_channels)
     h0, w0 = raw.shape[:2]
     cropped = crop_height != -1 and crop_width != -1
@@ -128,10 +134,17 @@ def raw_example(slot, path, num_channels, input_height, input_width, crop_height
         if cropped:
             y0 = int(rng.integers(0, input_height - crop_height + 1))
             x0 = int(rng.integers(0, input_width - crop_width + 1))
-        if augmentation:
+        geo = 0
+        if augmentation & 2:
+            from .preprocessing import AFFINE, ZOOM, geometric_draws
+            th, tw, rnd = geometric_draws(rng, out_h, out_w)
+            geo = AFFINE | (ZOOM if (th, tw) != (out_h, out_w) else 0)
+            hd[6] = geo
+            hd[10:13] = (th, tw, rnd)
+        if augmentation & 1:
             from .preprocessing import augmentation_draws
             flip, flags, brightness, hue, saturation = augmentation_draws(rng, num_channels)
-            hd[6] = flags
+            hd[6] = flags | geo
             hd[7:10].view(np.float32)[:] = (brightness, hue, saturation)
         else:
             flip = int(rng.random() < 0.5)

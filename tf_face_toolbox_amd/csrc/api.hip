@@ -1611,6 +1611,21 @@ int fte_preprocess_u8_aug(const uint8_t* slots, float* out, int n, long slot_str
     return rc(k_preprocess_u8_aug(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, (hipStream_t)stream));
 }
 
+size_t fte_preprocess_u8_geo_ws_bytes(int n, int channels, int crop_h, int crop_w) {
+    if (n <= 0 || (channels != 1 && channels != 3) || crop_h <= 0 || crop_w <= 0) return 0;
+    return k_preprocess_u8_geo_ws_bytes(n, channels, crop_h, crop_w);
+}
+
+int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
+                          const float* affine_table, void* ws, size_t ws_bytes, void* stream) {
+    if (!slots || !out || !affine_table || n <= 0 || (channels != 1 && channels != 3) || in_h <= 0 || in_w <= 0 || crop_h <= 0 ||
+        crop_w <= 0 || crop_h > in_h || crop_w > in_w || slot_stride < 64 || slot_stride % 64 || n > 65535 ||
+        (long)crop_h * crop_w * channels >= ((long)1 << 28)) return FTE_EINVAL;       // plane offsets are ints
+    const size_t need = k_preprocess_u8_geo_ws_bytes(n, channels, crop_h, crop_w);
+    if (need && (!ws || ws_bytes < need)) return FTE_EWORKSPACE;
+    return rc(k_preprocess_u8_geo(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, affine_table, ws, (hipStream_t)stream));
+}
+
 // ------------------------------------------------------------------------------------------------
 // grouped 3x3 conv, SE-gate pieces
 // fte.h: c / groups in {4, 8, 16, 32}; any other width is refused here, before a launcher sees it

@@ -1753,3 +1753,207 @@ hipError_t k_preprocess_u8_aug(const unsigned char* slots, float* out, int n, lo
     else preprocess_u8_aug_kernel<1><<<grid, 256, 0, st>>>(slots, out, slot_stride, in_h, in_w, crop_h, crop_w);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// the same transform with the geometric pair of preprocessing.py:41-71 of the reference between the crop and the flip:
+// _random_zoom_in_out (resize the crop down to th x tw and back up, both TF-1.x bilinear) and _random_affine_distort (a bilinear
+// warp, zero outside the image, by one of the 729 coefficient sets of `table`), as tf_face_toolbox_amd/preprocessing.py states them
+// in float32.  Header: hd[6] bit 8 = zoom, bit 16 = affine, hd[10] = th, hd[11] = tw, hd[12] = rnd (the table row).  Siblings of
+// the two kernels above, which stay what they were.
+//
+// An output pixel reads 4 warped-source pixels, each of those 4 zoomed-down pixels, each of those 4 resized pixels, each of
+// those 4 bytes: the stages are STAGED, not recomputed.  One workgroup per image; planes P (crop_h x crop_w x C floats) and Q
+// (th x tw x C, at most as large) live in LDS when both fit (gray 112 x 112: 98 KB), else in the caller's workspace (the
+// workgroup's own 2 planes: written and read by this workgroup only, __syncthreads() between the stages orders them):
+//   A  slot bytes -> P   resize + crop, not flipped           B  P -> Q   resize down      C  Q -> P   resize up
+//   D  P -> out          warp, flip (of the OUTPUT column), colour, normalise
+// An image with neither bit goes straight from the bytes to `out`, one pass, the arithmetic of preprocess_u8_aug_kernel.
+// Words 10..12 steer addresses and are not trusted: th outside [1, crop_h] or tw outside [1, crop_w] clears the zoom, rnd outside
+// [0, 728] clears the affine; every tap of B and C is clamped (lo into [0, n - 1], hi = min(lo + 1, n - 1)); the warp compares
+// its FLOAT coordinates with the image's bounds before any becomes an index (a NaN or an infinity reads the zero fill).
+template <int C>
+__device__ __forceinline__ void geo_resized_pixel(const unsigned char* img0, int h0, int w0, int in_h, int in_w, int yy, int xx, float* v) {
+#pragma clang fp contract(off)
+    const float s = (float)(1.0 / 255.0);
+    const float py = (float)yy * ((float)h0 / (float)in_h);
+    const float pxs = (float)xx * ((float)w0 / (float)in_w);
+    const int ylo = min(max((int)floorf(py), 0), h0 - 1), xlo = min(max((int)floorf(pxs), 0), w0 - 1);
+    const int yhi = min(ylo + 1, h0 - 1), xhi = min(xlo + 1, w0 - 1);
+    const float yw = py - (float)ylo, xw = pxs - (float)xlo;
+    const unsigned char* tl = img0 + ((long)ylo * w0 + xlo) * C;
+    const unsigned char* tr = img0 + ((long)ylo * w0 + xhi) * C;
+    const unsigned char* bl = img0 + ((long)yhi * w0 + xlo) * C;
+    const unsigned char* br = img0 + ((long)yhi * w0 + xhi) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float a = (float)tl[c] * s, b = (float)tr[c] * s;
+        const float d = (float)bl[c] * s, e = (float)br[c] * s;
+        const float top = (b - a) * xw + a;
+        const float bot = (e - d) * xw + d;
+        v[c] = (bot - top) * yw + top;
+    }
+}
+
+// src [sh, sw, C] -> dst [dh, dw, C], the float branch of resize_window (no 1/255)
+template <int C>
+__device__ __forceinline__ void geo_resize_plane(const float* src, int sh, int sw, float* dst, int dh, int dw) {
+#pragma clang fp contract(off)
+    const float ry = (float)sh / (float)dh, rx = (float)sw / (float)dw;
+    for (int p = threadIdx.x; p < dh * dw; p += blockDim.x) {
+        const int r = p / dw, cc = p - r * dw;
+        const float py = (float)r * ry, pxs = (float)cc * rx;
+        const int ylo = min(max((int)floorf(py), 0), sh - 1), xlo = min(max((int)floorf(pxs), 0), sw - 1);
+        const int yhi = min(ylo + 1, sh - 1), xhi = min(xlo + 1, sw - 1);
+        const float yw = py - (float)ylo, xw = pxs - (float)xlo;
+        const float* tl = src + (ylo * sw + xlo) * C;
+        const float* tr = src + (ylo * sw + xhi) * C;
+        const float* bl = src + (yhi * sw + xlo) * C;
+        const float* br = src + (yhi * sw + xhi) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float a = tl[c], b = tr[c], d = bl[c], e = br[c];
+            const float top = (b - a) * xw + a;
+            const float bot = (e - d) * xw + d;
+            dst[p * C + c] = (bot - top) * yw + top;
+        }
+    }
+}
+
+// brightness / hue / saturation / normalise of one pixel: the tail of preprocess_u8_aug_kernel
+template <int C>
+__device__ __forceinline__ void geo_colour_store(float* v, int flags, float delta_b, float delta_h, float factor, float* o) {
+#pragma clang fp contract(off)
+    if (flags & 1) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = v[c] - delta_b;
+    }
+    if constexpr (C == 3) {
+        if (flags & 2) {
+            float h, sa, va;
+            aug_rgb_to_hsv(fminf(fmaxf(v[0], 0.f), 1.f), fminf(fmaxf(v[1], 0.f), 1.f), fminf(fmaxf(v[2], 0.f), 1.f), h, sa, va);
+            const float a = h + (-delta_h);
+            h = a - floorf(a);
+            aug_hsv_to_rgb(h, sa, va, v[0], v[1], v[2]);
+        }
+        if (flags & 4) {
+            float h, sa, va;
+            aug_rgb_to_hsv(fminf(fmaxf(v[0], 0.f), 1.f), fminf(fmaxf(v[1], 0.f), 1.f), fminf(fmaxf(v[2], 0.f), 1.f), h, sa, va);
+            sa = fminf(fmaxf(sa * factor, 0.f), 1.f);
+            aug_hsv_to_rgb(h, sa, va, v[0], v[1], v[2]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = (v[c] - 0.5f) / 0.5f;
+}
+
+constexpr int GEO_THREADS = 1024;
+constexpr size_t GEO_LDS_MAX = 160 * 1024;
+
+template <int C, bool IN_LDS>
+__global__ __launch_bounds__(GEO_THREADS) void preprocess_u8_geo_kernel(const unsigned char* __restrict__ slots, float* __restrict__ out,
+                                                                        long slot_stride, int in_h, int in_w, int crop_h, int crop_w,
+                                                                        const float* __restrict__ table, float* ws) {
+#pragma clang fp contract(off)     // as in preprocess_u8_kernel: every operation rounds on its own, as numpy's do
+    extern __shared__ __attribute__((aligned(16))) float geo_planes[];
+    const int img = blockIdx.x;
+    const unsigned char* slot = slots + (long)img * slot_stride;
+    const int* hd = reinterpret_cast<const int*>(slot);
+    const int mode = hd[0], h0 = hd[1], w0 = hd[2], y0 = hd[3], x0 = hd[4], flip = hd[5], flags = hd[6];
+    const int npx = crop_h * crop_w;
+    float* o = out + (long)img * npx * C;
+    if (mode == 1) {                              // finished by the worker, every augmentation included
+        const float* f = reinterpret_cast<const float*>(slot + 64);
+        for (int i = threadIdx.x; i < npx * C; i += GEO_THREADS) o[i] = f[i];
+        return;
+    }
+    const int th = hd[10], tw = hd[11], rnd = hd[12];
+    const bool zoom = (flags & 8) && th >= 1 && th <= crop_h && tw >= 1 && tw <= crop_w;
+    const bool affine = (flags & 16) && rnd >= 0 && rnd <= 728;
+    const float delta_b = __int_as_float(hd[7]), delta_h = __int_as_float(hd[8]), factor = __int_as_float(hd[9]);
+    const unsigned char* img0 = slot + 64;
+    if (!zoom && !affine) {                       // one pass, bytes -> out
+        for (int px = threadIdx.x; px < npx; px += GEO_THREADS) {
+            const int r = px / crop_w, cc = px - r * crop_w;
+            const int col = flip ? crop_w - 1 - cc : cc;
+            float v[C];
+            geo_resized_pixel<C>(img0, h0, w0, in_h, in_w, y0 + r, x0 + col, v);
+            geo_colour_store<C>(v, flags, delta_b, delta_h, factor, o + (long)px * C);
+        }
+        return;
+    }
+    float* P = IN_LDS ? geo_planes : ws + (long)img * 2 * npx * C;
+    float* Q = P + npx * C;
+    for (int px = threadIdx.x; px < npx; px += GEO_THREADS) {                  // A
+        const int r = px / crop_w, cc = px - r * crop_w;
+        float v[C];
+        geo_resized_pixel<C>(img0, h0, w0, in_h, in_w, y0 + r, x0 + cc, v);
+#pragma unroll
+        for (int c = 0; c < C; ++c) P[px * C + c] = v[c];
+    }
+    __syncthreads();
+    if (zoom) {                                   // uniform over the workgroup: the header decides
+        geo_resize_plane<C>(P, crop_h, crop_w, Q, th, tw);                     // B
+        __syncthreads();
+        geo_resize_plane<C>(Q, th, tw, P, crop_h, crop_w);                     // C
+        __syncthreads();
+    }
+    float a0 = 1.f, a1 = 0.f, a2 = 0.f, b0 = 0.f, b1 = 1.f, b2 = 0.f;
+    if (affine) {
+        const float* t = table + rnd * 6;
+        a0 = t[0]; a1 = t[1]; a2 = t[2]; b0 = t[3]; b1 = t[4]; b2 = t[5];
+    }
+    const float xmax = (float)(crop_w - 1), ymax = (float)(crop_h - 1);
+    for (int px = threadIdx.x; px < npx; px += GEO_THREADS) {                  // D
+        const int r = px / crop_w, cc = px - r * crop_w;
+        const int col = flip ? crop_w - 1 - cc : cc;
+        float v[C];
+        if (affine) {
+            const float x = (float)col, y = (float)r;
+            const float sx = (a0 * x + a1 * y) + a2, sy = (b0 * x + b1 * y) + b2;
+            const float fx = floorf(sx), fy = floorf(sy), cx = fx + 1.f, cy = fy + 1.f;
+            const float wl = cx - sx, wr = sx - fx, wt = cy - sy, wb = sy - fy;
+            const bool xl = fx >= 0.f && fx <= xmax, xr = cx >= 0.f && cx <= xmax;          // false for a NaN
+            const bool yt = fy >= 0.f && fy <= ymax, yb = cy >= 0.f && cy <= ymax;
+            const int ixl = xl ? (int)fx : 0, ixr = xr ? (int)cx : 0, iyt = yt ? (int)fy : 0, iyb = yb ? (int)cy : 0;
+            const float* ptl = P + (iyt * crop_w + ixl) * C;
+            const float* ptr = P + (iyt * crop_w + ixr) * C;
+            const float* pbl = P + (iyb * crop_w + ixl) * C;
+            const float* pbr = P + (iyb * crop_w + ixr) * C;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float rtl = (yt && xl) ? ptl[c] : 0.f, rtr = (yt && xr) ? ptr[c] : 0.f;
+                const float rbl = (yb && xl) ? pbl[c] : 0.f, rbr = (yb && xr) ? pbr[c] : 0.f;
+                const float top = wl * rtl + wr * rtr;
+                const float bot = wl * rbl + wr * rbr;
+                v[c] = wt * top + wb * bot;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[c] = P[(r * crop_w + col) * C + c];
+        }
+        geo_colour_store<C>(v, flags, delta_b, delta_h, factor, o + (long)px * C);
+    }
+}
+
+size_t k_preprocess_u8_geo_ws_bytes(int n, int channels, int crop_h, int crop_w) {
+    const size_t planes = (size_t)2 * crop_h * crop_w * channels * sizeof(float);
+    return planes <= GEO_LDS_MAX ? 0 : planes * n;
+}
+
+hipError_t k_preprocess_u8_geo(const unsigned char* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w,
+                               int crop_h, int crop_w, const float* table, void* ws, hipStream_t st) {
+    const size_t planes = (size_t)2 * crop_h * crop_w * channels * sizeof(float);
+    const bool in_lds = planes <= GEO_LDS_MAX;
+    const size_t lds = in_lds ? planes : 0;
+#define FTE_GEO(C_, L_) do { \
+        auto kern = preprocess_u8_geo_kernel<C_, L_>; \
+        if (lds > 48 * 1024) { \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            if (e != hipSuccess) return e; \
+        } \
+        kern<<<dim3(n), GEO_THREADS, lds, st>>>(slots, out, slot_stride, in_h, in_w, crop_h, crop_w, table, (float*)ws); } while (0)
+    if (channels == 3) { if (in_lds) FTE_GEO(3, true); else FTE_GEO(3, false); }
+    else { if (in_lds) FTE_GEO(1, true); else FTE_GEO(1, false); }
+#undef FTE_GEO
+    return hipGetLastError();
+}

@@ -397,21 +397,31 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
     """(slot bytes, transform) when the decode workers hand over DECODED uint8 images and the resize / crop / flip / normalise
     runs on the GPU (fte_preprocess_u8: the same bits as the host transform, tests/test_gpu_loader.py), else (0, None).  The
     host transform is 0.6 of the 1.7 ms a 250 x 250 JPEG costs a worker; the decode stays.  With `augmentation` the colour
-    augmentation (preprocessing.py) runs there too, from the workers' draws (fte_preprocess_u8_aug, tests/test_gpu_augment.py).
+    augmentation (preprocessing.py) runs there too, from the workers' draws (fte_preprocess_u8_aug, tests/test_gpu_augment.py);
+    with `augmentation & 2` the geometric pair (zoom, affine warp) as well (fte_preprocess_u8_geo, tests/test_gpu_geo_augment.py:
+    the affine table is uploaded and the workspace allocated once per loader; the slot size is the same).
     FTE_LOADER_GPU=0 keeps everything on the host.  A slot holds an image of FTE_LOADER_RAW_SIDE^2 pixels
     (default 256; CASIA-WebFace crops are 250 x 250) -- a larger image is transformed by its worker and handed over finished."""
     if num_workers <= 0 or torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0':
         return 0, None
-    entry = 'fte_preprocess_u8_aug' if augmentation else 'fte_preprocess_u8'
+    entry = 'fte_preprocess_u8_geo' if augmentation & 2 else 'fte_preprocess_u8_aug' if augmentation else 'fte_preprocess_u8'
     from . import _lib
     from ._decode_worker import HEADER_BYTES
     side = int(os.environ.get('FTE_LOADER_RAW_SIDE', '256'))
     slot = HEADER_BYTES + max(side * side * num_channels, out_h * out_w * num_channels * 4)
     slot = (slot + 63) // 64 * 64
 
+    extra = ()
+    if augmentation & 2:
+        from .preprocessing import AFFINE_TABLE
+        table = torch.from_numpy(AFFINE_TABLE).to(device)
+        ws_bytes = _lib.query('fte_preprocess_u8_geo_ws_bytes', rows, num_channels, out_h, out_w)
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=device)
+        extra = (table, ws, ws_bytes)             # the tensors live as long as the closure
+
     def transform(raw):
         out = torch.empty((rows, out_h, out_w, num_channels), dtype=torch.float32, device=raw.device)
-        _lib.call(entry, raw.data_ptr(), out.data_ptr(), rows, slot, num_channels, in_h, in_w, out_h, out_w,
+        _lib.call(entry, raw.data_ptr(), out.data_ptr(), rows, slot, num_channels, in_h, in_w, out_h, out_w, *extra,
                   torch.cuda.current_stream().cuda_stream)
         return out
     return slot, transform

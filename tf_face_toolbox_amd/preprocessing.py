@@ -1,6 +1,8 @@
-"""Host-side image augmentation: mirror of the reference's preprocessing.py:22-38 (the only function
-train_inputs calls).  CPU image ops, not part of the GPU step; numpy restatements of
-tf.image.{random_flip_left_right, adjust_brightness, adjust_hue, adjust_saturation}."""
+"""Host-side image augmentation: mirror of the reference's preprocessing.py.  Lines 22-38 (the only function the reference's
+train_inputs calls): numpy restatements of tf.image.{random_flip_left_right, adjust_brightness, adjust_hue, adjust_saturation}.
+Lines 41-71 (_random_zoom_in_out, _random_affine_distort, which the reference defines and never calls): the geometric pair
+below, `augmentation & 2`.  The array code here is the bit-exact specification of the loader's GPU transforms
+(fte_preprocess_u8_aug, fte_preprocess_u8_geo; include/fte.h)."""
 import colorsys  # noqa: F401  (documented reference for the HSV convention below)
 
 import numpy as np
@@ -81,3 +83,79 @@ def data_augmentation(image, rng):
     """preprocessing.py:22-38: flip; with prob 1/2 darken by delta in [0,0.1); RGB only: with prob 1/2
     hue shift by -delta (delta in [0,0.2)), with prob 1/2 desaturate by a factor in [0.6,1)."""
     return apply_augmentation(image, *augmentation_draws(rng, image.shape[-1]))
+
+
+# ------------------------------------------------------------------ geometric pair (preprocessing.py:41-71 of the reference)
+GEOMETRIC = 2                                # bit of `augmentation`: zoom + affine before the flip / colour part
+ZOOM, AFFINE = 8, 16                         # flag bits of the slot header's word 6 (include/fte.h: fte_preprocess_u8_geo)
+LANDMARKS_X, LANDMARKS_Y = (38, 89, 64), (55, 55, 105)
+# The landmarks are two eyes and the mouth of a 128 x 128 aligned face, in PIXELS of the image being warped whatever its size
+# -- as the reference has them: on a 112 x 112 crop they sit 8 pixels low and right of the features, on a 32 x 24 image two of
+# them lie outside it.  The warp stays a one-pixel perturbation either way (the solve is exact for any three points).
+
+
+def _affine_table():
+    """All 729 coefficient sets of _random_affine_distort: each landmark moves by -1, 0 or +1 pixel in x and in y (rnd in base 3,
+    Python-2 integer division), A t = target solved in float64 for x and for y, the six coefficients (a0, a1, a2, b0, b1, b2)
+    cast to float32.  An OUTPUT pixel (x, y) samples the source at (a0 x + a1 y + a2, b0 x + b1 y + b2)."""
+    a = np.stack([np.asarray(LANDMARKS_X, np.float64), np.asarray(LANDMARKS_Y, np.float64), np.ones(3)], 1)
+    table = np.empty((729, 6), dtype=np.float32)
+    for rnd in range(729):
+        dx = (rnd // 243 - 1, rnd % 81 // 27 - 1, rnd % 9 // 3 - 1)
+        dy = (rnd % 243 // 81 - 1, rnd % 27 // 9 - 1, rnd % 3 - 1)
+        table[rnd, :3] = np.linalg.solve(a, a[:, 0] + dx)
+        table[rnd, 3:] = np.linalg.solve(a, a[:, 1] + dy)
+    return table
+
+
+AFFINE_TABLE = _affine_table()
+
+
+def geometric_draws(rng, height, width):
+    """The draws of the geometric pair for a height x width image, in order: the zoom's scale u in [0.5, 1.5) (float64, cast to
+    float32, min with 1; the target shape is the float32 product truncated), then the affine index rnd in [0, 729).
+    Returns (th, tw, rnd); (th, tw) == (height, width) -- about half of the draws -- means no zoom."""
+    scale = min(np.float32(rng.uniform(0.5, 1.5)), np.float32(1))
+    th, tw = int(scale * np.float32(height)), int(scale * np.float32(width))
+    return th, tw, int(rng.integers(0, 729))
+
+
+def zoom_in_out(image, th, tw):
+    """_random_zoom_in_out with the target shape given: resize down to th x tw and back up, both TF-1.x bilinear
+    (_decode_worker.resize_window); the same shape is the identity, as in TF."""
+    from ._decode_worker import resize_window
+    h, w = image.shape[:2]
+    return resize_window(resize_window(image, th, tw), h, w)
+
+
+def affine_warp(image, coef):
+    """tf.contrib.image.transform(image, coef + [0, 0], 'BILINEAR') as the TF-1.x kernel computes it, in float32 with every
+    operation rounded on its own: output pixel (x, y) reads (sx, sy) = ((a0 x + a1 y) + a2, (b0 x + b1 y) + b2); with
+    f = floor, c = f + 1:  top = (cx - sx) R(fy, fx) + (sx - fx) R(fy, cx), bot the same on row cy,
+    out = (cy - sy) top + (sy - fy) bot;  R is 0 outside the image."""
+    h, w, _ = image.shape
+    a0, a1, a2, b0, b1, b2 = (np.float32(v) for v in coef)
+    x = np.arange(w, dtype=np.float32)[None, :]
+    y = np.arange(h, dtype=np.float32)[:, None]
+    sx = (a0 * x + a1 * y) + a2
+    sy = (b0 * x + b1 * y) + b2
+    fx, fy = np.floor(sx), np.floor(sy)
+    cx, cy = fx + np.float32(1), fy + np.float32(1)
+
+    def read(yy, xx):
+        ok = (yy >= 0) & (yy <= h - 1) & (xx >= 0) & (xx <= w - 1)          # false for NaN as well
+        yi = np.where(ok, yy, 0).astype(np.int64)
+        xi = np.where(ok, xx, 0).astype(np.int64)
+        return np.where(ok[:, :, None], image[yi, xi], np.float32(0))
+    wl, wr = (cx - sx)[:, :, None], (sx - fx)[:, :, None]
+    top = wl * read(fy, fx) + wr * read(fy, cx)
+    bot = wl * read(cy, fx) + wr * read(cy, cx)
+    out = (cy - sy)[:, :, None] * top + (sy - fy)[:, :, None] * bot
+    assert out.dtype == np.float32
+    return out
+
+
+def geometric_augmentation(image, rng):
+    """zoom, then affine, from draws taken here (u, then rnd)"""
+    th, tw, rnd = geometric_draws(rng, image.shape[0], image.shape[1])
+    return affine_warp(zoom_in_out(np.ascontiguousarray(image, dtype=np.float32), th, tw), AFFINE_TABLE[rnd])

@@ -35,7 +35,8 @@ def build_parser():
     parser.add_argument('--crop_height', type=int, default=-1, help='The height of input images.')
     parser.add_argument('--crop_width', type=int, default=-1, help='The width of input images.')
     parser.add_argument('--is_color', type=int, default=1, help='Whether to read inputs as RGB images.')
-    parser.add_argument('--augmentation', type=int, default=0, help='Whether to employ data augmentation to training set.')
+    parser.add_argument('--augmentation', type=int, default=0, help='Data augmentation of the training set: 0 = random flip only, 1 = flip + colour (brightness, hue, saturation), '
+                        '2 = geometric (low-resolution zoom, one-pixel affine warp) + flip, 3 = geometric + colour.')
     # Hyperparameters configure
     parser.add_argument('--batch_size', type=int, default=-1, help='Number of sampled images in a batch.')
     parser.add_argument('--num_classes', type=int, default=-1, help='Number of sampled classesin a batch.')
