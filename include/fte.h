@@ -661,6 +661,37 @@ int fte_margin_softmax_rows_fwd_bwd(const float* s, const float* xn, const float
  * FTE_EINVAL: a null pointer, n < 2, m < 0, h <= 0, t_alpha outside [0, 1] (or any of them NaN). */
 int fte_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats,
                         float* a_rows, float* b_rows, void* stream);
+/* Sub-center ArcFace (Deng et al., ECCV 2020): K centres per class, the class cosine the max over them; DESIGN.md 4.16.
+ * LAYOUT -- planar: with ld the padded class count of ONE plane, the classifier W [d, K*ld], the raw product s = x @ W [n, K*ld],
+ * G [n, K*ld], wn [K*ld] and colcoef [K*ld] hold centre k of class j at column k*ld + j; columns c..ld-1 of every plane are
+ * padding.  (A 16-byte chunk of a plane is four classes, so the pool is an element-wise max of K aligned loads; plane k of W is
+ * W + k*ld with row stride K*ld, which a per-plane gather / scatter of sampled classes can address without a new kernel.)
+ * The contract is that of fte_margin_softmax_fwd_bwd -- eps, clamp, t, t', the presets -- on the pooled cosine:
+ *   c_ijk = clamp(s[i, k*ld+j] / (max(xn_i, eps) * wn[k*ld+j]), -1, 1),   c_ij = max_k c_ijk,
+ *   k*(i,j) = the LOWEST k that attains the max (a fixed rule: two calls give the same bits)
+ *   z, loss_rows and dL/dc_ij as above on c_ij (the margin applies to the pooled target cosine)
+ *   G[i, k*ld+j] = dL/dc_ij / (max(xn_i, eps) * wn[k*ld+j]) for k = k*(i,j), exactly 0.0f for the other centres and in the pad
+ *   columns of every plane;  rowcoef_i = xn_i > eps ? -sum_{j,k} G s / xn_i^2 : 0;  f (optional, [n, ld]) = the pooled z, 0 in pads.
+ * wn is read only at k*ld + j, j < c.  An out-of-range label gives a NaN row: loss, rowcoef, f and G below c in EVERY plane are
+ * NaN, the pads 0, the other rows bitwise unaffected.  With K = 1 every output is bit-identical to fte_margin_softmax_fwd_bwd on
+ * the same inputs.  16-byte aligned s / wn / G / f and ld % 4 == 0 take the vector path, anything else the scalar one.
+ * FTE_EINVAL: the cases of fte_margin_softmax_fwd_bwd, and K outside 1..8. */
+int fte_subcenter_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, int K,
+                                         float scale, float m, float m3, float* f, float* loss_rows, float* G, float* rowcoef,
+                                         int n, int c, int ld, float grad_scale, void* stream);
+/* colcoef [K*ld] of the planar layout: colcoef[k*ld+j] = -sum_i G[i, k*ld+j] * s[i, k*ld+j] / wn[k*ld+j]^2 for j < c and 0 for
+ * the pad columns c..ld-1 of EVERY plane (fte_asoftmax_colcoef over one width K*ld would divide by wn = 0 in the pads of the
+ * interior planes).  With K = 1 bit-identical to fte_asoftmax_colcoef.  FTE_EINVAL: its cases, and K outside 1..8. */
+int fte_subcenter_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int K, int n, int c, int ld, void* stream);
+/* The assignment of the cleaning pass: for sample i with label y, cosv[k*n + i] = clamp(x_i . w_k / (max(|x_i|, eps) *
+ * max(|w_k|, eps)), -1, 1) for the K centres w_k = Wt[k*c + y, :] of its OWN class, and sel[i] = arg max_k, the lowest k on a tie.
+ * x [n, d]; Wt [K*c, d] is the classifier transposed once by the caller, row k*c + j = centre k of class j (no padding);
+ * sel [n] int32, cosv [K*n].  Only K rows of Wt are read per sample -- the [n, K*c] product is never formed.  A label outside
+ * [0, c) gives sel = -1 and cosv = NaN for every k.  One wave per sample; lane l sums elements l, l+64, ... in index order and the
+ * lanes merge in a fixed butterfly, so the order of every sum depends on d ONLY: a sample's result is the same bits wherever it
+ * sits in the batch and whatever n is.  FTE_EINVAL: a null pointer, n, d or c < 1, K outside 1..8. */
+int fte_subcenter_assign(const float* x, const float* Wt, const int32_t* labels, int K, int32_t* sel, float* cosv,
+                         int n, int d, int c, void* stream);
 /* out[i] = sqrt(sum_j a[i,j]^2) over rows of [rows, ld] (cols used) */
 int fte_row_norms(const float* a, float* out, int rows, int cols, int ld, void* stream);
 /* out[j] = sqrt(sum_i a[i,j]^2) over columns */

@@ -157,6 +157,9 @@ _SIGS = {
     'fte_asoftmax_colcoef': (c_int, [_P] * 4 + [c_int] * 3 + [_P]),
     'fte_margin_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] * 3 + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
     'fte_margin_softmax_rows_fwd_bwd': (c_int, [_P] * 4 + [c_float] + [_P] * 6 + [c_int] * 3 + [c_float, _P]),
+    'fte_subcenter_margin_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_int] + [c_float] * 3 + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
+    'fte_subcenter_colcoef': (c_int, [_P] * 4 + [c_int] * 4 + [_P]),
+    'fte_subcenter_assign': (c_int, [_P] * 3 + [c_int] + [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_adaface_margins': (c_int, [_P, c_int] + [c_float] * 3 + [c_int] + [_P] * 4),
     'fte_row_norms': (c_int, [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_col_norms': (c_int, [_P] * 2 + [c_int] * 3 + [_P]),

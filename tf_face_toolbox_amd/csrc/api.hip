@@ -1230,6 +1230,24 @@ int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float*
     if (!G || !s || !wn || !colcoef || n <= 0 || c <= 0 || ld < c) return FTE_EINVAL;
     return rc(k_asoftmax_colcoef(G, s, wn, colcoef, n, c, ld, (hipStream_t)stream));
 }
+int fte_subcenter_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, int K, float scale, float m,
+                                         float m3, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld,
+                                         float grad_scale, void* stream) {
+    if (!s || !xn || !wn || !labels || !loss_rows || !G || !rowcoef || n <= 0 || c <= 0 || ld < c || !(scale > 0.f) || !(m >= 0.f) ||
+        K < 1 || K > 8)
+        return FTE_EINVAL;
+    return rc(k_subcenter_margin_softmax(s, xn, wn, labels, K, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, grad_scale,
+                                         (hipStream_t)stream));
+}
+int fte_subcenter_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int K, int n, int c, int ld, void* stream) {
+    if (!G || !s || !wn || !colcoef || n <= 0 || c <= 0 || ld < c || K < 1 || K > 8) return FTE_EINVAL;
+    return rc(k_subcenter_colcoef(G, s, wn, colcoef, K, n, c, ld, (hipStream_t)stream));
+}
+int fte_subcenter_assign(const float* x, const float* wt, const int32_t* labels, int K, int32_t* sel, float* cosv, int n, int d, int c,
+                         void* stream) {
+    if (!x || !wt || !labels || !sel || !cosv || n <= 0 || d <= 0 || c <= 0 || K < 1 || K > 8) return FTE_EINVAL;
+    return rc(k_subcenter_assign(x, wt, labels, K, sel, cosv, n, d, c, (hipStream_t)stream));
+}
 int fte_row_norms(const float* a, float* out, int rows, int cols, int ld, void* stream) {
     if (!a || !out || rows <= 0 || cols <= 0 || ld < cols) return FTE_EINVAL;
     return rc(k_row_norms(a, out, rows, cols, ld, (hipStream_t)stream));

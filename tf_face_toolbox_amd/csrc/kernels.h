@@ -28,6 +28,13 @@ hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, co
 hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, const float* a_rows,
                                  const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
                                  hipStream_t st);
+// K centres per class in K planes of ld columns (fte.h "Sub-center ArcFace"); K in 1..8 (hipErrorInvalidValue otherwise)
+hipError_t k_subcenter_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, int K, float scale, float m,
+                                      float m3, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
+                                      hipStream_t st);
+hipError_t k_subcenter_colcoef(const float* G, const float* s, const float* wn, float* cc, int K, int n, int c, int ld, hipStream_t st);
+hipError_t k_subcenter_assign(const float* x, const float* wt, const int32_t* labels, int K, int32_t* sel, float* cosv, int n, int d, int c,
+                              hipStream_t st);
 hipError_t k_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats, float* a_rows, float* b_rows,
                              hipStream_t st);
 hipError_t k_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* cc, int n, int c, int ld, hipStream_t st);

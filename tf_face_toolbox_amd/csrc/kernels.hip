@@ -852,6 +852,283 @@ __global__ __launch_bounds__(256) void margin_softmax_rows_kernel(const float* _
     }
 }
 
+// Sub-center head (fte.h fte_subcenter_margin_softmax_fwd_bwd): K centres per class in K planes of ld columns, centre k of class j
+// at column k * ld + j; s / G rows are K * ld wide, f rows ld.  The class cosine is the max over the K planes, the LOWEST k winning
+// a tie (strict > from plane 0 up; a NaN in plane 0 stays), and the two passes are margin_softmax_kernel's on the pooled cosine,
+// statement for statement: with K = 1 the results are the same bits.  Pass 2 writes the winner's plane and 0.0f into the others.
+// K is a template parameter (the planes of a chunk sit in registers, no scratch); the chunks in flight shrink as K grows so that
+// a thread holds at most 8 s / wn chunk pairs.  A kernel of its own for the reason given at margin_softmax_rows_kernel.
+struct PoolRow {
+    float ix, S, zy;
+    int y;
+    // cosine to one centre, and the winner so far (c, its r = ix / wn and its s)
+    __device__ __forceinline__ void first(float sv, float wv, float& cb, float& rb, float& sb) const {
+        rb = ix * __builtin_amdgcn_rcpf(wv);
+        cb = clamp1(sv * rb);
+        sb = sv;
+    }
+    __device__ __forceinline__ bool next(float sv, float wv, float& cb, float& rb, float& sb) const {
+        const float r = ix * __builtin_amdgcn_rcpf(wv);
+        const float ck = clamp1(sv * r);
+        const bool win = ck > cb;
+        if (win) { cb = ck; rb = r; sb = sv; }
+        return win;
+    }
+    __device__ __forceinline__ float z(float cb, int j) const { return j == y ? zy : S * cb; }
+};
+
+template <int K, bool VEC>
+__global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                       const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                       float S, float m, float m3, float* __restrict__ f,
+                                                                       float* __restrict__ loss_rows, float* __restrict__ G,
+                                                                       float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    constexpr int U = K <= 2 ? 4 : (K <= 4 ? 2 : 1);            // chunks (of K planes) in flight per thread and trip
+    constexpr float EPS = 1e-12f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * K * ld;
+    float* gr = G + (long)row * K * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const int yl = labels[row];
+    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
+    const int y = bad ? 0 : yl;
+    const float xr = xn[row];
+    PoolRow R;
+    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
+    R.S = S;
+    R.y = y;
+    // target term, once per row, on the pooled target cosine
+    float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        const float ck = clamp1(sr[(long)k * ld + y] * (R.ix * __builtin_amdgcn_rcpf(wn[(long)k * ld + y])));
+        if (ck > cy) cy = ck;
+    }
+    float ty = cy - m3, tp = 1.f;
+    if (m > 0.f) {
+        const float cm = cosf(m), sm = sinf(m);
+        if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
+            const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+            ty = cy * cm - st * sm - m3;
+            tp = cm + sm * cy / fmaxf(st, 1e-6f);
+        } else {
+            ty = cy - m * sm - m3;                              // easy_margin = False fallback
+        }
+    }
+    R.zy = S * ty;
+    const float off = bad ? NAN : 0.f;                          // the centres that did not win: 0, NaN in a NaN row
+
+    // pass 1: online max / sum of exp over the pooled logits
+    float mx = -INFINITY, se = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < c; b += 1024 * U) {
+            f32x4 sv[U][K], wv[U][K];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        sv[u][k] = *reinterpret_cast<const f32x4*>(sr + (long)k * ld + j);
+                        if (j + 4 <= c) wv[u][k] = *reinterpret_cast<const f32x4*>(wn + (long)k * ld + j);
+                        else for (int q = 0; q < 4; ++q) wv[u][k][q] = j + q < c ? wn[(long)k * ld + j + q] : 1.f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    float z[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        z[q] = -INFINITY;
+                        if (j + q < c) {
+                            float cb, rb, sb;
+                            R.first(sv[u][0][q], wv[u][0][q], cb, rb, sb);
+#pragma unroll
+                            for (int k = 1; k < K; ++k) R.next(sv[u][k][q], wv[u][k][q], cb, rb, sb);
+                            z[q] = R.z(cb, j + q);
+                        }
+                    }
+                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
+                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < c; j += 256) {
+            float cb, rb, sb;
+            R.first(sr[j], wn[j], cb, rb, sb);
+#pragma unroll
+            for (int k = 1; k < K; ++k) R.next(sr[(long)k * ld + j], wn[(long)k * ld + j], cb, rb, sb);
+            const float z = R.z(cb, j);
+            if (z > mx) { se *= __expf(mx - z); mx = z; }
+            se += __expf(z - mx);
+        }
+    }
+    const float M = block_max(mx, sh);
+    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
+    const float inv = 1.f / se;
+    const float gS = gscale * S, gT = gscale * S * tp;
+
+    // pass 2: G of the winning centre (0 in the others; and f), sum of G * s
+    float acc = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < ld; b += 1024 * U) {
+            f32x4 sv[U][K], wv[U][K];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        sv[u][k] = *reinterpret_cast<const f32x4*>(sr + (long)k * ld + j);
+                        if (j + 4 <= c) wv[u][k] = *reinterpret_cast<const f32x4*>(wn + (long)k * ld + j);
+                        else for (int q = 0; q < 4; ++q) wv[u][k][q] = j + q < c ? wn[(long)k * ld + j + q] : 1.f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < ld) {
+                    f32x4 gv[K], fv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < K; ++k) gv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (j < c) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            if (j + q < c) {
+                                float cb, rb, sb;
+                                int kw = 0;
+                                R.first(sv[u][0][q], wv[u][0][q], cb, rb, sb);
+#pragma unroll
+                                for (int k = 1; k < K; ++k) if (R.next(sv[u][k][q], wv[u][k][q], cb, rb, sb)) kw = k;
+                                const float z = R.z(cb, j + q);
+                                const float p = __expf(z - M) * inv;
+                                const float g = (j + q == y ? (p - 1.f) * gT : p * gS) * rb;
+                                acc += g * sb;
+#pragma unroll
+                                for (int k = 0; k < K; ++k) gv[k][q] = k == kw ? g : off;
+                                fv[q] = z;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < K; ++k) *reinterpret_cast<f32x4*>(gr + (long)k * ld + j) = gv[k];
+                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < ld; j += 256) {
+            float g = 0.f, fv = 0.f;
+            int kw = 0;
+            if (j < c) {
+                float cb, rb, sb;
+                R.first(sr[j], wn[j], cb, rb, sb);
+#pragma unroll
+                for (int k = 1; k < K; ++k) if (R.next(sr[(long)k * ld + j], wn[(long)k * ld + j], cb, rb, sb)) kw = k;
+                const float z = R.z(cb, j);
+                const float p = __expf(z - M) * inv;
+                g = (j == y ? (p - 1.f) * gT : p * gS) * rb;
+                acc += g * sb;
+                fv = z;
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) gr[(long)k * ld + j] = k == kw ? g : (j < c ? off : 0.f);
+            if (fr) fr[j] = fv;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (t == 0) {
+        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
+        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
+    }
+}
+
+// colcoef of the K-plane classifier: asoftmax_colcoef_kernel's sums, statement for statement, with the row stride K * ld and the plane
+// in blockIdx.y -- live columns are j < c of EVERY plane, the pads of every plane get 0 (wn is not read there: it is 0)
+__global__ __launch_bounds__(256) void subcenter_colcoef_kernel(const float* __restrict__ G, const float* __restrict__ s,
+                                                                const float* __restrict__ wn, float* __restrict__ cc,
+                                                                int n, int c, int ld, long ldr) {
+    __shared__ float sh[4][64];
+    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + cl;
+    const long col = (long)blockIdx.y * ld + j;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (j < c) {
+        int i = rl;
+        for (; i + 12 < n; i += 16) {
+            const long o0 = (long)i * ldr + col, o1 = (long)(i + 4) * ldr + col, o2 = (long)(i + 8) * ldr + col, o3 = (long)(i + 12) * ldr + col;
+            a0 += G[o0] * s[o0]; a1 += G[o1] * s[o1]; a2 += G[o2] * s[o2]; a3 += G[o3] * s[o3];
+        }
+        for (; i < n; i += 4) { const long o = (long)i * ldr + col; a0 += G[o] * s[o]; }
+    }
+    sh[rl][cl] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    if (rl == 0 && j < ld) {
+        float a = 0.f;
+        if (j < c) {
+            a = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
+            const float w_ = wn[col];
+            a = -a / (w_ * w_);
+        }
+        cc[col] = a;
+    }
+}
+
+// Assignment of the cleaning pass (fte.h fte_subcenter_assign): one wave per sample, four samples per block.  Lane l takes the
+// elements l, l + 64, ... of the feature and of the K centre rows of the sample's class in index order (the dot products and all
+// norms in the one pass), and the lanes merge through the xor butterfly: the order of every sum depends on d alone.
+__global__ __launch_bounds__(256) void subcenter_assign_kernel(const float* __restrict__ x, const float* __restrict__ wt,
+                                                               const int32_t* __restrict__ labels, int K, int32_t* __restrict__ sel,
+                                                               float* __restrict__ cosv, int n, int d, int c) {
+    constexpr float EPS = 1e-12f;
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int y = labels[i];
+    if ((unsigned)y >= (unsigned)c) {                           // a label outside the table: nothing of it is read
+        if (lane == 0) sel[i] = -1;
+        if (lane < K) cosv[(long)lane * n + i] = NAN;
+        return;
+    }
+    const float* xr = x + (long)i * d;
+    float xx = 0.f, dot[8], ww[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { dot[k] = 0.f; ww[k] = 0.f; }
+    for (int e = lane; e < d; e += 64) {
+        const float xv = xr[e];
+        xx += xv * xv;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k < K) {
+                const float wv = wt[((long)k * c + y) * d + e];
+                dot[k] += xv * wv;
+                ww[k] += wv * wv;
+            }
+        }
+    }
+    xx = wave_sum(xx);
+    const float ix = 1.f / fmaxf(sqrtf(xx), EPS);
+    float best = 0.f;
+    int kb = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (k < K) {
+            const float dk = wave_sum(dot[k]), wk = wave_sum(ww[k]);
+            const float ck = clamp1(dk * ix / fmaxf(sqrtf(wk), EPS));
+            if (k == 0 || ck > best) { best = ck; kb = k; }
+            if (lane == 0) cosv[(long)k * n + i] = ck;
+        }
+    }
+    if (lane == 0) sel[i] = kb;
+}
+
 // AdaFace margins from the embedding norms (fte.h fte_adaface_margins).  ONE block: every thread sums its strided elements in
 // index order, the partials merge through block_sum in a fixed order (two calls on the same data are bit-identical); two passes
 // (mean, then squared deviations), the running statistics blended on the device -- no host read-back.
@@ -1386,6 +1663,35 @@ hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* w
     const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
     if (vec) hipLaunchKernelGGL(margin_softmax_rows_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(margin_softmax_rows_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+template <int K>
+static void subcenter_launch(bool vec, const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m, float m3,
+                             float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs, hipStream_t st) {
+    if (vec) hipLaunchKernelGGL((subcenter_margin_softmax_kernel<K, true>), dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
+    else hipLaunchKernelGGL((subcenter_margin_softmax_kernel<K, false>), dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
+}
+hipError_t k_subcenter_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, int K, float scale, float m,
+                                      float m3, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
+                                      hipStream_t st) {
+    // ld % 4 == 0 and aligned bases: every plane k * ld of s / wn / G starts on 16 bytes, and so does every row (stride K * ld)
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+#define FTE_SUBCENTER_K(k) case k: subcenter_launch<k>(vec, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, gs, st); break;
+    switch (K) {
+        FTE_SUBCENTER_K(1) FTE_SUBCENTER_K(2) FTE_SUBCENTER_K(3) FTE_SUBCENTER_K(4)
+        FTE_SUBCENTER_K(5) FTE_SUBCENTER_K(6) FTE_SUBCENTER_K(7) FTE_SUBCENTER_K(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef FTE_SUBCENTER_K
+    return hipGetLastError();
+}
+hipError_t k_subcenter_colcoef(const float* G, const float* s, const float* wn, float* cc, int K, int n, int c, int ld, hipStream_t st) {
+    hipLaunchKernelGGL(subcenter_colcoef_kernel, dim3((ld + 63) / 64, K), dim3(256), 0, st, G, s, wn, cc, n, c, ld, (long)K * ld);
+    return hipGetLastError();
+}
+hipError_t k_subcenter_assign(const float* x, const float* wt, const int32_t* labels, int K, int32_t* sel, float* cosv, int n, int d, int c,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(subcenter_assign_kernel, dim3((n + 3) / 4), dim3(256), 0, st, x, wt, labels, K, sel, cosv, n, d, c);
     return hipGetLastError();
 }
 hipError_t k_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats, float* a_rows, float* b_rows,

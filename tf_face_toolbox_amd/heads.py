@@ -1,10 +1,11 @@
-"""The launch sequence of the heads on the normalised features and classifier columns (A-softmax, ArcFace / CosFace, AdaFace and the
-sampled-class form), written once: loss.py, nets/sphere.py and nets/graph.py call it.
+"""The launch sequence of the heads on the normalised features and classifier columns (A-softmax, ArcFace / CosFace, AdaFace, the
+sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py call it.
 
 Plain functions over buffers the CALLER owns.  `b` is any object that carries them under the nets' attribute names -- a net itself, or
 the scratch namespace loss.py allocates per call: xn [n], wn [ld], rowcoef [n], colcoef [ld], G [n, ld], loss_rows [n]; for AdaFace
 also adaface_stats [2], a_rows [n], b_rows [n]; for the class sampler class_index [spad], class_inverse [c], sampled_labels [n],
-Ws [d, spad].  Nothing here allocates on a step (the sampler's all-gather pair is made once per batch size).  Every launch goes
+Ws [d, spad]; with K > 1 centres per class (planar layout, fte.h "Sub-center ArcFace") wn, colcoef and the columns of G are K * ld.
+Nothing here allocates on a step (the sampler's all-gather pair is made once per batch size).  Every launch goes
 through `_lib.call`, looked up when it is made: the launch recorder and tests/step_audit.py swap it.
 
 The gradient contract (fte.h): G = dLoss/ds feeds the classifier's two products, and the two normalisations add
@@ -25,14 +26,42 @@ def describe(net):
     statistics move under the net's update_moving_stats -- or (head, S, m, m3) for 'arcface' / 'cosface'."""
     if net.head == 'adaface':
         return ('adaface', net.margin_scale, net.margin, net.adaface_h, net.adaface_t_alpha, int(net.update_moving_stats))
+    K = int(getattr(net, 'sub_centers', 1))
+    if K > 1:                            # K centres per class: the count rides behind (S, m, m3); K = 1 is today's tuple
+        return (net.head, net.margin_scale, net.margin, net.margin_cos, K)
     return (net.head, net.margin_scale, net.margin, net.margin_cos)
+
+
+SUB_CENTERS_MAX = 8
+
+
+def check_sub_centers(K, head='arcface', sample_rate=None, what='the head'):
+    """The centre count of a net or a loss call -> int K.  ValueError for K outside 1..8 and, with K > 1, for every head but ArcFace /
+    CosFace and for the class sampler (the per-plane gather / scatter the planar layout prepares is not built: DESIGN.md 9)."""
+    if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= SUB_CENTERS_MAX:
+        raise ValueError('sub_centers must be an integer in 1..%d (got %r)' % (SUB_CENTERS_MAX, K))
+    K = int(K)
+    if K > 1 and head not in ('arcface', 'cosface'):
+        raise ValueError('sub_centers = %d needs an ArcFace / CosFace head: %s has %r' % (K, what, head))
+    if K > 1 and sample_rate is not None and float(sample_rate) < 1.0:
+        raise ValueError('sub_centers = %d does not compose with the class sampler (sample_rate %g < 1): not built yet' % (K, sample_rate))
+    return K
 
 
 def margin_forward(b, x, W, s, labels, logits, head, n, d, c, ld, grad_scale, st):
     """From the features x [n, d], the classifier columns in use W [d, ld] (c live ones) and their raw product s [n, ld]: the norms,
-    the margin kernel of `head` -- ('asoftmax', lambda), describe()'s tuples -- and colcoef.  Leaves the margin logits in `logits`
+    the margin kernel of `head` -- ('asoftmax', lambda), describe()'s tuples -- and colcoef.  A describe() tuple that ends in K > 1:
+    W, s, b.G are K * ld wide, b.wn / b.colcoef K * ld long, c and ld describe ONE plane and `logits` is [n, ld].  Leaves the margin logits in `logits`
     (None: not wanted), the loss per row in b.loss_rows, G = grad_scale * dLoss/ds in b.G, and rowcoef / colcoef for the backward."""
     call = _lib.call
+    if head[0] in ('arcface', 'cosface') and len(head) == 5:      # K centres per class
+        S, m, m3, K = head[1:]
+        call('fte_row_norms', x, b.xn, n, d, d, st)
+        call('fte_col_norms', W, b.wn, d, K * ld, K * ld, st)       # the pads of every plane are zero columns: wn = 0, never read
+        call('fte_subcenter_margin_softmax_fwd_bwd', s, b.xn, b.wn, labels, K, S, m, m3, logits, b.loss_rows, b.G, b.rowcoef, n, c, ld,
+             grad_scale, st)
+        call('fte_subcenter_colcoef', b.G, s, b.wn, b.colcoef, K, n, c, ld, st)
+        return
     call('fte_row_norms', x, b.xn, n, d, d, st)
     call('fte_col_norms', W, b.wn, d, c, ld, st)
     out = (logits, b.loss_rows, b.G, b.rowcoef, n, c, ld, grad_scale, st)

@@ -1,5 +1,5 @@
 """Host-side mirror of the reference's loss.py: focal_loss (:18-27), center_loss (:29-45), batch_hard_triplet_loss
-(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference), its sampled-class form partial_fc_margin_loss and adaface_loss (the margin per row from the feature norms).  Same names, argument meaning and defaults.  There is no autograd here, so every function
+(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference), its K-centre form subcenter_margin_loss, its sampled-class form partial_fc_margin_loss and adaface_loss (the margin per row from the feature norms).  Same names, argument meaning and defaults.  There is no autograd here, so every function
 also returns the gradient of ITS OWN loss value with respect to its first argument (what tf.gradients would have
 produced for that term); the graph nets wire them as heads (nets/graph.py), a caller can combine them freely.
 
@@ -118,6 +118,31 @@ def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, marg
     dw = torch.empty_like(weights)
     head = ('arcface', float(scale), float(margin), float(margin_cos))
     return _head_run(_head_scratch(features, n, d, ld), features, weights, dw, labels, head, n, d, c, ld) + (dw,)
+
+
+def subcenter_margin_loss(features, weights, labels, K, scale=64.0, margin=0.5, margin_cos=0.0, num_classes=None):
+    """additive_margin_loss with K centres per class (sub-center ArcFace, Deng et al. 2020): the class cosine is the max over its K
+    centres, the lowest k on a tie, and only the winning centre of a (row, class) pair takes its gradient; the contract is fte.h's
+    fte_subcenter_margin_softmax_fwd_bwd.  weights [D, K * ld] is planar: centre k of class j is column k * ld + j, columns
+    num_classes..ld-1 of every plane are padding (default num_classes = ld); D % 64 == 0 and ld % 64 == 0.  K in 1..8; K = 1 is
+    additive_margin_loss itself (the same calls, bit-identical).  The other arguments and the result (loss, dfeatures [N, D],
+    dweights [D, K * ld]) are additive_margin_loss's."""
+    K = heads.check_sub_centers(K)
+    if K == 1:
+        return additive_margin_loss(features, weights, labels, scale, margin, margin_cos, num_classes)
+    features, weights, labels, n, d, wide, c = _head_args(features, weights, labels, None)
+    if wide % K:
+        raise ValueError('weights [D, K * ld] with K = %d: %d columns do not divide' % (K, wide))
+    ld = wide // K
+    c = ld if num_classes is None else int(num_classes)
+    dw = torch.empty_like(weights)
+    b = _head_scratch(features, n, d, wide)
+    head = ('arcface', float(scale), float(margin), float(margin_cos), K)
+    _lib.call('fte_gemm_nn', features, weights, None, b.s, n, wide, d, b.ws, b.wsb, b.st)
+    heads.margin_forward(b, features, weights, b.s, labels, None, head, n, d, c, ld, 1.0 / n, b.st)
+    heads.classifier_dw(b, features, weights, dw, n, d, wide, b.ws, b.wsb, b.st)
+    heads.classifier_dx(b, features, weights, b.dx, n, d, wide, b.ws, b.wsb, b.st)
+    return _scaled_sum(b.loss_rows, 1.0 / n), b.dx, dw
 
 
 def adaface_loss(features, weights, labels, stats, scale=64.0, margin=0.4, h=0.333, t_alpha=0.01, update=True, num_classes=None):

@@ -112,6 +112,7 @@ class GraphNet(Network):
         self.triplet_margin = None        # 'triplet': None = soft-margin (softplus), loss.py:47
         self.focal_gamma, self.focal_alpha = 1.0, 2.0     # 'focal': loss.py:18 defaults (names as in the reference)
         self.margin_scale = self.margin = self.margin_cos = None      # 'arcface' / 'cosface': S, m, m3 (_set_head)
+        self.sub_centers = 1              # 'arcface' / 'cosface': K centres per class in K planes of cpad columns (set_sub_centers)
 
     def _set_head(self, head, scale=None, margin=None, margin_cos=None):
         """the subclasses' head= argument; a margin head resolves (S, m, m3) against its preset (nets/net_base.py MARGIN_PRESETS)"""
@@ -125,6 +126,12 @@ class GraphNet(Network):
             self.margin_cos = 0.0
         elif (scale, margin, margin_cos) != (None, None, None):
             raise ValueError('scale / margin / margin_cos belong to the arcface / cosface heads, not %r' % head)
+
+    def set_sub_centers(self, K):
+        """K centres per class (fte.h "Sub-center ArcFace"), before build(): the classifier becomes [D, K * cpad], centre k of class j at
+        column k * cpad + j, and [D, K * C] in the reference layout (planes packed)."""
+        assert not self.built, 'sub_centers is fixed when the variables are created'
+        self.sub_centers = heads.check_sub_centers(K, self.head, None, self.name)
 
     # ---- to be provided by the subclass ----------------------------------------------------------
     def build_graph(self, in_ch, num_classes):
@@ -140,6 +147,8 @@ class GraphNet(Network):
         self.num_classes = int(num_classes)
         self.cpad = (self.num_classes + 127) // 128 * 128
         self.graph, spec = self.build_graph(channels, num_classes)
+        if self.sub_centers > 1:
+            spec = [(n, (s[0], self.sub_centers * s[1]) if k == 'cls_w' else s, k) for n, s, k in spec]
         self.spec = OrderedDict((n, (s, k)) for n, s, k in spec)
         # A 3x3 stem of at most 32 filters (ShuffleNet-v2 small: 24) is stored 32 channels wide, not channel_pad wide: its
         # 56x56 output is the largest tensor of the net, and every pass over it (BN statistics / apply, max-pool, their
@@ -200,7 +209,7 @@ class GraphNet(Network):
         pc = (lambda c: (c + 31) // 32 * 32) if name in self.narrow else self._pc
         if kind == 'cls_w':
             assert pc(shape[0]) == shape[0]
-            return (shape[0], self.cpad)
+            return (shape[0], self.sub_centers * self.cpad)
         if kind == 'conv_w':
             k, _, cin, cout = shape
             if cin <= 4:                                       # the stem (image channels): [k*k*cin -> kpad, cout]
@@ -260,7 +269,7 @@ class GraphNet(Network):
         t = self.view(name, arena).reshape(self.ishape[name])
         ref = v.ref_shape
         if v.kind == 'cls_w':
-            return t[:, :self.num_classes].clone()
+            return t.reshape(ref[0], self.sub_centers, self.cpad)[:, :, :self.num_classes].reshape(ref).clone()
         if v.kind == 'conv_w':
             k, _, cin, cout = ref
             if cin <= 4:
@@ -288,7 +297,7 @@ class GraphNet(Network):
         assert tuple(t.shape) == ref, (name, tuple(t.shape), ref)
         buf = torch.zeros(self.ishape[name], device=self.device)
         if v.kind == 'cls_w':
-            buf[:, :self.num_classes] = t
+            buf.view(ref[0], self.sub_centers, self.cpad)[:, :, :self.num_classes] = t.reshape(ref[0], self.sub_centers, self.num_classes)
         elif v.kind == 'conv_w':
             k, _, cin, cout = ref
             if cin <= 4:
@@ -343,7 +352,7 @@ class GraphNet(Network):
                 shp[out] = (shp[op[2]][2],)
                 real[out] = real[op[2]]
             elif kind == 'fc':
-                shp[out] = (self.cpad,)
+                shp[out] = (self.sub_centers * self.cpad,)
                 real[out] = self.num_classes
             elif kind == 'split':
                 ih, iw, _ = shp[op[2]]
@@ -720,19 +729,19 @@ class GraphNet(Network):
             elif kind == 'dropout':
                 self.t[out + '/mask'] = torch.empty(shape, **f32)
             elif kind == 'fc':
-                need = max(need, q('fte_gemm_ws_bytes', n, self.cpad, self.shapes[op[2]][0]))
+                need = max(need, q('fte_gemm_ws_bytes', n, self.sub_centers * self.cpad, self.shapes[op[2]][0]))
         if s16:
             from ._packs import FilterPacks
             self.packs = FilterPacks(self._pack_entries, dev, head=int(os.environ.get('FTE_PACK_HEAD', '4')))
             self.w16, self.w16t = self.packs.w16, self.packs.w16t
-        self.G = torch.empty(n, self.cpad, **f32)
+        self.G = torch.empty(n, self.sub_centers * self.cpad, **f32)
         self.loss_rows = torch.empty(n, **f32)
         fdim = self.shapes[self.feature_name][0]
         self.dfeat = torch.empty(n, fdim, **f32)
         self.ones_n = torch.ones(n, **f32)
         if self.head in NORMALISED_HEADS:
             self.xn, self.rowcoef = torch.empty(n, **f32), torch.empty(n, **f32)
-            self.wn, self.colcoef = torch.empty(self.cpad, **f32), torch.empty(self.cpad, **f32)
+            self.wn, self.colcoef = (torch.empty(self.sub_centers * self.cpad, **f32) for _ in range(2))
         if self.head == 'adaface':
             self.a_rows, self.b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
         need = max(need, 4 * n * fdim, 12 * n * n)
@@ -1066,7 +1075,7 @@ class GraphNet(Network):
                     T[out].copy_(T[op[2]])
             elif kind == 'fc':
                 k = self.shapes[op[2]][0]
-                call('fte_gemm_nn', T[op[2]], self.view(op[3]), None, T[out], n, self.cpad, k, self.ws, self.ws_bytes, st)
+                call('fte_gemm_nn', T[op[2]], self.view(op[3]), None, T[out], n, self.sub_centers * self.cpad, k, self.ws, self.ws_bytes, st)
             else:
                 raise RuntimeError('op %s must have been fused away' % kind)
 
@@ -1296,8 +1305,8 @@ class GraphNet(Network):
             main = torch.cuda.current_stream()
             side.wait_event(main.record_event())         # G (the loss head's gradient) and the features are complete
             wst, wws = side.cuda_stream, self.ws_side
-        heads.classifier_dw(self, x, W, self.view(op[3], self.grads), n, k, self.cpad, wws, self.ws_bytes, wst, norm)      # (before the bucket is reduced)
-        heads.classifier_dx(self, x, W, gin, n, k, self.cpad, self.ws, self.ws_bytes, st, norm)
+        heads.classifier_dw(self, x, W, self.view(op[3], self.grads), n, k, self.sub_centers * self.cpad, wws, self.ws_bytes, wst, norm)      # (before the bucket is reduced)
+        heads.classifier_dx(self, x, W, gin, n, k, self.sub_centers * self.cpad, self.ws, self.ws_bytes, st, norm)
         if side is not None and join:
             torch.cuda.current_stream().wait_stream(side)
         self._grad[op[2]] = gin

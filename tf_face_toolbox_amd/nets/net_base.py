@@ -52,10 +52,25 @@ def adaface_state(device):
     return stats, OrderedDict((name, stats[i:i + 1]) for i, name in enumerate(ADAFACE_STATE))
 
 
-def net_select(name, data_format='NCHW', weight_decay=5e-4):
+SUB_CENTER_NETS = ('SphereNet-ArcFace', 'SphereNet-CosFace', 'ResNet-50-arcface', 'ResNet-50-cosface')
+
+
+def sub_centers_check(name, sub_centers, sample_rate=None):
+    """sub_centers of net_select / train.py --sub_centers -> int K; ValueError for what the K-centre head does not do (K outside 1..8;
+    with K > 1: a net outside SUB_CENTER_NETS -- the A-softmax and AdaFace heads among them -- and the class sampler)."""
+    from ..heads import check_sub_centers
+    K = check_sub_centers(sub_centers)
+    if K > 1 and name not in SUB_CENTER_NETS:
+        raise ValueError('sub_centers = %d: only %s have a K-centre head, not %s' % (K, ' / '.join(SUB_CENTER_NETS), name))
+    return check_sub_centers(K, 'arcface', sample_rate, name)
+
+
+def net_select(name, data_format='NCHW', weight_decay=5e-4, sub_centers=1):
     """nets/net_base.py:22-63.  Names kept verbatim; `SphereNet-ASoftmax` is the margin net the
     reference's `DataParallel_margin` (data_parallel.py:220) expects but whose code is missing
-    from the snapshot (README.md:14,19)."""
+    from the snapshot (README.md:14,19).  `sub_centers` = K centres per class (sub-center ArcFace, fte.h; SUB_CENTER_NETS only;
+    1 = one column per class, the nets as they always were)."""
+    sub_centers = sub_centers_check(name, sub_centers)
     if name == 'SphereNet':
         from .sphere import SphereNet
         network = SphereNet(data_format=data_format, weight_decay=weight_decay)
@@ -64,7 +79,8 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4):
         network = SphereNetMargin(data_format=data_format, weight_decay=weight_decay)
     elif name in ('SphereNet-ArcFace', 'SphereNet-CosFace'):      # additive-margin heads (fte.h fte_margin_softmax_fwd_bwd)
         from .sphere import SphereNetAdditiveMargin
-        network = SphereNetAdditiveMargin(data_format=data_format, weight_decay=weight_decay, head=name.split('-')[1].lower())
+        network = SphereNetAdditiveMargin(data_format=data_format, weight_decay=weight_decay, head=name.split('-')[1].lower(),
+                                          sub_centers=sub_centers)
     elif name == 'SphereNet-AdaFace':                             # quality-adaptive margin head (fte.h fte_adaface_margins)
         from .sphere import SphereNetAdaFace
         network = SphereNetAdaFace(data_format=data_format, weight_decay=weight_decay)
@@ -74,6 +90,7 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4):
     elif name in ('ResNet-50-arcface', 'ResNet-50-cosface', 'ResNet-50-adaface'):
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay, head=name.split('-')[2])
+        network.set_sub_centers(sub_centers)
     elif name == 'ResNet-26':                    # not a reference factory name; the class accepts 26 (nets/resnet.py:39-40)
         from .resnet import ResNet
         network = ResNet(num_layers=26, data_format=data_format, weight_decay=weight_decay)

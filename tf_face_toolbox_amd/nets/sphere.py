@@ -67,6 +67,7 @@ class SphereNet(Network):
         self.bf16_copies = os.environ.get('FTE_BF16_COPIES', '1') != '0'
         self.tower_scale = 1.0        # 1/num_gpus, set by the parallel wrapper (data_parallel.py:37)
         self.global_step = 0          # A-softmax lambda annealing reads it
+        self.sub_centers = 1          # K centres per class (SphereNetAdditiveMargin only; fte.h "Sub-center ArcFace")
         self._act_n = None
 
     # ------------------------------------------------------------------ construction
@@ -107,7 +108,9 @@ class SphereNet(Network):
             big.append((c.name + '/weights', 'conv_w', (3, 3, c.cin, c.cout), 9 * c.cin * c.cout))
         small.append((self.name + '/fully_connected/biases', 'fc_b', (EMBED,), EMBED))
         big.append((self.name + '/fully_connected/weights', 'fc_w', (self.fin, EMBED), self.fin * EMBED))
-        big.append(('classifier/fc_classifier/weights', 'cls_w', (EMBED, self.num_classes), EMBED * self.cpad))
+        # K centres per class: K planes of cpad columns, centre k of class j at column k * cpad + j; the reference layout packs them
+        K = self.sub_centers
+        big.append(('classifier/fc_classifier/weights', 'cls_w', (EMBED, K * self.num_classes), EMBED * K * self.cpad))
         self.variables = OrderedDict()
         off = 0
         for nm, kind, shape, size in small + big:
@@ -152,8 +155,9 @@ class SphereNet(Network):
         lim = (6.0 / (self.fin + EMBED)) ** 0.5
         w = (torch.rand(self.fin, EMBED, generator=g) * 2 - 1) * lim
         self.view(self.name + '/fully_connected/weights').copy_(w.reshape(-1))
-        wc = torch.zeros(EMBED, self.cpad)
-        wc[:, :self.num_classes] = torch.randn(EMBED, self.num_classes, generator=g) * 0.001
+        K = self.sub_centers                              # every plane drawn on its own: identical planes would tie on every sample
+        wc = torch.zeros(EMBED, K, self.cpad)
+        wc[:, :, :self.num_classes] = (torch.randn(EMBED, K * self.num_classes, generator=g) * 0.001).reshape(EMBED, K, self.num_classes)
         self.view('classifier/fc_classifier/weights').copy_(wc.reshape(-1))
 
     # ---- reference-layout import / export ----------------------------------------------
@@ -173,7 +177,7 @@ class SphereNet(Network):
         v = self.variables[name]
         t = self.view(name, arena)
         if v.kind == 'cls_w':
-            return t.reshape(EMBED, self.cpad)[:, :self.num_classes].clone()
+            return t.reshape(EMBED, self.sub_centers, self.cpad)[:, :, :self.num_classes].reshape(v.ref_shape).clone()
         if v.kind == 'fc_w':
             return self._fc_perm(t.reshape(self.fin, EMBED), False).contiguous()
         return t.reshape(v.ref_shape).clone()
@@ -187,8 +191,8 @@ class SphereNet(Network):
         t = torch.as_tensor(value, dtype=torch.float32).to(self.device)
         assert tuple(t.shape) == v.ref_shape, (name, tuple(t.shape), v.ref_shape)
         if v.kind == 'cls_w':
-            buf = torch.zeros(EMBED, self.cpad, device=self.device)
-            buf[:, :self.num_classes] = t
+            buf = torch.zeros(EMBED, self.sub_centers, self.cpad, device=self.device)
+            buf[:, :, :self.num_classes] = t.reshape(EMBED, self.sub_centers, self.num_classes)
             t = buf
         elif v.kind == 'fc_w':
             t = self._fc_perm(t, True)
@@ -227,7 +231,7 @@ class SphereNet(Network):
         hw = self._head_width()                           # cpad; the sampled-class head: its Spad columns
         self.s_raw = torch.empty(n, hw, **f32)
         self.G = torch.empty(n, hw, **f32)
-        self.logits_buf = torch.empty(n, hw, **f32) if self.head == 'asoftmax' or self.head in NORMALISED_HEADS else self.s_raw
+        self.logits_buf = torch.empty(n, hw // self.sub_centers, **f32) if self.head == 'asoftmax' or self.head in NORMALISED_HEADS else self.s_raw
         self.loss_rows = torch.empty(n, **f32)
         self.xn = torch.empty(n, **f32)
         self.wn = torch.empty(hw, **f32)
@@ -275,7 +279,7 @@ class SphereNet(Network):
 
     def _head_width(self):
         """columns of the head's [n, .] buffers (s_raw, G, logits_buf)"""
-        return self.cpad
+        return self.sub_centers * self.cpad
 
     def _alloc_head(self, n):
         """further head buffers of a subclass, sized with the activations"""
@@ -433,7 +437,7 @@ class SphereNet(Network):
 
     def _classifier_raw(self, n):
         W, _, _, ld = self._head_cols()
-        _lib.call('fte_gemm_nn', self.emb, W, None, self.s_raw, n, ld, EMBED, self.ws, self.ws_bytes, _stream())
+        _lib.call('fte_gemm_nn', self.emb, W, None, self.s_raw, n, self.sub_centers * ld, EMBED, self.ws, self.ws_bytes, _stream())
 
     def _ensure_built(self, images, num_classes):
         if not self.built:
@@ -497,6 +501,7 @@ class SphereNet(Network):
     def _head_backward(self, n, st):
         """the classifier's two products on the columns of _head_cols; the margin heads add the norm corrections (heads.py)"""
         W, dW, _, ld = self._head_cols()
+        ld *= self.sub_centers                            # the products run over every plane
         norm = self.head != 'softmax'
         heads.classifier_dw(self, self.emb, W, dW, n, EMBED, ld, self.ws, self.ws_bytes, st, norm)
         self._scatter_dw(st)
@@ -779,8 +784,9 @@ class SphereNetAdditiveMargin(SphereNetMargin):
     not applied under no_grad.  The variables and their names are SphereNet's."""
 
     def __init__(self, weight_decay=0.0005, data_format='NCHW', name='SphereNet', seed=0, head='arcface',
-                 scale=None, margin=None, margin_cos=None, sample_rate=None, sample_seed=0):
+                 scale=None, margin=None, margin_cos=None, sample_rate=None, sample_seed=0, sub_centers=1):
         super(SphereNetAdditiveMargin, self).__init__(weight_decay, data_format, name, seed)
+        self.sub_centers = heads.check_sub_centers(sub_centers, head, sample_rate, name)
         self.margin_scale, self.margin, self.margin_cos = margin_params(head, scale, margin, margin_cos)
         self.head = head
         # the sampled-class head under data parallelism and its compact classifier update (DESIGN.md 4.13); the dense head ignores both
@@ -797,6 +803,7 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         other classes with the smallest hashes under (seed, global_step); None or 1: the dense head.  The variables, the dense
         [D, cpad] classifier gradient (0.0 in the unsampled columns), the optimizer and the checkpoints stay as they are."""
         sample_size(1, rate)                              # validates the rate
+        heads.check_sub_centers(self.sub_centers, self.head, rate, self.name)
         self.sample_rate = None if rate is None or float(rate) >= 1.0 else float(rate)
         self.sample_seed = int(seed)
         self._act_n = None                                # the head buffers change width
@@ -807,7 +814,7 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         return sample_size(self.num_classes, self.sample_rate)
 
     def _head_width(self):
-        return self.cpad if self.sample_rate is None else (self.sample_size + 63) // 64 * 64
+        return self.sub_centers * self.cpad if self.sample_rate is None else (self.sample_size + 63) // 64 * 64
 
     def _alloc_head(self, n):
         if self.sample_rate is None:

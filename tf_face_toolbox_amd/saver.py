@@ -13,7 +13,8 @@ What is kept:
     latest one (tf.train.get_checkpoint_state, train.py:207); at most 20 are kept (train.py:188);
   * finetuning restores `pretrained_param` (backbone variables) only (train.py:191-193,211-213).
 The container is a torch.save dict of reference-layout tensors (HWIO conv weights, [in,out] dense
-weights), so a checkpoint is portable across data_format and classifier padding."""
+weights), so a checkpoint is portable across data_format and classifier padding.  A classifier of K centres per class
+(sub-center ArcFace) is saved as [D, K * C], column k * C + j = centre k of class j; K = 1 is the file it always was."""
 import os
 import re
 
@@ -81,6 +82,12 @@ def restore(model, path, optimizer=None, only=None):
     for name in names:
         if name not in state['variables']:
             raise KeyError('%s not found in checkpoint %s' % (name, path))
+        var = getattr(model, 'variables', {}).get(name)
+        if var is not None and var.kind == 'cls_w' and tuple(state['variables'][name].shape) != var.ref_shape:
+            # a classifier of K centres per class is [D, K * C], planes packed: a file of another width is another K (or class count)
+            K, C = int(getattr(model, 'sub_centers', 1)), model.num_classes
+            raise ValueError('%s in %s has %d columns, the net expects sub_centers * num_classes = %d * %d = %d'
+                             % (name, path, state['variables'][name].shape[-1], K, C, K * C))
         model.set_variable(name, state['variables'][name])
     if optimizer is not None and only is None and state['slots']:
         optimizer._ensure()

@@ -82,6 +82,10 @@ def build_parser():
                         help='--sample_rate < 1: 1 = the classifier and its optimizer slots are updated straight from the compact gradient '
                              'of the sampled columns (one fused kernel, the same values bit for bit); the dense classifier gradient is '
                              'never written.')
+    parser.add_argument('--sub_centers', type=int, default=1,
+                        help='SphereNet-ArcFace / -CosFace, ResNet-50-arcface / -cosface: K centres per class (sub-center ArcFace), 1..8; the class '
+                             'logit is the max cosine over its centres.  1 (default) = one centre, the head as it always was.  Not with '
+                             '--sample_rate < 1.  subcenter_clean.py reduces a trained K-centre model to K = 1 and cleans the list.')
     return parser
 
 
@@ -97,6 +101,15 @@ def sample_flags_check(FLAGS):
                          % (FLAGS.sample_rate, ' / '.join(SAMPLED_NETS), FLAGS.net_name))
     if FLAGS.sample_rate < 1.0 and FLAGS.num_gpus > 1 and not getattr(FLAGS, 'sync_sample', 0):
         raise SystemExit('--sample_rate %g: the sampled-class head runs on one GPU only (--num_gpus %d)' % (FLAGS.sample_rate, FLAGS.num_gpus))
+
+
+def sub_centers_flags_check(FLAGS):
+    """--sub_centers: refuse what the K-centre head does not do, before anything is built"""
+    from tf_face_toolbox_amd.nets.net_base import sub_centers_check
+    try:
+        sub_centers_check(FLAGS.net_name, FLAGS.sub_centers, FLAGS.sample_rate)
+    except ValueError as e:
+        raise SystemExit('--sub_centers %d: %s' % (FLAGS.sub_centers, e))
 
 
 def FLAGS_assertion(FLAGS):
@@ -205,7 +218,7 @@ def train(FLAGS):
                               num_per_class=FLAGS.num_per_class, device=device, seed=1234, rank=rank, world_size=world)
     try:
         batches_per_epoch = inputs['num_examples'] // batch_size + 1                                  # train.py:172
-        network = net_select(FLAGS.net_name, FLAGS.data_format, FLAGS.weight_decay)                  # train.py:174
+        network = net_select(FLAGS.net_name, FLAGS.data_format, FLAGS.weight_decay, sub_centers=FLAGS.sub_centers)      # train.py:174
         margins = (FLAGS.margin_scale, FLAGS.margin, FLAGS.margin_cos)
         if getattr(network, 'margin_scale', None) is not None and margins != (None, None, None):
             network.set_margin(*margins)
@@ -305,6 +318,7 @@ def main(argv=None):
     FLAGS = build_parser().parse_args(argv)
     FLAGS_assertion(FLAGS)
     sample_flags_check(FLAGS)
+    sub_centers_flags_check(FLAGS)
     os.makedirs(os.path.join(FLAGS.train_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     os.makedirs(os.path.join(FLAGS.model_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     train(FLAGS)
