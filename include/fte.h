@@ -930,6 +930,43 @@ int fte_pfc_momentum_update_cols(float* W, float* acc, const float* dWs, const i
 int fte_pfc_adam_update_cols(float* W, float* m, float* v, const float* dWs, const int32_t* inverse, int D, int C, int cpad, int S,
                              int Spad, float lr, float b1, float b2, float eps, float wd, float gscale, int t, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Clustering: link rules over kNN lists and connected components (cluster.py, verification.py).
+ * Grouping the embeddings of an unlabelled or badly labelled list into identities.  The input is the neighbour lists exactly as
+ * fte_topk_search writes them for a leave-one-out search of a set against itself: scores [n, k] fp32 and index [n, k] int32 with
+ * 1 <= k <= 64, n * k < 2^29, index values global row numbers.  A slot (a, t) is VALID iff 0 <= index[a,t] < n and
+ * index[a,t] != a; every other slot is a hole (the (-inf, -1) tails, garbage, self): a hole never links, is never a member of a
+ * list, and is never followed, so bad indices cannot cause an out-of-bounds access.  Both link rules write a keep mask
+ * uint8 [n, k] (1 or 0 in every slot); fte_components turns either mask into labels.  Everything after the fp32 scores is
+ * integer logic: the results are exact and do not depend on execution order.  Like the evaluation entry points these neither
+ * allocate nor synchronise, and no host loop waits on the device.
+ * FTE_EINVAL (all three): a NULL pointer, n < 1, k outside 1..64, n * k >= 2^29.
+ * ------------------------------------------------------------------------- */
+
+/* Cosine threshold on the (mutual) kNN graph.  With b = index[a,t]: keep[a,t] = 1 iff the slot is valid, scores[a,t] >= min_score,
+ * and, when mutual != 0, some slot u of row b has index[b,u] == a and scores[b,u] >= min_score.  A NaN score compares false. */
+int fte_knn_links_threshold(const float* scores, const int32_t* index, int n, int k, float min_score, int mutual, uint8_t* keep,
+                            void* stream);
+/* Approximate rank-order links (Otto, Wang, Jain, "Clustering Millions of Faces by Identity", TPAMI 2018).  L_a is the list
+ * (a, index[a,0], ..., index[a,k-1]) at positions 0..k; its members are a and its valid entries (an entry repeated in a row
+ * counts at its first position only; fte_topk_search never writes one).
+ *     r(a,b) = 1 + the smallest t with index[a,t] == b, or k + 1 if there is none;
+ *     m(a,b) = the number of positions p in 0..min(r(a,b), k) of L_a whose entry is a member of L_a and not a member of L_b.
+ * With b = index[a,t]: keep[a,t] = 1 iff the slot is valid, scores[a,t] >= min_score (min_score = -inf turns the floor off), and
+ *     (float)(m(a,b) + m(b,a)) < theta * (float)min(r(a,b), r(b,a))        (exactly this fp32 expression: one rounded product)
+ * The distance is symmetric in (a, b): a pair listed from both sides gets the same answer from both.
+ * FTE_EINVAL also: theta not finite or <= 0. */
+int fte_knn_links_rank_order(const float* scores, const int32_t* index, int n, int k, float theta, float min_score, uint8_t* keep,
+                             void* stream);
+/* Connected components of the graph whose edges are the slots with keep[a,t] != 0 that are valid (a -- index[a,t]; a link from
+ * either side is enough).  label[i] = the smallest row number of i's component, int32 [n].  parent: int32 [n] workspace, fully
+ * rewritten by the call.  A lock-free union-find in three launches on the stream (init, link, flatten): links hook the larger
+ * root under the smaller with a compare-and-swap and retry from the new roots when the swap loses, so the root of a tree is always
+ * its smallest member; no thread waits for another's progress and nothing is driven from the host.  Two calls write identical
+ * bytes. */
+int fte_components(const int32_t* index, const uint8_t* keep, int n, int k, int32_t* parent /* workspace [n] */, int32_t* label /* [n] */,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,9 @@ _SIGS = {
     'fte_pfc_scatter_cols': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_pfc_momentum_update_cols': (c_int, [_P] * 4 + [c_int] * 5 + [c_float] * 4 + [_P]),
     'fte_pfc_adam_update_cols': (c_int, [_P] * 5 + [c_int] * 5 + [c_float] * 6 + [c_int, _P]),
+    'fte_knn_links_threshold': (c_int, [_P] * 2 + [c_int] * 2 + [c_float, c_int, _P, _P]),
+    'fte_knn_links_rank_order': (c_int, [_P] * 2 + [c_int] * 2 + [c_float] * 2 + [_P, _P]),
+    'fte_components': (c_int, [_P] * 2 + [c_int] * 2 + [_P] * 3),
     'fte_dwconv3x3_fwd': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_dgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P]),
     'fte_dwconv3x3_wgrad': (c_int, [_P] * 3 + [c_int] * 5 + [_P, c_size_t, _P]),

@@ -18,6 +18,7 @@
 #include "wino.h"
 #include "search.h"
 #include "partial_fc.h"
+#include "cluster.h"
 
 namespace {
 
@@ -1989,5 +1990,23 @@ int fte_pfc_adam_update_cols(float* W, float* m, float* v, const float* dWs, con
         return FTE_EINVAL;
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t));      // fte_adam_update's
     return rc(p_adam_update_cols(W, m, v, dWs, inverse, D, C, cpad, S, Spad, (float)lr_t, b1, b2, eps, wd, gscale, (hipStream_t)stream));
+}
+
+// ---- Clustering (cluster.hip) ----
+static inline bool knn_lists_ok(int n, int k) { return n >= 1 && k >= 1 && k <= 64 && (long)n * k < (1L << 29); }
+int fte_knn_links_threshold(const float* scores, const int32_t* index, int n, int k, float min_score, int mutual, uint8_t* keep,
+                            void* stream) {
+    if (!scores || !index || !keep || !knn_lists_ok(n, k)) return FTE_EINVAL;
+    return rc(c_links_threshold(scores, index, n, k, min_score, mutual != 0, keep, (hipStream_t)stream));
+}
+int fte_knn_links_rank_order(const float* scores, const int32_t* index, int n, int k, float theta, float min_score, uint8_t* keep,
+                             void* stream) {
+    if (!scores || !index || !keep || !knn_lists_ok(n, k) || !(theta > 0.f && theta <= 3.402823466e38f))
+        return FTE_EINVAL;                                   // (a NaN or infinite theta fails the comparison too)
+    return rc(c_links_rank_order(scores, index, n, k, theta, min_score, keep, (hipStream_t)stream));
+}
+int fte_components(const int32_t* index, const uint8_t* keep, int n, int k, int32_t* parent, int32_t* label, void* stream) {
+    if (!index || !keep || !parent || !label || !knn_lists_ok(n, k)) return FTE_EINVAL;
+    return rc(c_components(index, keep, n, k, parent, label, (hipStream_t)stream));
 }
 }  // extern "C"
