@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import ops
+import wino_map
 
 pytestmark = pytest.mark.gpu
 
@@ -16,16 +17,18 @@ if torch.cuda.is_available():
 
 DIRECT, WINOGRAD, AUTO = 0, 1, 2
 
+# On 256 CUs every case but the last is ONE round of at most 128 tiles and so runs the HALF-tile kernel wino_mm_kernel<e,1> alone (the launch
+# records say so, and the tests below hold them to tests/wino_map.py's list); the whole-tile kernel's shapes are tests/test_gpu_wino_edges.py's.
 CASES = [
     # n, h, w, cin, cout
-    (2, 14, 14, 256, 256),       # stage 3: 7x7 tiles per image, ragged last row block
-    (3, 9, 7, 64, 128),          # odd, non-square: half-outside tiles on both edges, cin != cout
-    (5, 7, 7, 512, 512),         # stage 4: 7x7 padded to 4x4 tiles
-    (1, 28, 28, 128, 128),       # stage 2
-    (2, 56, 56, 64, 64),         # stage 1: one column block
-    (40, 14, 14, 256, 256),      # 31 row blocks: every XCD class, several tiles per filter-gradient share
+    (2, 14, 14, 256, 256),       # stage 3: 7x7 tiles per image, ragged last row block (8 tiles: half tiles)
+    (3, 9, 7, 64, 128),          # odd, non-square: half-outside tiles on both edges, cin != cout (2 tiles: half tiles)
+    (5, 7, 7, 512, 512),         # stage 4: 7x7 padded to 4x4 tiles (16 tiles: half tiles)
+    (1, 28, 28, 128, 128),       # stage 2 (8 tiles: half tiles)
+    (2, 56, 56, 64, 64),         # stage 1: one column block (25 tiles: half tiles)
+    (40, 14, 14, 256, 256),      # 31 row blocks: every XCD class, several tiles per filter-gradient share (124 tiles: STILL half tiles)
     (64, 7, 7, 512, 512),        # the 8-GPU shard of stage 4: 128 tiles = 256 half tiles, no whole round
-    (84, 14, 14, 256, 256),      # 260 tiles: a whole round + a second round of 4 tiles (resident blocks with 2 and with 1 tile)
+    (84, 14, 14, 256, 256),      # 260 tiles, WHOLE tiles: a whole round + a second round of 4 tiles (resident blocks with 2 and with 1 tile)
 ]
 
 
@@ -46,6 +49,12 @@ def _symbols(fn):
     return [r[5] for r in _lib.prof_records(shapes=True)]
 
 
+def _planned(n, h, w, N, epi):
+    """the launches csrc/wino.hip wino_mm makes for N output channels on THIS device (tests/wino_map.py)"""
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    return wino_map.mm_plan(wino_map.geom(n, h, w)[1], N, cus, epi)['symbols']
+
+
 @pytest.mark.parametrize('n,h,w,cin,cout', CASES)
 def test_wino_fwd(winograd, n, h, w, cin, cout):
     r = np.random.default_rng(21)
@@ -58,7 +67,7 @@ def test_wino_fwd(winograd, n, h, w, cin, cout):
     wsb, nb = ws(query('fte_conv3x3_fwd_ws_bytes', n, h, w, cin, cout, 1))
     args = (dev(x), dev(wt), dev(b), dev(al), dev(res), z, y, n, h, w, cin, cout, 1, wsb, nb, stream())
     syms = _symbols(lambda: call('fte_conv3x3_fwd', *args))
-    assert syms and all(s_.startswith('wino_mm_kernel<0,') for s_ in syms), syms
+    assert syms == _planned(n, h, w, cout, 0), (syms, _planned(n, h, w, cout, 0))
     check_maxabs(host(z), z_ref, what='z'); check_maxabs(host(y), y_ref, what='y')
     y2 = torch.full(z_ref.shape, 7.0, device='cuda')
     call('fte_conv3x3_fwd', dev(x), dev(wt), None, None, None, None, y2, n, h, w, cin, cout, 1, wsb, nb, stream())
@@ -85,7 +94,7 @@ def test_wino_dgrad_with_prelu_backward(winograd, n, h, w, cin, cout):
     wsb, nb = ws(query('fte_conv3x3_dgrad_ws_bytes', n, h, w, cin, cout, 1))
     args = (dev(dz), dev(wt), dev(addin), dev(zprev), dev(alp), raw, dzp, da, db, n, h, w, cin, cout, 1, wsb, nb, stream())
     syms = _symbols(lambda: call('fte_conv3x3_dgrad', *args))
-    assert syms and all(s_.startswith('wino_mm_kernel<1,') for s_ in syms), syms
+    assert syms == _planned(n, h, w, cin, 1), (syms, _planned(n, h, w, cin, 1))
     check_maxabs(host(raw), g_ref, what='raw'); check_maxabs(host(dzp), dzprev_ref, what='dzprev')
     check_rell2(host(da), dalpha_ref, what='dalpha'); check_rell2(host(db), dbias_ref, what='dbias')
     dzp2 = torch.full(x.shape, 7.0, device='cuda')
@@ -180,8 +189,8 @@ def test_kept_v_pack_feeds_the_filter_gradient(winograd):
 @pytest.mark.parametrize('n,h,w,c', [(64, 7, 7, 512), (2, 14, 14, 256), (4, 8, 8, 128), (2, 56, 56, 64), (40, 14, 14, 256)])
 def test_products_are_stable_over_many_launches(winograd, n, h, w, c):
     """300 launches of the forward and the data-gradient product on the same operands while another stream keeps the memory system busy
-    (as the filter gradients do in the backward walk): every result equal to the first, bit for bit (half-tile kernel: all cases but
-    the 40-image one).  A late zero-fill of an out-of-range LDS-DMA slot landing in the epilogue's exchange buffer showed as a wrong
+    (as the filter gradients do in the backward walk): every result equal to the first, bit for bit.  On 256 CUs ALL five cases -- the 40-image
+    one too: 124 tiles in one round -- run the half-tile kernel alone.  A late zero-fill of an out-of-range LDS-DMA slot landing in the epilogue's exchange buffer showed as a wrong
     output of the half-tile kernel once in a few training steps."""
     r = np.random.default_rng(27)
     x = dev(r.standard_normal((n, h, w, c))); wt = dev(r.standard_normal((3, 3, c, c)) * 0.05)
