@@ -266,6 +266,30 @@ int fte_bn_train_stats(const float* z, const float* gamma, const float* beta, fl
                        void* ws, size_t ws_bytes, void* stream);
 int fte_bn_infer_coef(const float* gamma, const float* beta, const float* moving_mean, const float* moving_var,
                       float* scale, float* shift, int c, float eps, void* stream);
+/* ---------------------------------------------------------------------------
+ * BN + PReLU: batch norm followed by a per-channel PReLU in one pass (the IResNet block, nets/iresnet.py).  fp32 tensors only,
+ * z / y / dy / dz are [rows, c], c % 4 == 0; alpha / dalpha are [c].  With u = fma(z, scale[c], shift[c]) -- the expression
+ * fte_bn_apply evaluates, scale / shift from fte_bn_train_stats, fte_conv2d_bn_fwd or fte_bn_infer_coef:
+ *   fte_bn_prelu_apply      y = u > 0 ? u : alpha[c] * u  (the PReLU of the conv epilogues; the product is rounded on its own, so
+ *                           alpha = 1 gives the bytes of fte_bn_apply(relu = 0) and alpha = 0 the values of fte_bn_apply(relu = 1)).
+ *   fte_bn_prelu_infer_fwd  fte_bn_infer_coef (scale / shift from the moving statistics, written for the caller) followed by
+ *                           fte_bn_prelu_apply: two launches.
+ *   fte_bn_prelu_train_bwd  the sign of u is recomputed from z exactly as the forward evaluated it (the activated tensor is not read):
+ *                           g = dy * (u > 0 ? 1 : alpha[c]),  dalpha[c] = sum_{u <= 0} dy * u,  dgamma = sum g * xhat,  dbeta = sum g,
+ *                           dz = gamma * rstd * (g - dbeta / rows - xhat * dgamma / rows).
+ *                           Two passes over (dy, z): a split reduce with three sums per channel, then the apply.  The sums are fp32,
+ *                           merged in a fixed order without float atomics: two calls write identical bytes.
+ *                           ws >= fte_bn_prelu_ws_bytes(c).
+ * FTE_EINVAL: a null pointer, rows < 1, c < 4 or c % 4, ws NULL or shorter than fte_bn_prelu_ws_bytes(c).  Nothing is launched then.
+ * ------------------------------------------------------------------------- */
+size_t fte_bn_prelu_ws_bytes(int c);
+int fte_bn_prelu_apply(const float* z, const float* scale, const float* shift, const float* alpha, float* y, long rows, int c,
+                       void* stream);
+int fte_bn_prelu_infer_fwd(const float* z, const float* gamma, const float* beta, const float* moving_mean, const float* moving_var,
+                           const float* alpha, float* y, float* scale, float* shift, long rows, int c, float eps, void* stream);
+int fte_bn_prelu_train_bwd(const float* dy, const float* z, const float* gamma, const float* mean, const float* rstd,
+                           const float* scale, const float* shift, const float* alpha, float* dz, float* dgamma, float* dbeta,
+                           float* dalpha, long rows, int c, void* ws, size_t ws_bytes, void* stream);
 /* g = dy * (y > 0)  (tf.nn.relu gradient, materialised where a residual shortcut needs it) */
 int fte_relu_bwd(const float* dy, const float* y, float* g, long n, void* stream);
 

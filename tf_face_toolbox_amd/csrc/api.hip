@@ -19,6 +19,7 @@
 #include "search.h"
 #include "partial_fc.h"
 #include "cluster.h"
+#include "iresnet.h"
 
 namespace {
 
@@ -1370,6 +1371,28 @@ int fte_bn_infer_coef(const float* gamma, const float* beta, const float* moving
                       float* scale, float* shift, int c, float eps, void* stream) {
     if (!gamma || !beta || !moving_mean || !moving_var || !scale || !shift || c <= 0) return FTE_EINVAL;
     return rc(l_bn_infer_coef(gamma, beta, moving_mean, moving_var, eps, c, scale, shift, (hipStream_t)stream));
+}
+// BN + PReLU (iresnet.hip)
+size_t fte_bn_prelu_ws_bytes(int c) { return c > 0 ? l_bn_prelu_ws_floats(c) * sizeof(float) : 0; }
+int fte_bn_prelu_apply(const float* z, const float* scale, const float* shift, const float* alpha, float* y, long rows, int c,
+                       void* stream) {
+    if (!z || !scale || !shift || !alpha || !y || rows <= 0 || c < 4 || c % 4) return FTE_EINVAL;
+    return rc(l_bn_prelu_apply(z, scale, shift, alpha, y, rows, c, (hipStream_t)stream));
+}
+int fte_bn_prelu_infer_fwd(const float* z, const float* gamma, const float* beta, const float* moving_mean, const float* moving_var,
+                           const float* alpha, float* y, float* scale, float* shift, long rows, int c, float eps, void* stream) {
+    if (!z || !gamma || !beta || !moving_mean || !moving_var || !alpha || !y || !scale || !shift || rows <= 0 || c < 4 || c % 4) return FTE_EINVAL;
+    hipError_t e = l_bn_infer_coef(gamma, beta, moving_mean, moving_var, eps, c, scale, shift, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    return rc(l_bn_prelu_apply(z, scale, shift, alpha, y, rows, c, (hipStream_t)stream));
+}
+int fte_bn_prelu_train_bwd(const float* dy, const float* z, const float* gamma, const float* mean, const float* rstd,
+                           const float* scale, const float* shift, const float* alpha, float* dz, float* dgamma, float* dbeta,
+                           float* dalpha, long rows, int c, void* ws, size_t ws_bytes, void* stream) {
+    if (!dy || !z || !gamma || !mean || !rstd || !scale || !shift || !alpha || !dz || !dgamma || !dbeta || !dalpha || rows <= 0 ||
+        c < 4 || c % 4) return FTE_EINVAL;
+    if (!ws || ws_bytes < fte_bn_prelu_ws_bytes(c)) return FTE_EINVAL;      // (fte.h: one refusal code for this block)
+    return rc(l_bn_prelu_bwd(dy, z, gamma, mean, rstd, scale, shift, alpha, dz, dgamma, dbeta, dalpha, rows, c, (float*)ws, (hipStream_t)stream));
 }
 int fte_relu_bwd(const float* dy, const float* y, float* g, long n, void* stream) {
     if (!dy || !y || !g || n <= 0 || n % 4) return FTE_EINVAL;

@@ -41,6 +41,13 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _prod(shape):
+    n = 1
+    for d in shape:
+        n *= d
+    return n
+
+
 class _Activations(dict):
     """name -> stored activation.  A BN output that was folded into the channel gather that consumes it is never stored;
     asking for it (tests, debugging) recomputes it from z and the kept scale / shift."""
@@ -89,6 +96,7 @@ class GraphNet(Network):
 
     head = 'softmax'
     channel_pad = 1
+    bn_eps, bn_decay = BN_EPS, BN_DECAY      # per net: IResNet sets 1e-5 / 0.9; they reach every BN call of the walk
 
     def _pc(self, c):
         p = self.channel_pad
@@ -165,8 +173,8 @@ class GraphNet(Network):
                             if o2[0] == 'bn' and o2[2] == op[1]:
                                 self.narrow.update([o2[3] + '/gamma', o2[3] + '/beta'])
         self._infer_shapes()
-        small = [(n, s, k) for n, s, k in spec if k in ('gamma', 'beta', 'bias')]
-        convs = [(n, s, k) for n, s, k in spec if k in ('conv_w', 'gconv_w', 'fc_w', 'dw_w')]
+        small = [(n, s, k) for n, s, k in spec if k in ('gamma', 'beta', 'bias', 'alpha')]
+        convs = [(n, s, k) for n, s, k in spec if k in ('conv_w', 'gconv_w', 'fc_w', 'dw_w', 'embed_w')]
         cls = [(n, s, k) for n, s, k in spec if k == 'cls_w']
         self.variables = OrderedDict()
         off = 0
@@ -219,9 +227,9 @@ class GraphNet(Network):
             return (3, 3, pc(shape[2]))
         if kind == 'fc_w':
             return (pc(shape[-2]), pc(shape[-1]))
-        if kind in ('gamma', 'beta', 'bias'):
+        if kind in ('gamma', 'beta', 'bias', 'alpha'):
             return (pc(shape[0]),)
-        assert self.channel_pad == 1 or kind != 'gconv_w'
+        assert self.channel_pad == 1 or kind not in ('gconv_w', 'embed_w')
         return tuple(shape)
 
     def view(self, name, arena=None):
@@ -258,8 +266,13 @@ class GraphNet(Network):
                 self.set_variable(n, (torch.rand(v.ref_shape, generator=g) * 2 - 1) * lim)
             elif v.kind == 'cls_w':
                 self.set_variable(n, torch.randn(v.ref_shape, generator=g) * 0.001)
+            elif v.kind == 'embed_w':
+                lim = (6.0 / (v.ref_shape[0] + v.ref_shape[1])) ** 0.5
+                self.set_variable(n, (torch.rand(v.ref_shape, generator=g) * 2 - 1) * lim)
             elif v.kind == 'gamma':
                 self.set_variable(n, torch.ones(v.ref_shape))
+            elif v.kind == 'alpha':                      # nets/sphere.py:34
+                self.set_variable(n, torch.full(v.ref_shape, 0.25))
 
     def get_variable(self, name, arena=None):
         if name in self.state:
@@ -279,8 +292,10 @@ class GraphNet(Network):
             return t[:, :, :ref[2]].reshape(ref).clone()
         if v.kind == 'fc_w':
             return t[:ref[-2], :ref[-1]].reshape(ref).clone()
-        if v.kind in ('gamma', 'beta', 'bias'):
+        if v.kind in ('gamma', 'beta', 'bias', 'alpha'):
             return t[:ref[0]].clone()
+        if v.kind == 'embed_w':
+            return self._embed_perm(name, t, False).contiguous()
         return t.reshape(ref).clone()
 
     def set_variable(self, name, value, arena=None):
@@ -308,8 +323,10 @@ class GraphNet(Network):
             buf[:, :, :ref[2]] = t.reshape(3, 3, ref[2])
         elif v.kind == 'fc_w':
             buf[:ref[-2], :ref[-1]] = t.reshape(ref[-2], ref[-1])
-        elif v.kind in ('gamma', 'beta', 'bias'):
+        elif v.kind in ('gamma', 'beta', 'bias', 'alpha'):
             buf[:ref[0]] = t
+        elif v.kind == 'embed_w':
+            buf = self._embed_perm(name, t, True)
         else:
             buf = t
         self.view(name, arena).copy_(buf.reshape(-1))
@@ -318,6 +335,17 @@ class GraphNet(Network):
         for k, val in params.items():
             self.set_variable(k, val)
 
+    def _embed_perm(self, name, t, to_internal):
+        """Rows of an FC that flattens a feature map: the reference order is the flatten order of data_format (SphereNet's fc,
+        nets/sphere.py _fc_perm); the arena keeps NHWC order, the order the activations are stored in."""
+        h, w, c = self.embed_in[name]
+        d = t.shape[-1]
+        if self.data_format == 'NHWC':
+            return t.reshape(h * w * c, d)
+        if to_internal:
+            return t.reshape(c, h, w, d).permute(1, 2, 0, 3).reshape(h * w * c, d)
+        return t.reshape(h, w, c, d).permute(2, 0, 1, 3).reshape(h * w * c, d)
+
     # ---- static analysis ----------------------------------------------------------------------------
     def _infer_shapes(self):
         """self.shapes: stored (channel-padded) shape of every tensor; self.real_c: its true channel count."""
@@ -325,6 +353,7 @@ class GraphNet(Network):
         shp = {'images': (h, w, c)}
         real = {'images': c}
         pc = self._pc
+        self.embed_in = {}                               # 'embed_w' variable -> (h, w, c) of the feature map its FC flattens
 
         def put(name, hh, ww, cc):
             real[name] = cc
@@ -341,7 +370,7 @@ class GraphNet(Network):
             elif kind in ('gconv', 'dwconv'):
                 ih, iw, _ = shp[op[2]]
                 put(out, same_pads(ih, 3, op[4])[0], same_pads(iw, 3, op[4])[0], real[op[2]])
-            elif kind in ('bn', 'relu', 'dropout', 'se', 'add'):
+            elif kind in ('bn', 'relu', 'dropout', 'se', 'add', 'prelu'):
                 shp[out] = shp[op[2]]
                 real[out] = real[op[2]]
             elif kind == 'maxpool':
@@ -351,6 +380,13 @@ class GraphNet(Network):
             elif kind == 'gap':
                 shp[out] = (shp[op[2]][2],)
                 real[out] = real[op[2]]
+            elif kind == 'fc' and self.spec[op[3]][1] == 'embed_w':      # dense layer on the flattened [n, h w c] map (or on [n, c])
+                fin, d = self.spec[op[3]][0]
+                src = shp[op[2]]
+                assert self.channel_pad == 1 and fin == _prod(src) and d % 64 == 0 and fin % 32 == 0, (op, src, fin, d)
+                self.embed_in[op[3]] = src if len(src) == 3 else (1, 1, src[0])
+                shp[out] = (d,)
+                real[out] = d
             elif kind == 'fc':
                 shp[out] = (self.sub_centers * self.cpad,)
                 real[out] = self.num_classes
@@ -442,6 +478,10 @@ class GraphNet(Network):
                 if len(u) == 1 and g[u[0]][0] == 'relu':
                     relu, final = 1, g[u[0]][1]
                     skip.add(u[0])
+                elif len(u) == 1 and g[u[0]][0] == 'prelu':      # bn -> prelu: one plan op (fte_bn_prelu_apply / _train_bwd)
+                    skip.add(u[0])
+                    plan.append(('bnprelu', g[u[0]][1], op[2], op[3], g[u[0]][3]))
+                    continue
                 elif len(u) == 1 and g[u[0]][0] == 'add':
                     add = g[u[0]]
                     other = add[3] if add[2] == out else add[2]
@@ -449,7 +489,15 @@ class GraphNet(Network):
                     if len(u2) == 1 and g[u2[0]][0] == 'relu' and self._defined_before(other, i):
                         res, relu, final = other, 1, g[u2[0]][1]
                         skip.update([u[0], u2[0]])
+                    elif not any(g[k][0] == 'relu' for k in u2) and other != out and self._defined_before(other, i):
+                        # bn -> add with NO activation (the IResNet block's last BN plus shortcut): fte_bn_apply(res, relu = 0);
+                        # backward: the gradient goes unmasked into the BN backward and unchanged to the shortcut
+                        res, final = other, add[1]
+                        skip.add(u[0])
                 plan.append(('bn', final, op[2], op[3], res, relu))
+            elif op[0] == 'prelu':
+                raise ValueError('%s: prelu %r does not directly follow a bn that feeds nothing else (its input is %r): only the fused '
+                                 'bn -> prelu pair is implemented' % (self.name, op[1], op[2]))
             elif op[0] == 'add':
                 u = users.get(op[1], [])
                 assert len(u) == 1 and g[u[0]][0] == 'relu', 'a bare add is always followed by a ReLU in these nets'
@@ -497,14 +545,15 @@ class GraphNet(Network):
         self.fuse_bwd_gconv = os.environ.get('FTE_BN_FUSE_GBWD', '0') == '1'
         if os.environ.get('FTE_BN_FUSE', '1') != '0':
             producer = {op[1]: j for j, op in enumerate(plan) if op[0] in ('conv', 'gconv')}
+            prelu_net = any(op[0] == 'bnprelu' for op in plan)
             for j, op in enumerate(plan):
-                if op[0] not in ('bn', 'bnstats', 'seblock'):
+                if op[0] not in ('bn', 'bnstats', 'seblock', 'bnprelu'):
                     continue
                 i = producer.get(op[2])
                 if i is not None and pusers.get(op[2], []) == [j]:
                     self.fuse_fwd[i] = j
                 us = pusers.get(op[1], [])
-                if op[0] == 'bn' and us and op[1] != self.feature_name:
+                if op[0] == 'bn' and us and op[1] != self.feature_name and not prelu_net:      # (the opt-in backward fusion is not taken by the BN + PReLU nets)
                     first = plan[us[0]]
                     if (first[0] == 'conv' and len(us) <= 2) or (first[0] == 'gconv' and len(us) == 1):
                         self.fuse_bwd[op[1]] = j
@@ -540,8 +589,11 @@ class GraphNet(Network):
                 if as_res and i is not None and pusers.get(op[2], []) == [j] and i == j - 1:
                     self.shortcut_fwd[i] = True
                     self.shortcut_fwd[j] = True
+        # tensors read by a BN AND by the activation-free shortcut of a later BN (the input of an IResNet identity block): the only
+        # place where two gradient contributions are summed outside a conv's `addin` (_add); everywhere else a second one is a plan bug (_put)
+        self.shortcut_shared = {op[4] for op in plan if op[0] == 'bn' and op[4] is not None and not op[5]}
         self.plan = plan
-        self.has_classifier = plan[-1][0] == 'fc'
+        self.has_classifier = plan[-1][0] == 'fc' and self.spec[plan[-1][3]][1] == 'cls_w'
 
     @staticmethod
     def _inputs(op):
@@ -555,6 +607,8 @@ class GraphNet(Network):
             return [x for x in op[2]['ins'] if x is not None]
         if op[0] == 'bn':
             return [op[2]] + ([op[4]] if op[4] is not None else [])
+        if op[0] == 'bnprelu':
+            return [op[2]]
         if op[0] == 'addrelu':
             return [op[2], op[3]]
         if op[0] == 'seblock':
@@ -667,8 +721,10 @@ class GraphNet(Network):
             shape = (n,) + self.shapes[out]
             if kind != 'bnstats':
                 self.t[out] = torch.empty(shape, **(i16 if out in self.h16 else f32))
-            if kind in ('bn', 'bnstats', 'seblock'):
+            if kind in ('bn', 'bnstats', 'seblock', 'bnprelu'):
                 c = shape[-1]
+                if kind == 'bnprelu':
+                    need = max(need, q('fte_bn_prelu_ws_bytes', c))
                 self.bn[out] = dict(mean=torch.empty(c, **f32), rstd=torch.empty(c, **f32), scale=torch.empty(c, **f32),
                                     shift=torch.empty(c, **f32), coef=torch.empty(3 * c, **f32))
                 need = max(need, q('fte_bn_ws_bytes', c))
@@ -728,6 +784,8 @@ class GraphNet(Network):
                 self.t[out + '/idx'] = torch.empty(shape, dtype=torch.uint8, device=dev)
             elif kind == 'dropout':
                 self.t[out + '/mask'] = torch.empty(shape, **f32)
+            elif kind == 'fc' and self.spec[op[3]][1] == 'embed_w':
+                need = max(need, q('fte_gemm_ws_bytes', n, shape[-1], self.spec[op[3]][0][0]))
             elif kind == 'fc':
                 need = max(need, q('fte_gemm_ws_bytes', n, self.sub_centers * self.cpad, self.shapes[op[2]][0]))
         if s16:
@@ -846,7 +904,7 @@ class GraphNet(Network):
             bop = self.plan[j]
             b, pre = self.bn[bop[1]], bop[3]
             return (self.view(pre + '/gamma'), self.view(pre + '/beta'), b['mean'], b['rstd'], b['scale'], b['shift'],
-                    self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None, BN_EPS, BN_DECAY)
+                    self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None, self.bn_eps, self.bn_decay)
         main_s = torch.cuda.current_stream()
         sc_side = self.side if (self.side is not None and is_training and self.shortcut_fwd) else None
         sc_ev = {}                                       # shortcut tensor -> event of the side stream that completes it
@@ -933,16 +991,16 @@ class GraphNet(Network):
                     call('fte_bn_train_stats_s16', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
                          b['mean'], b['rstd'], b['scale'], b['shift'],
                          self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                         rows, c, BN_EPS, BN_DECAY, 1 if inp in h16 else 0, self.ws, self.ws_bytes, st)
+                         rows, c, self.bn_eps, self.bn_decay, 1 if inp in h16 else 0, self.ws, self.ws_bytes, st)
                 elif is_training:
                     upd = self.update_moving_stats
                     call('fte_bn_train_stats', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
                          b['mean'], b['rstd'], b['scale'], b['shift'],
                          self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                         rows, c, BN_EPS, BN_DECAY, self.ws, self.ws_bytes, st)
+                         rows, c, self.bn_eps, self.bn_decay, self.ws, self.ws_bytes, st)
                 else:
                     call('fte_bn_infer_coef', self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], b['scale'], b['shift'], c, BN_EPS, st)
+                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], b['scale'], b['shift'], c, self.bn_eps, st)
             elif kind == 'bn':
                 _, _, inp, pre, res, relu = op
                 b = self.bn[out]
@@ -964,23 +1022,36 @@ class GraphNet(Network):
                         call('fte_bn_train_fwd_s16', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'), resbuf, T[out],
                              b['mean'], b['rstd'], b['scale'], b['shift'],
                              self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                             rows, c, BN_EPS, BN_DECAY, relu, fl, ws_j, self.ws_bytes, st)
+                             rows, c, self.bn_eps, self.bn_decay, relu, fl, ws_j, self.ws_bytes, st)
                     else:
                         call('fte_bn_infer_fwd_s16', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
                              self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], resbuf, T[out],
-                             b['scale'], b['shift'], rows, c, BN_EPS, relu, fl, st)
+                             b['scale'], b['shift'], rows, c, self.bn_eps, relu, fl, st)
                 elif is_training:
                     upd = self.update_moving_stats
                     call('fte_bn_train_fwd', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'), resbuf, T[out],
                          b['mean'], b['rstd'], b['scale'], b['shift'],
                          self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                         rows, c, BN_EPS, BN_DECAY, relu, ws_j, self.ws_bytes, st)
+                         rows, c, self.bn_eps, self.bn_decay, relu, ws_j, self.ws_bytes, st)
                 else:
                     call('fte_bn_infer_fwd', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
                          self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], resbuf, T[out],
-                         b['scale'], b['shift'], rows, c, BN_EPS, relu, st)
+                         b['scale'], b['shift'], rows, c, self.bn_eps, relu, st)
                 if on_side:
                     sc_ev[out] = sc_side.record_event()
+            elif kind == 'bnprelu':
+                _, _, inp, pre, aname = op
+                b = self.bn[out]
+                c = self.shapes[out][-1]
+                rows = T[out].numel() // c
+                if not is_training:                            # moving statistics -> scale / shift, then the apply (fte.h)
+                    call('fte_bn_prelu_infer_fwd', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'), self.state[pre + '/moving_mean'],
+                         self.state[pre + '/moving_variance'], self.view(aname), T[out], b['scale'], b['shift'], rows, c, self.bn_eps, st)
+                else:
+                    if j not in stats_done:                    # (else the producing conv's epilogue left the batch statistics)
+                        ba = bn_args(j)
+                        call('fte_bn_train_stats', T[inp], *ba[:8], rows, c, ba[8], ba[9], ws_j, self.ws_bytes, st)
+                    call('fte_bn_prelu_apply', T[inp], b['scale'], b['shift'], self.view(aname), T[out], rows, c, st)
             elif kind == 'gconv':
                 ih, iw, c = self.shapes[op[2]]
                 pk = self._gconv_pack(op)
@@ -1028,14 +1099,14 @@ class GraphNet(Network):
                     upd = self.update_moving_stats
                     args = (T[zin], self.view(pre + '/gamma'), self.view(pre + '/beta'), b['mean'], b['rstd'], b['scale'], b['shift'],
                             self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                            n * hw, c, BN_EPS, BN_DECAY)
+                            n * hw, c, self.bn_eps, self.bn_decay)
                     if s16:
                         call('fte_bn_train_stats_s16', *args, 1 if zin in h16 else 0, self.ws, self.ws_bytes, st)
                     else:
                         call('fte_bn_train_stats', *args, self.ws, self.ws_bytes, st)
                 else:
                     call('fte_bn_infer_coef', self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], b['scale'], b['shift'], c, BN_EPS, st)
+                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], b['scale'], b['shift'], c, self.bn_eps, st)
                 sq, hid, gate = T[out + '/sq'], T[out + '/hid'], T[out + '/gate']
                 call('fte_se_squeeze', T[zin], b['scale'], b['shift'], b['mean'], b['rstd'], sq, T[out + '/xm'] if is_training else None,
                      n, hw, c, fl & 1, st)
@@ -1073,6 +1144,9 @@ class GraphNet(Network):
                     call('fte_dropout_fwd', T[op[2]], T[out + '/mask'], T[out], T[out].numel(), op[3], seed, st)
                 else:
                     T[out].copy_(T[op[2]])
+            elif kind == 'fc' and self.spec[op[3]][1] == 'embed_w':      # [n, h, w, c] read as one row-major [n, h w c] operand; no bias
+                fin, d = self.spec[op[3]][0]
+                call('fte_gemm_nn', T[op[2]], self.view(op[3]), None, T[out], n, d, fin, self.ws, self.ws_bytes, st)
             elif kind == 'fc':
                 k = self.shapes[op[2]][0]
                 call('fte_gemm_nn', T[op[2]], self.view(op[3]), None, T[out], n, self.sub_centers * self.cpad, k, self.ws, self.ws_bytes, st)
@@ -1238,7 +1312,7 @@ class GraphNet(Network):
         return ([self.backward_head] if self.has_classifier else []) + body
 
     def _op_weight_names(self, op):
-        if op[0] in ('conv', 'gconv', 'dwconv'):
+        if op[0] in ('conv', 'gconv', 'dwconv') or (op[0] == 'fc' and self.spec[op[3]][1] == 'embed_w'):
             return [op[3]]
         if op[0] in ('se', 'seblock'):
             w1, _, w2, _, _ = self._se_names(op[5] if op[0] == 'seblock' else op)
@@ -1531,6 +1605,11 @@ class GraphNet(Network):
                     else:
                         call('fte_bn_train_bwd_s16', dy, None, T[inp], gam, b['mean'], b['rstd'], None, None, None, dz, dgam, dbet,
                              rows, c, fl, self.ws, self.ws_bytes, st)
+                elif res is not None and not relu:         # BN + shortcut, no activation: dy goes unmasked into the BN backward and
+                    call('fte_bn_train_bwd', dy, None, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], dz,      # unchanged (no copy) to the shortcut
+                         self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), rows, c,
+                         self.ws, self.ws_bytes, st)
+                    self._add(res, dy)
                 elif res is not None:                      # the shortcut gets g = dy * (out > 0): a by-product of the reduce pass
                     g = self._new(out)
                     call('fte_bn_train_bwd_res', dy, T[out], T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], g, dz,
@@ -1545,7 +1624,27 @@ class GraphNet(Network):
                     call('fte_bn_train_bwd', dy, None, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], dz,
                          self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), rows, c,
                          self.ws, self.ws_bytes, st)
+                if inp in self.shortcut_shared:
+                    self._add(inp, dz)               # ... plus the gradient the shortcut passed on
+                else:
+                    self._put(inp, dz)
+            elif kind == 'bnprelu':
+                _, _, inp, pre, aname = op
+                b = self.bn[out]
+                c = self.shapes[out][-1]
+                rows = dy.numel() // c
+                dz = torch.empty_like(T[inp])
+                call('fte_bn_prelu_train_bwd', dy, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], b['scale'], b['shift'], self.view(aname),
+                     dz, self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), self.view(aname, self.grads), rows, c,
+                     self.ws, self.ws_bytes, st)
                 self._put(inp, dz)
+            elif kind == 'fc':                           # a dense layer inside the body (the classifier is backward_head's)
+                fin, d = self.spec[op[3]][0]
+                x = T[op[2]]
+                wgrad('fte_gemm_tn', dy, x, dy, self.view(op[3], self.grads), n, d, fin, wws, self.ws_bytes, wst)
+                dx = self._new(op[2])
+                call('fte_gemm_nt', dy, self.view(op[3]), None, None, 0, None, dx, None, n, d, fin, self.ws, self.ws_bytes, st)
+                self._put(op[2], dx)
             elif kind == 'conv':
                 _, _, inp, wname, stride = op
                 ih, iw, cin = self.shapes[inp]
@@ -1591,6 +1690,24 @@ class GraphNet(Network):
         if name in self._grad:
             raise RuntimeError('gradient of %s already has a contribution that cannot be accumulated in place' % name)
         self._grad[name] = g
+
+    def _add(self, name, g):
+        """_put, or -- a tensor read by a BN and by a shortcut (the IResNet block's input) -- the sum of the two contributions.  The
+        one already there may be shared with another tensor's gradient (a shortcut passes its gradient on without a copy), so the
+        sum goes to whichever buffer is the walk's own: `g` when it is a fresh BN dz, else a new one."""
+        assert name in self.shortcut_shared, name
+        prev = self._grad.get(name)
+        if prev is None:
+            self._grad[name] = g
+            return
+        assert prev.dtype == torch.float32 and g.dtype == torch.float32 and prev.shape == g.shape, name
+        out = g if self._own(g) else torch.empty_like(g)
+        _lib.call('fte_axpby', 1.0, g, 1.0, prev, out, g.numel(), _stream())
+        self._grad[name] = out
+
+    def _own(self, g):
+        """is `g` referenced by no other entry of the gradients in flight?"""
+        return not any(v is g for v in self._grad.values())
 
     # ---- bookkeeping the wrappers use ---------------------------------------------------------------------
     def param_list(self, is_training, trainable, scope=None):
