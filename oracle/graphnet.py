@@ -2,7 +2,7 @@
 (nets/resnet.py, nets/resnext.py, nets/shufflenet_v2.py).  TEST INFRASTRUCTURE -- PARITY UNPINNED.
 
 A net is a list of ops over named tensors; forward fills an environment, backward walks the list in
-reverse accumulating gradients.  The HIP engine (tf_face_toolbox_amd/nets/graph.py) executes the same
+reverse accumulating gradients.  The HIP engine (tf_face_toolbox_amd/nets/graph.py, planned by nets/plan.py) executes the same
 op lists, which is what makes the layer-by-layer parity checks line up."""
 from collections import OrderedDict
 

@@ -308,7 +308,8 @@ def test_shufflenet_training_steps_and_eval_mode():
 def test_second_stream_and_folded_gather_change_no_bit(name, n, monkeypatch):
     """The filter gradients run on a second HIP stream, BN is folded into the channel gather and the 3x3 stem runs on the direct
     conv: every kernel is deterministic and the folds evaluate the same fused multiply-adds, so after five optimizer steps the
-    parameter arena is BIT-IDENTICAL to a run with the side stream and the gather fold switched off."""
+    parameter arena is BIT-IDENTICAL to a run with the side stream and the gather fold switched off -- and to one that keeps the side
+    stream for the filter gradients but takes the shortcut branches, the classifier's filter gradient and the weight-decay sum off it."""
     ncls, h, w = 10, 64, 64
     rng = np.random.default_rng(3)
     x = dev(rng.uniform(-1, 1, (n, h, w, 3))); y = dev(rng.integers(0, ncls, n), torch.int32)
@@ -323,12 +324,15 @@ def test_second_stream_and_folded_gather_change_no_bit(name, n, monkeypatch):
             step()
         torch.cuda.synchronize()
         return net.params.clone(), float(losses[0]), net
-    p1, l1, net1 = run({'FTE_SIDE_STREAM': '1', 'FTE_BN_GATHER': '1'})
-    p0, l0, net0 = run({'FTE_SIDE_STREAM': '0', 'FTE_BN_GATHER': '0'})
-    assert net1.side is not None and net0.side is None
+    moves = ('FTE_SHORTCUT_SIDE', 'FTE_HEAD_SIDE', 'FTE_REG_SIDE')          # these only choose the stream a launch goes to
+    p1, l1, net1 = run(dict({'FTE_SIDE_STREAM': '1', 'FTE_BN_GATHER': '1'}, **{k: '1' for k in moves}))
+    p2, l2, net2 = run(dict({'FTE_SIDE_STREAM': '1', 'FTE_BN_GATHER': '1'}, **{k: '0' for k in moves}))
+    p0, l0, net0 = run(dict({'FTE_SIDE_STREAM': '0', 'FTE_BN_GATHER': '0'}, **{k: '0' for k in moves}))
+    assert net1.side is not None and net2.side is not None and net0.side is None
     assert (len(net1.folded) > 0) == name.startswith('Shuffle') and len(net0.folded) == 0
-    assert np.isfinite(l1) and l1 == l0
-    assert torch.equal(p1, p0)
+    assert (len(net1.shortcut_fwd) > 0) == (not name.startswith('Shuffle')) and len(net2.shortcut_fwd) == 0 and len(net0.shortcut_fwd) == 0
+    assert np.isfinite(l1) and l1 == l0 and l1 == l2
+    assert torch.equal(p1, p0) and torch.equal(p1, p2)
 
 
 def test_config5_per_gpu_workload_properties():

@@ -5,6 +5,7 @@ import torch
 
 from oracle import spherenet as osn
 from tf_face_toolbox_amd import net_select, Singular, DataParallel
+from tf_face_toolbox_amd.nets import plan
 from tf_face_toolbox_amd.nets.sphere import same_pads
 
 
@@ -285,3 +286,50 @@ def test_profile_tables_regenerate_from_the_committed_profiles(capsys):
         d = json.load(open(os.path.join(root, 'tests', 'golden', name)))
         assert ('r6_' if name.startswith('headline') else 'r5_') in d['source'], name      # SphereNet: round 6's profiles; the BN nets': round 5's
         assert (d[key] if key else [v for k, v in d.items() if isinstance(v, list)][0])
+
+
+# plan tables of the three families under the default switches: (plan ops, seblock, se, bnstats, fuse_fwd, fuse_bwd, fold_apply,
+# shortcut_fwd, folded, se_fused, narrow, stored stem width), as the engine planned them before planning became nets/plan.py
+_PLAN_DEFAULTS = {'ResNet-50': (110, 0, 0, 0, 53, 47, 32, 8, 0, 0, 0, 64),
+                  'SENet-50': (110, 16, 0, 0, 53, 32, 32, 8, 0, 32, 0, 64),
+                  'ShuffleNet-v2-small': (152, 0, 0, 19, 56, 19, 0, 0, 19, 0, 3, 32)}
+
+
+def _plan_tables(net):
+    count = lambda kind: sum(1 for op in net.plan if op[0] == kind)
+    return (len(net.plan), count('seblock'), count('se'), count('bnstats'), len(net.fuse_fwd), len(net.fuse_bwd), len(net.fold_apply),
+            len(net.shortcut_fwd), len(net.folded), len(net.se_fused), len(net.narrow), net.shapes[net.plan[0][1]][-1])
+
+
+@pytest.mark.parametrize('name', sorted(_PLAN_DEFAULTS))
+@pytest.mark.parametrize('switch', [None, 'FTE_BN_FUSE', 'FTE_BN_FOLD', 'FTE_SE_FUSE', 'FTE_BN_GATHER', 'FTE_SHORTCUT_SIDE', 'FTE_DIRECT_STEM'])
+def test_planning_switches_act_on_the_plan(name, switch, monkeypatch):
+    """Every planning switch of the graph engine (nets/plan.py read_options) set to 0 takes exactly its own table away and leaves the
+    others at the default counts; the switches are read when the net is built."""
+    for k in ('FTE_BN_FUSE', 'FTE_BN_FOLD', 'FTE_SE_FUSE', 'FTE_BN_GATHER', 'FTE_SHORTCUT_SIDE', 'FTE_DIRECT_STEM', 'FTE_BN_FUSE_3X3'):
+        monkeypatch.delenv(k, raising=False)
+    if switch is not None:
+        monkeypatch.setenv(switch, '0')
+    net = net_select(name)
+    net.build(112, 112, 3, 100, 'cpu')
+    nops, seblock, se, bnstats, fuse_fwd, fuse_bwd, fold, sc, folded, se_fused, narrow, stem = want = _PLAN_DEFAULTS[name]
+    if switch == 'FTE_BN_FUSE':                          # no statistics in a conv epilogue, so nothing to fold into a consumer either
+        assert net.fuse_fwd == {} and net.fuse_bwd == {} and net.fold_apply == {}
+        want = (nops, seblock, se, bnstats, 0, 0, 0, sc, folded, se_fused, narrow, stem)
+    elif switch == 'FTE_BN_FOLD':
+        assert net.fold_apply == {}
+        want = (nops, seblock, se, bnstats, fuse_fwd, fuse_bwd, 0, sc, folded, se_fused, narrow, stem)
+    elif switch == 'FTE_SE_FUSE':                        # every SE block back as BN, gate, add + ReLU: two more plan ops each
+        assert not any(op[0] == 'seblock' for op in net.plan) and net.se_fused == {}
+        want = (nops + 2 * seblock, 0, seblock, bnstats, fuse_fwd, fuse_bwd, fold, sc, folded, 0, narrow, stem)
+    elif switch == 'FTE_BN_GATHER':
+        assert net.folded == {} and not any(op[0] == 'bnstats' for op in net.plan)
+        want = (nops, seblock, se, 0, fuse_fwd, fuse_bwd, fold, sc, 0, se_fused, narrow, stem)
+    elif switch == 'FTE_SHORTCUT_SIDE':
+        assert net.shortcut_fwd == {}
+        want = (nops, seblock, se, bnstats, fuse_fwd, fuse_bwd, fold, 0, folded, se_fused, narrow, stem)
+    elif switch == 'FTE_DIRECT_STEM':                    # the stem stored channel_pad wide, like every other tensor
+        assert net.narrow == set() and net.shapes[net.plan[0][1]][-1] == net._pc(net.real_c[net.plan[0][1]])
+        want = (nops, seblock, se, bnstats, fuse_fwd, fuse_bwd, fold, sc, folded, se_fused, 0, max(stem, net.channel_pad))
+    assert _plan_tables(net) == want
+    assert net.opt == plan.read_options()

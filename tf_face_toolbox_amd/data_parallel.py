@@ -218,7 +218,7 @@ class DataParallel(Singular):
     def __init__(self, model, lr, optimizer, num_gpus=4, weight_decay=5e-4, comm=None, sync_centers=False, sync_sample=False):
         """`sync_centers` (not in the reference; default off = the reference's behaviour): the center loss's `centers` table
         is per-tower state there (loss.py:34-39) and the towers' tables drift apart; True all-gathers every step's scatter rows
-        so that all replicas keep ONE table, equal to the single-tower update of the global batch (nets/graph.py).
+        so that all replicas keep ONE table, equal to the single-tower update of the global batch (nets/graph.py _reconcile_centers).
         `sync_sample` (default off): a sampled-class head (sample_rate) under data parallelism.  The ranks all-gather their labels
         and draw ONE class sample from the global batch, the compact [D, Spad] classifier gradient is all-reduced instead of the
         dense one and goes straight into the classifier; without it such a net is refused.  No effect on a dense

@@ -1,5 +1,5 @@
 """The launch sequence of the heads on the normalised features and classifier columns (A-softmax, ArcFace / CosFace, AdaFace, the
-sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py call it.
+sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py (loss_function, backward_head) call it.
 
 Plain functions over buffers the CALLER owns.  `b` is any object that carries them under the nets' attribute names -- a net itself, or
 the scratch namespace loss.py allocates per call: xn [n], wn [ld], rowcoef [n], colcoef [ld], G [n, ld], loss_rows [n]; for AdaFace

@@ -14,7 +14,7 @@ class FilterPacks(object):
     def __init__(self, entries, device, head=0):
         """`head` > 0: the first `head` entries form launches of their own (refresh_head / refresh_rest): a net whose forward walk
         starts with them can pack those on its main stream and the rest -- and every HWIO pack, which only the backward pass reads --
-        on a side stream, under its first layers (nets/graph.py)."""
+        on a side stream, under its first layers (nets/graph.py _start_packs)."""
         i16 = dict(dtype=torch.int16, device=device)
         self.head = int(head)
         off = 0

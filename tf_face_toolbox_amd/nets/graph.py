@@ -7,45 +7,23 @@ fusion -- and then forward / backward are fixed sequences of kernel launches on 
 It replaces the TF graph that nets/resnet.py builds and `tf.gradients` differentiates
 (data_parallel.py:33); every FLOP runs in libfte.so.
 """
-import os
 from collections import OrderedDict
 
 import torch
 
 from .. import _lib, heads
+from . import plan
 from .net_base import MARGIN_PRESETS, NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
-from .sphere import Variable, same_pads
+from .plan import shuffle_perm, stem_kpad          # noqa: F401 (shuffle_perm: the tests import it from here)
+from .sphere import Variable
 
 BN_EPS = 1e-3          # nets/resnet.py:97-99 via layers.batch_norm defaults
 BN_DECAY = 0.999
 
 
-def stem_kpad(k, cin):
-    """rows of the im2col'ed stem weight, zero-padded to a multiple of 32 (7*7*3 = 147 -> 160, 3*3*3 = 27 -> 32)"""
-    return (k * k * cin + 31) // 32 * 32
-
-
-STEM_KPAD = stem_kpad(7, 3)
-
-
-def shuffle_perm(c, data_format):
-    """_channel_shuffle (nets/shufflenet_v2.py:66-77) as an index vector: out[k] = in[perm[k]].  The reference's NCHW
-    branch views channels as [2, C/2] and transposes; its NHWC branch views them as [C/2, 2] -- a different permutation."""
-    idx = torch.arange(c)
-    if data_format == 'NCHW':
-        return idx.reshape(2, c // 2).t().reshape(-1).tolist()
-    return idx.reshape(c // 2, 2).t().reshape(-1).tolist()
-
-
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
-
-def _prod(shape):
-    n = 1
-    for d in shape:
-        n *= d
-    return n
 
 
 class _Activations(dict):
@@ -75,6 +53,16 @@ class _Activations(dict):
             zz = zz.view(torch.bfloat16).float()
         y = torch.addcmul(b['shift'], zz, b['scale'])
         return torch.relu(y) if relu else y
+
+
+class _Walk(object):
+    """What the handlers of one walk over the plan share beside the net's buffers.  forward: batch size, _lib.call as found when the
+    walk started, training / storage mode, the main and side streams, the stream and workspace of the op at hand, the BN ops whose
+    statistics a conv epilogue left, the folds taken, the events of the shortcut branches and of the filter packs.  backward: the
+    side stream's handle and workspace, the queued filter gradients, the BN outputs reduced by a fused data gradient, the gradients
+    in flight.  _alloc: batch size, storage mode and the workspace bytes needed so far."""
+    __slots__ = ('call', 'n', 'is_training', 's16', 'sfx', 'upd', 'main', 'side', 'st', 'ws', 'on_side', 'pack_ev', 'packs_pending',
+                 'stats_done', 'folded_in', 'sc_ev', 'wst', 'wws', 'pending', 'reduced', 'G', 'need')
 
 
 class GraphNet(Network):
@@ -154,25 +142,19 @@ class GraphNet(Network):
         self.in_hwc = (height, width, channels)
         self.num_classes = int(num_classes)
         self.cpad = (self.num_classes + 127) // 128 * 128
+        self.opt = plan.read_options()                   # every FTE_* switch of the engine, as set now
+        self.fuse_3x3, self.fuse_bwd_conv, self.fuse_bwd_gconv = self.opt.bn_fuse_3x3, self.opt.bn_fuse_bwd, self.opt.bn_fuse_gbwd
         self.graph, spec = self.build_graph(channels, num_classes)
         if self.sub_centers > 1:
             spec = [(n, (s[0], self.sub_centers * s[1]) if k == 'cls_w' else s, k) for n, s, k in spec]
         self.spec = OrderedDict((n, (s, k)) for n, s, k in spec)
-        # A 3x3 stem of at most 32 filters (ShuffleNet-v2 small: 24) is stored 32 channels wide, not channel_pad wide: its
-        # 56x56 output is the largest tensor of the net, and every pass over it (BN statistics / apply, max-pool, their
-        # gradients) is pure HBM traffic -- 64-wide storage made 62 % of those bytes padding.  `narrow` = the variables
-        # (filter, BN gamma / beta) that follow that width.
-        self.narrow = set()
-        if self.channel_pad > 32 and os.environ.get('FTE_DIRECT_STEM', '1') != '0':
-            for op in self.graph:
-                if op[0] == 'conv':
-                    k, _, cin, cout = self.spec[op[3]][0]
-                    if cin <= 4 and k == 3 and cout <= 32:
-                        self.narrow.add(op[3])
-                        for o2 in self.graph:
-                            if o2[0] == 'bn' and o2[2] == op[1]:
-                                self.narrow.update([o2[3] + '/gamma', o2[3] + '/beta'])
-        self._infer_shapes()
+        # shapes, typed plan ops and fusion tables (nets/plan.py); the gather tables become device tensors here
+        compiled = plan.compile_net(self.graph, self.spec, self.in_hwc, self.channel_pad, self.feature_name, self.opt,
+                                    self.num_classes, self.sub_centers * self.cpad, self.name)
+        for field, value in compiled._asdict().items():
+            setattr(self, field, value)
+        self.plan = [self._device_tables(op) if op[0] == 'gather' else op for op in compiled.plan]
+        self._alloc_ops, self._fwd_ops, self._bwd_ops = (self._dispatch(phase) for phase in ('alloc', 'fwd', 'bwd'))
         small = [(n, s, k) for n, s, k in spec if k in ('gamma', 'beta', 'bias', 'alpha')]
         convs = [(n, s, k) for n, s, k in spec if k in ('conv_w', 'gconv_w', 'fc_w', 'dw_w', 'embed_w')]
         cls = [(n, s, k) for n, s, k in spec if k == 'cls_w']
@@ -208,7 +190,6 @@ class GraphNet(Network):
             self.adaface_stats, extra = adaface_state(dev)
             self.state.update(extra)
         self._init_params()
-        self._compile()
         self.built = True
         return self
 
@@ -346,311 +327,16 @@ class GraphNet(Network):
             return t.reshape(c, h, w, d).permute(1, 2, 0, 3).reshape(h * w * c, d)
         return t.reshape(h, w, c, d).permute(2, 0, 1, 3).reshape(h * w * c, d)
 
-    # ---- static analysis ----------------------------------------------------------------------------
-    def _infer_shapes(self):
-        """self.shapes: stored (channel-padded) shape of every tensor; self.real_c: its true channel count."""
-        h, w, c = self.in_hwc
-        shp = {'images': (h, w, c)}
-        real = {'images': c}
-        pc = self._pc
-        self.embed_in = {}                               # 'embed_w' variable -> (h, w, c) of the feature map its FC flattens
-
-        def put(name, hh, ww, cc):
-            real[name] = cc
-            shp[name] = (hh, ww, pc(cc))
-        for op in self.graph:
-            kind, out = op[0], op[1]
-            if kind == 'conv':
-                ih, iw, _ = shp[op[2]]
-                k, _, cin, cout = self.spec[op[3]][0]
-                assert cin == real[op[2]], (op, cin, real[op[2]])
-                put(out, same_pads(ih, k, op[4])[0], same_pads(iw, k, op[4])[0], cout)
-                if op[3] in self.narrow:
-                    shp[out] = shp[out][:2] + ((cout + 31) // 32 * 32,)
-            elif kind in ('gconv', 'dwconv'):
-                ih, iw, _ = shp[op[2]]
-                put(out, same_pads(ih, 3, op[4])[0], same_pads(iw, 3, op[4])[0], real[op[2]])
-            elif kind in ('bn', 'relu', 'dropout', 'se', 'add', 'prelu'):
-                shp[out] = shp[op[2]]
-                real[out] = real[op[2]]
-            elif kind == 'maxpool':
-                ih, iw, cp = shp[op[2]]
-                put(out, same_pads(ih, 3, 2)[0], same_pads(iw, 3, 2)[0], real[op[2]])
-                shp[out] = shp[out][:2] + (cp,)                 # keeps its input's stored width
-            elif kind == 'gap':
-                shp[out] = (shp[op[2]][2],)
-                real[out] = real[op[2]]
-            elif kind == 'fc' and self.spec[op[3]][1] == 'embed_w':      # dense layer on the flattened [n, h w c] map (or on [n, c])
-                fin, d = self.spec[op[3]][0]
-                src = shp[op[2]]
-                assert self.channel_pad == 1 and fin == _prod(src) and d % 64 == 0 and fin % 32 == 0, (op, src, fin, d)
-                self.embed_in[op[3]] = src if len(src) == 3 else (1, 1, src[0])
-                shp[out] = (d,)
-                real[out] = d
-            elif kind == 'fc':
-                shp[out] = (self.sub_centers * self.cpad,)
-                real[out] = self.num_classes
-            elif kind == 'split':
-                ih, iw, _ = shp[op[2]]
-                cc = real[op[2]]
-                put(out, ih, iw, int(0.5 * cc))
-                put(op[3], ih, iw, cc - int(0.5 * cc))
-            elif kind == 'shufsplit':
-                ih, iw, _ = shp[op[2]]
-                cc = real[op[2]] + real[op[3]]
-                put(out, ih, iw, int(0.5 * cc))
-                put(op[4], ih, iw, cc - int(0.5 * cc))
-            elif kind == 'shufcat':
-                ih, iw, _ = shp[op[2]]
-                put(out, ih, iw, real[op[2]] + real[op[3]])
-            else:
-                raise ValueError(kind)
-        # A tensor stored narrower than channel_pad (the 32-wide stem) may only feed ops that take their width from the stored
-        # input: BN / ReLU / max-pool, the channel gathers, and a 1x1 conv (which reads a valid row prefix).  A 3x3, grouped or
-        # depthwise conv, an SE gate or an add would lay out its weights / output for pc(real) channels while the kernel is
-        # launched with the stored width -- a silent wrong stride.  No net of the factory does that; a new one must not.
-        narrow_stored = {n for n in shp if n != 'images' and len(shp[n]) == 3 and shp[n][2] != pc(real[n])}
-        for op in self.graph:
-            ins = [a for a in op[2:] if isinstance(a, str) and a in narrow_stored]
-            if not ins:
-                continue
-            ok = op[0] in ('bn', 'relu', 'maxpool', 'split', 'shufsplit', 'shufcat', 'dropout') or \
-                (op[0] == 'conv' and self.spec[op[3]][0][0] == 1)
-            assert ok, 'op %r consumes %s, which is stored %d channels wide (not %d): unsupported consumer of the narrow stem' % (
-                op, ins[0], shp[ins[0]][2], pc(real[ins[0]]))
-        self.shapes = shp
-        self.real_c = real
-
-    def _table(self, entries, width):
-        """device int32 gather table of `width` slots from [(src, channel) or None]"""
-        t = [-1] * width
-        for k, e in enumerate(entries):
-            if e is not None:
-                t[k] = (e[0] << 16) | e[1]
-        return torch.tensor(t, dtype=torch.int32, device=self.device)
+    def _device_tables(self, op):
+        """a 'gather' plan op with its int32 tables (plan.gather_tables) as device tensors"""
+        dev = lambda pairs: [(name, torch.tensor(t, dtype=torch.int32, device=self.device)) for name, t in pairs]
+        return op._replace(outs=dev(op.outs), bwd=dev(op.bwd))
 
     def _gather_tables(self, op):
-        """Forward and backward channel-gather tables of a split / shufsplit / shufcat op (fte_channel_gather)."""
-        kind = op[0]
-        real, shp = self.real_c, self.shapes
-        if kind == 'split':                                   # nets/shufflenet_v2.py:60-64
-            cc = real[op[2]]
-            h = int(0.5 * cc)
-            fwd = [(op[1], self._table([(0, k) for k in range(h)], shp[op[1]][2])),
-                   (op[3], self._table([(0, h + k) for k in range(cc - h)], shp[op[3]][2]))]
-            bwd = [(op[2], self._table([(0, k) if k < h else (1, k - h) for k in range(cc)], shp[op[2]][2]))]
-            return dict(ins=(op[2], None), outs=fwd, gouts=(op[1], op[3]), bwd=bwd)
-        a, b = op[2], op[3]
-        ca, cb = real[a], real[b]
-        cc = ca + cb
-        fmt = op[5] if kind == 'shufsplit' else op[4]
-        perm = shuffle_perm(cc, fmt)                          # shuffled[k] = cat[perm[k]]
-        src = [(0, j) if j < ca else (1, j - ca) for j in perm]
-        if kind == 'shufsplit':
-            h = int(0.5 * cc)
-            fwd = [(op[1], self._table(src[:h], shp[op[1]][2])), (op[4], self._table(src[h:], shp[op[4]][2]))]
-            gouts = (op[1], op[4])
-            where = lambda k: (0, k) if k < h else (1, k - h)
-        else:
-            fwd = [(op[1], self._table(src, shp[op[1]][2]))]
-            gouts = (op[1], None)
-            where = lambda k: (0, k)
-        inv = [None] * cc
-        for k, j in enumerate(perm):
-            inv[j] = where(k)
-        bwd = [(a, self._table(inv[:ca], shp[a][2])), (b, self._table(inv[ca:], shp[b][2]))]
-        return dict(ins=(a, b), outs=fwd, gouts=gouts, bwd=bwd)
+        """the fields of the 'gather' plan op of a split / shufsplit / shufcat graph op (plan.gather_tables), tables on the device"""
+        return self._device_tables(plan.gather_tables(op, self.shapes, self.real_c))._asdict()
 
-    def _compile(self):
-        """Fuse bn -> relu and bn -> add -> relu into one BN-apply launch; build consumer counts."""
-        g = self.graph
-        users = {}
-        for i, op in enumerate(g):
-            for inp in self._inputs(op):
-                users.setdefault(inp, []).append(i)
-        plan, skip = [], set()
-        for i, op in enumerate(g):
-            if i in skip:
-                continue
-            if op[0] == 'bn':
-                out, res, relu, final = op[1], None, 0, op[1]
-                u = users.get(out, [])
-                if len(u) == 1 and g[u[0]][0] == 'relu':
-                    relu, final = 1, g[u[0]][1]
-                    skip.add(u[0])
-                elif len(u) == 1 and g[u[0]][0] == 'prelu':      # bn -> prelu: one plan op (fte_bn_prelu_apply / _train_bwd)
-                    skip.add(u[0])
-                    plan.append(('bnprelu', g[u[0]][1], op[2], op[3], g[u[0]][3]))
-                    continue
-                elif len(u) == 1 and g[u[0]][0] == 'add':
-                    add = g[u[0]]
-                    other = add[3] if add[2] == out else add[2]
-                    u2 = users.get(add[1], [])
-                    if len(u2) == 1 and g[u2[0]][0] == 'relu' and self._defined_before(other, i):
-                        res, relu, final = other, 1, g[u2[0]][1]
-                        skip.update([u[0], u2[0]])
-                    elif not any(g[k][0] == 'relu' for k in u2) and other != out and self._defined_before(other, i):
-                        # bn -> add with NO activation (the IResNet block's last BN plus shortcut): fte_bn_apply(res, relu = 0);
-                        # backward: the gradient goes unmasked into the BN backward and unchanged to the shortcut
-                        res, final = other, add[1]
-                        skip.add(u[0])
-                plan.append(('bn', final, op[2], op[3], res, relu))
-            elif op[0] == 'prelu':
-                raise ValueError('%s: prelu %r does not directly follow a bn that feeds nothing else (its input is %r): only the fused '
-                                 'bn -> prelu pair is implemented' % (self.name, op[1], op[2]))
-            elif op[0] == 'add':
-                u = users.get(op[1], [])
-                assert len(u) == 1 and g[u[0]][0] == 'relu', 'a bare add is always followed by a ReLU in these nets'
-                skip.add(u[0])
-                plan.append(('addrelu', g[u[0]][1], op[2], op[3]))
-            elif op[0] in ('split', 'shufsplit', 'shufcat'):
-                plan.append(('gather', op[1], self._gather_tables(op)))
-            else:
-                plan.append(op)
-        # A BN(+ReLU) output whose only consumer is a channel gather (conv3_1x1 and the stride-2 shortcut's 1x1 of a
-        # ShuffleNet block, nets/shufflenet_v2.py:96-113) is normalised INSIDE the gather: the BN op keeps its statistics
-        # pass only ('bnstats'), the gather applies scale / shift / ReLU to that source on the way
-        # (fte_channel_gather_affine), and the normalised tensor is never written (FTE_BN_GATHER=0: off, A/B hook).
-        # SE residual block: BN (no activation) -> SE gate -> add shortcut -> ReLU becomes ONE plan op whose kernels read the BN's input z
-        # and write the block's output; the BN output and the gated tensor never exist (csrc/layers.hip "SE residual block",
-        # fte_se_*).  FTE_SE_FUSE=0: the separate ops (A/B hook).
-        self.se_fused = {}
-        if os.environ.get('FTE_SE_FUSE', '1') != '0':
-            plan = self._fuse_se_blocks(plan)
-        self.folded = {}
-        pusers = {}
-        for j, op in enumerate(plan):
-            for x in self._plan_inputs(op):
-                pusers.setdefault(x, []).append(j)
-        if os.environ.get('FTE_BN_GATHER', '1') != '0':
-            for j, op in enumerate(plan):
-                if op[0] == 'bn' and op[4] is None:
-                    u = pusers.get(op[1], [])
-                    if len(u) == 1 and plan[u[0]][0] == 'gather' and op[1] != self.feature_name:
-                        plan[j] = ('bnstats',) + op[1:]
-                        self.folded[op[1]] = (op[2], op[5])          # name -> (z, relu)
-        # "BN fusion" (fte.h): a conv / grouped conv whose output feeds ONE batch norm leaves that layer's batch statistics in its
-        # epilogue (fuse_fwd: plan index of the conv -> plan index of the BN), and the data gradient that completes the gradient of
-        # a BN layer's OUTPUT -- the dgrad of its first consumer in plan order, which runs last in the backward walk and takes the
-        # other consumer's contribution through `addin` -- applies the ReLU mask and leaves the two sums of the BN backward
-        # (fuse_bwd: name of the BN output -> plan index of the BN).  Which of them can run fused (MFMA conv path, storage
-        # mode, grouped conv on the bf16 MFMA) is decided where they run.  FTE_BN_FUSE=0: off (A/B hook).
-        self.fuse_fwd, self.fuse_bwd = {}, {}
-        self.fuse_3x3 = os.environ.get('FTE_BN_FUSE_3X3', '1') != '0'
-        # The backward half is OPT-IN (FTE_BN_FUSE_BWD=1 / FTE_BN_FUSE_GBWD=1).  Measured on MI355X at 128 images per GPU, ms per step,
-        # forward only / + conv data gradients / + grouped-conv data gradients / no fusion: ResNeXt-50 7.84 / 7.91 / 8.17 / 8.23, ResNet-50
-        # 7.27 / 7.38 / - / 7.66, SE-ResNet-50 9.52 / 9.40 / - / 9.87, ShuffleNet-v2 (fp32, 256) 8.10 / 8.11 / - / 8.60: the tile kernels'
-        # epilogue waits for its three extra inputs with 3 blocks per CU, which costs what the separate reduce pass cost.
-        self.fuse_bwd_conv = os.environ.get('FTE_BN_FUSE_BWD', '0') == '1'
-        self.fuse_bwd_gconv = os.environ.get('FTE_BN_FUSE_GBWD', '0') == '1'
-        if os.environ.get('FTE_BN_FUSE', '1') != '0':
-            producer = {op[1]: j for j, op in enumerate(plan) if op[0] in ('conv', 'gconv')}
-            prelu_net = any(op[0] == 'bnprelu' for op in plan)
-            for j, op in enumerate(plan):
-                if op[0] not in ('bn', 'bnstats', 'seblock', 'bnprelu'):
-                    continue
-                i = producer.get(op[2])
-                if i is not None and pusers.get(op[2], []) == [j]:
-                    self.fuse_fwd[i] = j
-                us = pusers.get(op[1], [])
-                if op[0] == 'bn' and us and op[1] != self.feature_name and not prelu_net:      # (the opt-in backward fusion is not taken by the BN + PReLU nets)
-                    first = plan[us[0]]
-                    if (first[0] == 'conv' and len(us) <= 2) or (first[0] == 'gconv' and len(us) == 1):
-                        self.fuse_bwd[op[1]] = j
-        # ... and the normalise pass of a BN + ReLU whose output feeds ONE conv / grouped conv that itself runs fused can move into
-        # that consumer's operand loader (fold_apply: plan index of the BN -> plan index of the consumer): the consumer reads the
-        # BN's input z, applies scale / shift / ReLU on the way to the matrix cores and writes the normalised tensor back for the
-        # filter gradient; the bn_apply launch and its pass over the tensor disappear (fte.h, fte_conv2d_bn_fwd's in_scale).
-        # Whether the consumer's kernel takes it (bf16 storage, pointwise stride-1 conv of 64 / 128 / 256 channels, or a
-        # stride-1 grouped conv on the bf16 MFMA) is decided where it runs.  FTE_BN_FOLD=0: off (A/B hook).
-        self.fold_apply = {}
-        if self.fuse_fwd and os.environ.get('FTE_BN_FOLD', '1') != '0':
-            for j, op in enumerate(plan):
-                if op[0] == 'bn' and op[4] is None and op[5] and op[1] != self.feature_name and j in self.fuse_fwd.values():
-                    us = pusers.get(op[1], [])
-                    if len(us) == 1 and us[0] in self.fuse_fwd and plan[us[0]][0] in ('conv', 'gconv') and plan[us[0]][2] == op[1]:
-                        self.fold_apply[j] = us[0]
-        # Shortcut branches of the residual blocks (conv 1x1 -> BN without activation, consumed only as the `res` of the block's last
-        # BN or by its add + ReLU): independent of the block's main branch, so the forward walk queues them on the side stream and the
-        # consumer waits for their event (shortcut_fwd: plan index -> True for the conv and the BN).  FTE_SHORTCUT_SIDE=0: off (A/B hook).
-        self.shortcut_fwd = {}
-        if os.environ.get('FTE_SHORTCUT_SIDE', '1') != '0':
-            producer = {op[1]: j for j, op in enumerate(plan) if op[0] == 'conv'}
-            for j, op in enumerate(plan):
-                if op[0] != 'bn' or op[4] is not None or op[5]:
-                    continue
-                us = pusers.get(op[1], [])
-                if len(us) != 1 or op[1] == self.feature_name:
-                    continue
-                cons = plan[us[0]]
-                as_res = (cons[0] == 'bn' and cons[4] == op[1] and cons[2] != op[1]) or (cons[0] == 'addrelu' and op[1] in (cons[2], cons[3])) or \
-                    (cons[0] == 'seblock' and cons[4] == op[1] and cons[2] != op[1])
-                i = producer.get(op[2])
-                if as_res and i is not None and pusers.get(op[2], []) == [j] and i == j - 1:
-                    self.shortcut_fwd[i] = True
-                    self.shortcut_fwd[j] = True
-        # tensors read by a BN AND by the activation-free shortcut of a later BN (the input of an IResNet identity block): the only
-        # place where two gradient contributions are summed outside a conv's `addin` (_add); everywhere else a second one is a plan bug (_put)
-        self.shortcut_shared = {op[4] for op in plan if op[0] == 'bn' and op[4] is not None and not op[5]}
-        self.plan = plan
-        self.has_classifier = plan[-1][0] == 'fc' and self.spec[plan[-1][3]][1] == 'cls_w'
-
-    @staticmethod
-    def _inputs(op):
-        if op[0] in ('add', 'shufsplit', 'shufcat'):
-            return [op[2], op[3]]
-        return [op[2]]
-
-    def _plan_inputs(self, op):
-        """tensors a PLAN op reads"""
-        if op[0] == 'gather':
-            return [x for x in op[2]['ins'] if x is not None]
-        if op[0] == 'bn':
-            return [op[2]] + ([op[4]] if op[4] is not None else [])
-        if op[0] == 'bnprelu':
-            return [op[2]]
-        if op[0] == 'addrelu':
-            return [op[2], op[3]]
-        if op[0] == 'seblock':
-            return [op[2], op[4]]
-        return self._inputs(op)
-
-    def _fuse_se_blocks(self, plan):
-        """('bn', y, z, pre, None, 0) -> ('se', s, y, ...) -> ('addrelu', out, s, shortcut), each the only user of its input, becomes
-        ('seblock', out, z, pre, shortcut, se op, y, s) at the add's place (nets/resnet.py:63-92 with use_se)."""
-        users = {}
-        for j, op in enumerate(plan):
-            for x in self._plan_inputs(op):
-                users.setdefault(x, []).append(j)
-        drop, repl = set(), {}
-        for j, op in enumerate(plan):
-            if op[0] != 'bn' or op[4] is not None or op[5] or len(self.shapes[op[1]]) != 3 or op[1] == self.feature_name:
-                continue
-            u = users.get(op[1], [])
-            if len(u) != 1 or plan[u[0]][0] != 'se' or plan[u[0]][2] != op[1]:
-                continue
-            se = plan[u[0]]
-            u2 = users.get(se[1], [])
-            if len(u2) != 1 or plan[u2[0]][0] != 'addrelu' or se[1] == self.feature_name:
-                continue
-            ar = plan[u2[0]]
-            sc = ar[3] if ar[2] == se[1] else ar[2]
-            if sc == se[1] or self.shapes[sc] != self.shapes[op[1]] or self.shapes[op[1]][-1] % 4:
-                continue
-            repl[u2[0]] = ('seblock', ar[1], op[2], op[3], sc, se, op[1], se[1])
-            drop.update([j, u[0]])
-            self.se_fused[op[1]] = ('y', ar[1], op[2])
-            self.se_fused[se[1]] = ('s', ar[1], op[2])
-        return [repl.get(j, op) for j, op in enumerate(plan) if j not in drop]
-
-    def _defined_before(self, name, idx):
-        if name == 'images':
-            return True
-        for j in range(idx):
-            o = self.graph[j]
-            if o[1] == name or (o[0] == 'split' and o[3] == name) or (o[0] == 'shufsplit' and o[4] == name):
-                return True
-        return False
+    _op_weight_names = staticmethod(plan.op_weight_names)
 
     # ---- buffers --------------------------------------------------------------------------------------
     S16_OPS = ('conv', 'bn', 'bnstats', 'gconv', 'dwconv', 'gather', 'se', 'seblock', 'maxpool', 'addrelu', 'gap', 'dropout', 'fc')
@@ -669,8 +355,9 @@ class GraphNet(Network):
             print('%s: bf16 storage is not implemented for one of its ops; this net runs bf16 MFMA operands with fp32 tensors' % self.name)
         return ok
 
-    def _is16(self, name):
-        return name in self.h16
+    def _dispatch(self, phase):
+        """the handler of every plan op for one phase ('alloc' / 'fwd' / 'bwd'), in plan order; None: the kind has no work there"""
+        return [getattr(self, '_%s_%s' % (phase, op[0]), None) for op in self.plan]
 
     def _alloc(self, n):
         s16 = self._storage16()
@@ -679,118 +366,28 @@ class GraphNet(Network):
         self._act_s16 = s16
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
-        i16 = dict(dtype=torch.int16, device=dev)
-        # names of the tensors stored as bf16: conv / BN / grouped-conv / pool / add outputs; the stem conv's output (an fp32 GEMM),
-        # the pooled features and everything after them stay fp32
+        # h16: names of the tensors stored as bf16 (each kind's _alloc_ handler says whether its output is); the pooled features and
+        # everything after them stay fp32
         self.h16 = set()
-        if s16:
-            for op in self.plan:
-                if op[0] in ('gconv', 'dwconv', 'se', 'seblock', 'maxpool', 'addrelu') or (op[0] == 'bn' and len(self.shapes[op[1]]) == 3):
-                    self.h16.add(op[1])          # (a batch norm behind the pooling has a rank-1 output: the features stay fp32)
-                elif op[0] == 'conv':          # every conv writes bf16: the MFMA convs, the direct 3x3 stem, and the im2col stem (a 1x1 conv
-                    self.h16.add(op[1])        # of `kpad` bf16 columns on the bf16-source kernels)
-                elif op[0] == 'gather':
-                    self.h16.update(name for name, _ in op[2]['outs'])
-            self._pack_entries = []
-        # tensors whose GRADIENT is stored as bf16: the stored ones and the BN outputs folded into a gather (never stored themselves)
-        self.g16 = set(self.h16) | (set(self.folded) if s16 else set())
-        if s16:          # ... and the gated tensor of a fused SE block: its gradient g = dy * (out > 0) is stored (the shortcut's gradient too)
-            self.g16.update(op[7] for op in self.plan if op[0] == 'seblock')
-        if s16:          # every bf16-storage entry point reads its tensor input as bf16: an fp32 input would be misread silently
-            for op in self.plan:
-                ins = []
-                if op[0] == 'conv' and self.shapes[op[2]][-1] >= 32:
-                    ins = [op[2]]
-                elif op[0] in ('gconv', 'dwconv', 'maxpool', 'se'):
-                    ins = [op[2]]
-                elif op[0] == 'seblock':
-                    ins = [op[2], op[4]]
-                for x in ins:
-                    assert x in self.h16, 'bf16 storage: %s reads %s, which is stored as fp32' % (op[0] + ' ' + op[1], x)
+        self._pack_entries = []
         self.t = _Activations(self)
         self.bn = {}
         self.ident = {}
-        need = 1 << 20
-        q = _lib.query
-        for op in self.plan:
-            kind, out = op[0], op[1]
-            if kind == 'gather':
-                for name, _ in op[2]['outs']:
-                    self.t[name] = torch.empty((n,) + self.shapes[name], **(i16 if s16 else f32))
-                continue
-            shape = (n,) + self.shapes[out]
-            if kind != 'bnstats':
-                self.t[out] = torch.empty(shape, **(i16 if out in self.h16 else f32))
-            if kind in ('bn', 'bnstats', 'seblock', 'bnprelu'):
-                c = shape[-1]
-                if kind == 'bnprelu':
-                    need = max(need, q('fte_bn_prelu_ws_bytes', c))
-                self.bn[out] = dict(mean=torch.empty(c, **f32), rstd=torch.empty(c, **f32), scale=torch.empty(c, **f32),
-                                    shift=torch.empty(c, **f32), coef=torch.empty(3 * c, **f32))
-                need = max(need, q('fte_bn_ws_bytes', c))
-            elif kind == 'conv':
-                ih, iw, cin = self.shapes[op[2]]
-                k = self.spec[op[3]][0][0]
-                cout = shape[-1]
-                if cin >= 32:
-                    need = max(need, q('fte_conv2d_fwd_ws_bytes', n, ih, iw, cin, cout, k, op[4]),
-                               q('fte_conv2d_dgrad_ws_bytes', n, ih, iw, cin, cout, k, op[4]),
-                               q('fte_conv2d_wgrad_ws_bytes', n, ih, iw, cin, cout, k, op[4]),
-                               q('fte_conv2d_bn_fwd_ws_bytes', n, ih, iw, cin, cout, k, op[4]),
-                               q('fte_conv2d_dgrad_bn_ws_bytes', n, ih, iw, cin, cout, k, op[4]))
-                    if s16:          # bf16 packs of the filter: HWIO (data gradient) and [tap][cout][cin] (forward), refreshed every step
-                        self._pack_entries.append((op[3], self.variables[op[3]].offset, k, cin, cout))
-                elif self._direct_stem(k, cin, cout):
-                    need = max(need, q('fte_conv3x3_first_wgrad_ws_bytes', n, ih, iw, cin, cout, op[4]))
-                else:
-                    oh, ow, _ = self.shapes[out]
-                    kpad = stem_kpad(k, cin)
-                    self.cols = torch.empty(n * oh * ow, kpad, **(i16 if s16 else f32))
-                    need = max(need, q('fte_gemm_ws_bytes', n * oh * ow, cout, kpad))
-                    if s16:          # the stem as a 1x1 conv of kpad bf16 columns: packs like any other conv's, [1, 1, kpad, cout]
-                        self._pack_entries.append((op[3], self.variables[op[3]].offset, 1, kpad, cout))
-                        need = max(need, q('fte_conv2d_fwd_ws_bytes', n, oh, ow, kpad, cout, 1, 1), q('fte_conv2d_bn_fwd_ws_bytes', n, oh, ow, kpad, cout, 1, 1),
-                                   q('fte_conv2d_wgrad_ws_bytes', n, oh, ow, kpad, cout, 1, 1))
-            elif kind == 'dwconv':
-                ih, iw, cc = self.shapes[op[2]]
-                need = max(need, q('fte_dwconv3x3_wgrad_ws_bytes', n, ih, iw, cc, op[4]))
-            elif kind == 'gconv':
-                ih, iw, cc = self.shapes[op[2]]
-                need = max(need, q('fte_gconv3x3_wgrad_ws_bytes', n, ih, iw, cc, op[5], op[4]))
-                if cc % 32 == 0 and cc // op[5] in (4, 8, 16, 32):
-                    need = max(need, q('fte_gconv3x3_wgrad_bf16_ws_bytes', n, ih, iw, cc, op[5], op[4]),
-                               q('fte_gconv3x3_bn_ws_bytes', n, ih, iw, cc, op[4]))
-            if kind in ('se', 'seblock'):
-                cc = shape[-1]
-                hd = self._se_names(op[5] if kind == 'seblock' else op)[4]
-                if kind == 'seblock':          # per-image sums of the backward pass, the squeeze in xhat units
-                    for nm in ('xm', 's1', 's2'):
-                        self.t[out + '/' + nm] = torch.empty(n, cc, **f32)
-                self.t[out + '/sq'] = torch.empty(n, cc, **f32)
-                self.t[out + '/hid'] = torch.empty(n, hd, **f32)
-                self.t[out + '/gate'] = torch.empty(n, cc, **f32)
-                need = max(need, q('fte_gemm_ws_bytes', n, cc, hd), q('fte_gemm_ws_bytes', n, hd, cc))
-                # backward scratch: dsq is shared by all SE blocks of a width; dgate / dhid are per block -- the gate's weight gradients
-                # read them on the side stream while the walk has moved on to the next block
-                if ('se', 'dsq', cc) not in self.ident:
-                    self.ident[('se', 'dsq', cc)] = torch.empty(n, cc, **f32)
-                self.ident[('se', out, 'dgate')] = torch.empty(n, cc, **f32)
-                self.ident[('se', out, 'dhid')] = torch.empty(n, hd, **f32)
-            elif kind == 'addrelu':
-                cc = shape[-1]
-                if cc not in self.ident:
-                    self.ident[cc] = (torch.ones(cc, **f32), torch.zeros(cc, **f32))
-            elif kind == 'maxpool':
-                self.t[out + '/idx'] = torch.empty(shape, dtype=torch.uint8, device=dev)
-            elif kind == 'dropout':
-                self.t[out + '/mask'] = torch.empty(shape, **f32)
-            elif kind == 'fc' and self.spec[op[3]][1] == 'embed_w':
-                need = max(need, q('fte_gemm_ws_bytes', n, shape[-1], self.spec[op[3]][0][0]))
-            elif kind == 'fc':
-                need = max(need, q('fte_gemm_ws_bytes', n, self.sub_centers * self.cpad, self.shapes[op[2]][0]))
+        w = _Walk()
+        w.n, w.s16, w.need = n, s16, 1 << 20
+        for op, handler in zip(self.plan, self._alloc_ops):
+            if handler is None:                          # (a kind no walk knows: the forward walk raises on it)
+                self._alloc_out(w, op, False, op[1])
+            else:
+                handler(w, op)
+        # tensors whose GRADIENT is stored as bf16: the stored ones, the BN outputs folded into a gather (never stored themselves) and the
+        # gated tensor of a fused SE block: its gradient g = dy * (out > 0) is stored (the shortcut's gradient too)
+        self.g16 = set(self.h16)
         if s16:
+            self.g16.update(self.folded)
+            self.g16.update(op.s for op in self.plan if op[0] == 'seblock')
             from ._packs import FilterPacks
-            self.packs = FilterPacks(self._pack_entries, dev, head=int(os.environ.get('FTE_PACK_HEAD', '4')))
+            self.packs = FilterPacks(self._pack_entries, dev, head=self.opt.pack_head)
             self.w16, self.w16t = self.packs.w16, self.packs.w16t
         self.G = torch.empty(n, self.sub_centers * self.cpad, **f32)
         self.loss_rows = torch.empty(n, **f32)
@@ -802,14 +399,216 @@ class GraphNet(Network):
             self.wn, self.colcoef = (torch.empty(self.sub_centers * self.cpad, **f32) for _ in range(2))
         if self.head == 'adaface':
             self.a_rows, self.b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
-        need = max(need, 4 * n * fdim, 12 * n * n)
+        need = max(w.need, 4 * n * fdim, 12 * n * n)
         self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
         self.ws_bytes = self.ws.numel() * 4
         # filter gradients run on a second HIP stream beside the data-gradient chain (backward_body): their own workspace
-        self.side = side_stream(dev, int(os.environ.get('FTE_SIDE_PRIO', '0'))) if os.environ.get('FTE_SIDE_STREAM', '1') != '0' else None
+        self.side = side_stream(dev, self.opt.side_prio) if self.opt.side_stream else None
         self.ws_side = torch.empty_like(self.ws) if self.side is not None else self.ws
-        self.side_batch = int(os.environ.get('FTE_SIDE_BATCH', '3'))
+        self.side_batch = self.opt.side_batch
         self._act_n = n
+
+    def _alloc_out(self, w, op, stored16, name=None):
+        """the output tensor of a plan op; `stored16`: as bf16 under bf16 storage -> its shape with the batch dimension"""
+        name = op.out if name is None else name
+        shape = (w.n,) + self.shapes[name]
+        if stored16 and w.s16:
+            self.h16.add(name)
+        self.t[name] = torch.empty(shape, dtype=torch.int16 if name in self.h16 else torch.float32, device=self.device)
+        return shape
+
+    def _alloc_bn(self, w, op, stored=True):
+        """scale / shift / statistics of a BN layer (and its output: bf16 unless it lies behind the pooling, where the features stay fp32)"""
+        out = op.out
+        c = self.shapes[out][-1]
+        if stored:
+            self._alloc_out(w, op, len(self.shapes[out]) == 3)
+        self.bn[out] = dict((k, self._f32(c)) for k in ('mean', 'rstd', 'scale', 'shift'))
+        self.bn[out]['coef'] = self._f32(3 * c)
+        w.need = max(w.need, _lib.query('fte_bn_ws_bytes', c))
+
+    def _f32(self, *shape):
+        return torch.empty(*shape, dtype=torch.float32, device=self.device)
+
+    def _reads16(self, w, op, *names):
+        """every bf16-storage entry point reads its tensor input as bf16: an fp32 input would be misread silently"""
+        if w.s16:
+            for x in names:
+                assert x in self.h16, 'bf16 storage: %s reads %s, which is stored as fp32' % (op[0] + ' ' + op.out, x)
+
+    # ---- the pieces several kinds share -----------------------------------------------------------------
+    def _bn_args(self, op, upd):
+        """(gamma, beta, mean, rstd, scale, shift, moving_mean, moving_variance, eps, decay) of a BN plan op; the moving statistics
+        are None when they are not to move (`upd` False)"""
+        b, pre = self.bn[op.out], op.pre
+        return (self.view(pre + '/gamma'), self.view(pre + '/beta'), b['mean'], b['rstd'], b['scale'], b['shift'],
+                self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None, self.bn_eps, self.bn_decay)
+
+    def _bn_stats(self, w, op, x, x16):
+        """The statistics-only pass of BN plan op `op` over its input x: batch statistics -> mean / rstd / scale / shift (training), or
+        scale / shift from the moving statistics.  `x16`: x is stored as bf16."""
+        c = self.shapes[op.out][-1]
+        if not w.is_training:
+            ba = self._bn_args(op, True)
+            w.call('fte_bn_infer_coef', ba[0], ba[1], ba[6], ba[7], ba[4], ba[5], c, self.bn_eps, w.st)
+            return
+        ba = self._bn_args(op, w.upd)
+        rows = x.numel() // c
+        if w.s16:
+            w.call('fte_bn_train_stats_s16', x, *ba[:8], rows, c, ba[8], ba[9], 1 if x16 else 0, self.ws, self.ws_bytes, w.st)
+        else:
+            w.call('fte_bn_train_stats', x, *ba[:8], rows, c, ba[8], ba[9], self.ws, self.ws_bytes, w.st)
+
+    def _sflag(self, w, inp):
+        """the storage word of the BN / SE entry points: bit 0 = the input is bf16, bit 1 = the output is; 0 outside bf16 storage"""
+        return ((1 if inp in self.h16 else 0) | 2) if w.s16 else 0
+
+    def _se_buffers(self, out):
+        T = self.t
+        return T[out + '/sq'], T[out + '/hid'], T[out + '/gate']
+
+    def _alloc_se_gate(self, w, out, se, c):
+        n, hd = w.n, se.hidden
+        self.t[out + '/sq'] = self._f32(n, c)
+        self.t[out + '/hid'] = self._f32(n, hd)
+        self.t[out + '/gate'] = self._f32(n, c)
+        w.need = max(w.need, _lib.query('fte_gemm_ws_bytes', n, c, hd), _lib.query('fte_gemm_ws_bytes', n, hd, c))
+        # backward scratch: dsq is shared by all SE blocks of a width; dgate / dhid are per block -- the gate's weight gradients
+        # read them on the side stream while the walk has moved on to the next block
+        if ('se', 'dsq', c) not in self.ident:
+            self.ident[('se', 'dsq', c)] = self._f32(n, c)
+        self.ident[('se', out, 'dgate')] = self._f32(n, c)
+        self.ident[('se', out, 'dhid')] = self._f32(n, hd)
+
+    def _se_gate_fwd(self, w, out, se, c, how):
+        """squeeze -> hidden -> gate: the SE gate's two dense layers with ReLU / sigmoid.  `how`: 'small' (fte_dense_small, one launch
+        each), 'act' (the GEMM with the activation in the same pass over the output) or 'plain' (activations as launches of their own)"""
+        call, st, n, hd = w.call, w.st, w.n, se.hidden
+        sq, hid, gate = self._se_buffers(out)
+        w1, b1, w2, b2 = self.view(se.w1), self.view(se.b1), self.view(se.w2), self.view(se.b2)
+        if how == 'small':
+            call('fte_dense_small', sq, w1, b1, None, hid, n, hd, c, 0, 1, st)
+            call('fte_dense_small', hid, w2, b2, None, gate, n, c, hd, 0, 2, st)
+        elif how == 'act':
+            call('fte_gemm_nn_act', sq, w1, b1, hid, n, hd, c, 1, self.ws, self.ws_bytes, st)
+            call('fte_gemm_nn_act', hid, w2, b2, gate, n, c, hd, 2, self.ws, self.ws_bytes, st)
+        else:
+            call('fte_gemm_nn', sq, w1, b1, hid, n, hd, c, self.ws, self.ws_bytes, st)
+            call('fte_act_fwd', hid, hid, hid.numel(), 0, st)
+            call('fte_gemm_nn', hid, w2, b2, gate, n, c, hd, self.ws, self.ws_bytes, st)
+            call('fte_act_fwd', gate, gate, gate.numel(), 1, st)
+
+    def _se_gate_bwd(self, w, out, se, c, small):
+        """dgate = d(pre-sigmoid) -> dsq, the gradient of the squeeze, through the gate's two dense layers.  The four parameter
+        gradients feed nothing but the optimizer: side stream, like every filter gradient.  `small`: fte_dense_small, which takes
+        the ReLU mask in the same launch.  -> dsq"""
+        call, st, n, hd = w.call, w.st, w.n, se.hidden
+        sq, hid, _ = self._se_buffers(out)
+        # scratch preallocated in _alloc (three allocator calls per SE block and step otherwise)
+        dgate, dhid, dsq = self.ident[('se', out, 'dgate')], self.ident[('se', out, 'dhid')], self.ident[('se', 'dsq', c)]
+        self._wgrad(w, 'fte_gemm_tn', dgate, hid, dgate, self.view(se.w2, self.grads), n, c, hd, w.wws, self.ws_bytes, w.wst)
+        self._wgrad(w, 'fte_reduce_rows', dgate, dgate, self.view(se.b2, self.grads), None, 1, n, c, 1, 1.0, w.wst)
+        if small:                                      # d(pre-ReLU) = (dgate W2^T) * (hid > 0) in one launch
+            call('fte_dense_small', dgate, self.view(se.w2), None, hid, dhid, n, hd, c, 1, 0, st)
+        else:
+            call('fte_gemm_nt', dgate, self.view(se.w2), None, None, 0, None, dhid, None, n, c, hd, self.ws, self.ws_bytes, st)
+            call('fte_act_bwd', dhid, hid, dhid, dhid.numel(), 0, st)                        # -> d(pre-ReLU)
+        self._wgrad(w, 'fte_gemm_tn', dhid, sq, dhid, self.view(se.w1, self.grads), n, hd, c, w.wws, self.ws_bytes, w.wst)
+        self._wgrad(w, 'fte_reduce_rows', dhid, dhid, self.view(se.b1, self.grads), None, 1, n, hd, 1, 1.0, w.wst)
+        if small:
+            call('fte_dense_small', dhid, self.view(se.w1), None, None, dsq, n, c, hd, 1, 0, st)
+        else:
+            call('fte_gemm_nt', dhid, self.view(se.w1), None, None, 0, None, dsq, None, n, hd, c, self.ws, self.ws_bytes, st)
+        return dsq
+
+    def _wait_shortcut(self, w, *names):
+        """the shortcut branch (side stream) has written these tensors"""
+        for nm in names:
+            if nm in w.sc_ev:
+                w.main.wait_event(w.sc_ev.pop(nm))
+
+    def _wgrad(self, w, name, dy, *args):
+        """a filter-gradient launch: queued for the side stream (released by _flush), or issued at once without one"""
+        if w.side is None:
+            w.call(name, *args)
+        else:
+            w.pending.append((name, dy, args))
+
+    def _flush(self, w, limit=0):
+        if len(w.pending) > limit:
+            w.side.wait_event(w.main.record_event())
+            for name, dy, args in w.pending:
+                dy.record_stream(w.side)
+                w.call(name, *args)
+            del w.pending[:]
+
+    def _bn_below(self, w, name):
+        """arguments of the BN layer whose output `name` a fused data gradient lands on, or None"""
+        bj = self.fuse_bwd.get(name)
+        if bj is None:
+            return None
+        bop = self.plan[bj]
+        T = self.t
+        if w.s16 and not (bop.inp in self.h16 and bop.out in self.h16):
+            return None
+        b, pre = self.bn[bop.out], bop.pre
+        zmask = bop.relu and bop.res is None
+        return (T[bop.inp], T[bop.out] if bop.res is not None else None, self.view(pre + '/gamma'), b['mean'], b['rstd'],
+                b['scale'] if zmask else None, b['shift'] if zmask else None), \
+               (self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), b['coef'])
+
+    def _folds(self, w, bj):
+        """does the consumer of BN plan op bj take the normalise pass into its loader? (bf16 storage, training, statistics fused)"""
+        cj = self.fold_apply.get(bj)
+        if cj is None or not (w.s16 and w.is_training and bj in w.stats_done):
+            return False
+        cop = self.plan[cj]
+        ih, iw, cin = self.shapes[cop.inp]
+        if cop[0] == 'gconv':                       # (its fused launch carries the fold: FTE_BN_FUSE_3X3=0 takes both away)
+            return cop.stride == 1 and self._gconv_pack(cop) is not None and self.fuse_3x3
+        return bool(_lib.query('fte_conv2d_bn_fwd_folds', w.n, ih, iw, cin, self.shapes[cop.out][-1], self.spec[cop.wname][0][0], cop.stride, 1))
+
+    def _fold_args(self, w, j):
+        """(x, in_scale, in_shift, y_side) of consumer plan op j"""
+        bj = w.folded_in.get(j)
+        if bj is None:
+            return self.t[self.plan[j].inp], None, None, None
+        bop = self.plan[bj]
+        b = self.bn[bop.out]
+        return self.t[bop.inp], b['scale'], b['shift'], self.t[bop.out]
+
+    def _gconv_pack(self, op):
+        """(forward, dgrad) packed bf16 filters of a grouped 3x3 that runs on the matrix cores -- bf16 MFMA mode,
+        4 / 8 / 16 / 32 channels per group -- else None (fp32 vector kernels)."""
+        c = self.shapes[op.inp][-1]
+        if c % 32 or (c // op.groups) not in (4, 8, 16, 32) or _lib.get_mfma_dtype() != 'bf16' or not self.opt.gconv_mfma:
+            return None
+        pk = self._gpacks.get(op.wname)
+        if pk is None:
+            words = (c // 32) * 9 * 1024
+            pk = self._gpacks[op.wname] = (torch.empty(words, dtype=torch.int16, device=self.device),
+                                           torch.empty(words, dtype=torch.int16, device=self.device))
+        return pk
+
+    def _direct_stem(self, k, cin, cout):
+        return plan.direct_stem(k, cin, cout, self.opt)
+
+    def _se_small(self, c, hd):
+        """the SE gate's dense layers through fte_dense_small (one launch each)?  FTE_SE_DENSE=0: fte_gemm_* (A/B hook)"""
+        return c % 128 == 0 and hd % 128 == 0 and self.opt.se_dense
+
+    def _scr(self, c, i):
+        key = ('scr', c, i)
+        if key not in self.ident:
+            self.ident[key] = torch.empty(c, dtype=torch.float32, device=self.device)
+        return self.ident[key]
+
+    def _new(self, name):
+        """a gradient buffer for tensor `name`: bf16 where the tensor (or, for a BN output folded into a gather, its gradient) is"""
+        if name in self.folded:                  # never stored: no tensor to take the layout from
+            z = self.t[self.folded[name][0]]
+            return torch.empty(z.shape, dtype=torch.int16 if name in self.g16 else torch.float32, device=self.device)
+        return torch.empty_like(self.t[name])
 
     # ---- forward ----------------------------------------------------------------------------------------
     def _check_images(self, images):
@@ -819,23 +618,40 @@ class GraphNet(Network):
 
     def _run_forward(self, images, is_training):
         x = self._check_images(images)
-        n, h, w, ch = x.shape
-        assert (h, w, ch) == self.in_hwc, ((h, w, ch), self.in_hwc)
+        n, h, wd, ch = x.shape
+        assert (h, wd, ch) == self.in_hwc, ((h, wd, ch), self.in_hwc)
         self._alloc(n)
-        st = _stream()
-        call = _lib.call
-        T = self.t
-        T['images'] = x
-        s16 = self._act_s16
-        h16 = self.h16
-        pack_ev = None
-        side_packs = None
+        self.t['images'] = x
+        w = _Walk()
+        w.call, w.n, w.is_training, w.s16, w.sfx = _lib.call, n, is_training, self._act_s16, '_s16' if self._act_s16 else ''
+        w.upd = self.update_moving_stats
+        w.main, w.side = torch.cuda.current_stream(), self.side
+        w.st, w.ws, w.on_side = w.main.cuda_stream, self.ws, False
+        w.pack_ev, w.packs_pending = None, False
+        w.stats_done = set()                             # BN plan ops whose statistics came out of the producing conv's epilogue
+        w.folded_in = {}                                 # consumer plan op -> BN plan op whose normalise pass its loader applies
+        w.sc_ev = {}                                     # shortcut tensor -> event of the side stream that completes it
+        self._start_regularizer(w)
+        if w.s16:
+            self._start_packs(w)
+        st_main = w.st
+        side_ops = self.shortcut_fwd if (self.side is not None and is_training) else ()
+        sst = self.side.cuda_stream if side_ops else None
+        for j, (op, handler) in enumerate(zip(self.plan, self._fwd_ops)):
+            if handler is None:
+                raise RuntimeError('op %s must have been fused away' % op[0])
+            if j in side_ops:
+                w.on_side, w.st, w.ws = True, sst, self.ws_side
+            else:
+                w.on_side, w.st, w.ws = False, st_main, self.ws
+            handler(w, j, op)
+
+    def _start_regularizer(self, w):
         self._reg_ev = None
-        if is_training and self.side is not None and os.environ.get('FTE_REG_SIDE', '1') != '0':
+        if w.is_training and self.side is not None and self.opt.reg_side:
             # Network._regularize's sum over the decayed weights (one pass over the arena: 25-40 us) depends on nothing the walk computes:
             # it runs on the side stream under the first layers instead of between the loss head's launches; loss_function waits for it
-            main = torch.cuda.current_stream()
-            self.side.wait_stream(main)
+            self.side.wait_stream(w.main)
             nreg = self.arena_size - self.small_end
             # (into a scratch scalar of its own, not the displayed slot: the previous step's reg_loss stays readable until this step's
             # loss_function copies the new value in; the scale used is remembered -- a tower_scale / weight_decay changed between
@@ -843,354 +659,589 @@ class GraphNet(Network):
             if getattr(self, '_reg_scratch', None) is None:
                 self._reg_scratch = torch.zeros(4, dtype=torch.float32, device=self.params.device)
             self._reg_scale = 0.5 * self.weight_decay * self.tower_scale
-            call('fte_sumsq', self.params[self.small_end:], nreg, self._reg_scale,
-                 self._reg_scratch[0:1], self.ws_side, self.ws_bytes, self.side.cuda_stream)
+            w.call('fte_sumsq', self.params[self.small_end:], nreg, self._reg_scale,
+                   self._reg_scratch[0:1], self.ws_side, self.ws_bytes, self.side.cuda_stream)
             self._reg_ev = self.side.record_event()
-        if s16:
-            # every filter's bf16 packs, refreshed once per step.  The walk's first layers need only THEIR forward packs: those are
-            # made here; the rest -- the other layers' forward packs, every HWIO pack (read by the backward pass only) and the
-            # grouped convs' packs -- are made on the side stream under the first layers, and the first conv outside the head
-            # waits for them (0.27 ms of launches off the ResNeXt-50 step's critical path at 128 images).
-            side = self.side
-            if side is not None and self.packs.head_names != set(self.w16t):
-                self.packs.refresh_head(self.params, st)
 
-                def side_packs():
-                    main = torch.cuda.current_stream()
-                    side.wait_stream(main)
-                    sst = side.cuda_stream
-                    self.packs.refresh_rest(self.params, sst)
-                    for op in self.plan:
-                        if op[0] == 'gconv':
-                            pk = self._gconv_pack(op)
-                            if pk is not None:
-                                call('fte_gconv3x3_pack_bf16', self.view(op[3]), pk[0], pk[1], self.shapes[op[2]][-1], op[5], sst)
-                    return side.record_event()
-                # A 7x7 stem's im2col (150-200 MB of strided traffic) and the packs (the same again) choke each other when they run
-                # side by side: im2col 74 -> 240-260 us beside ResNet-50's 47 MB of packs (profiles/r5_resnet50_*).  The packs start
-                # behind the im2col instead, under the stem's GEMM (FTE_PACK_AFTER_STEM=0: at the start of the walk, as before).
-                first = self.plan[0]
-                stem_cols = first[0] == 'conv' and self.shapes[first[2]][-1] < 32 and not self._direct_stem(self.spec[first[3]][0][0], self.shapes[first[2]][-1], self.shapes[first[1]][-1])
-                if not (stem_cols and os.environ.get('FTE_PACK_AFTER_STEM', '1') != '0'):
-                    pack_ev = side_packs()
-                    side_packs = None
-            else:
-                self.packs.refresh(self.params, st)
-        stats_done = set()                               # BN plan ops whose statistics came out of the producing conv's epilogue
-        folded_in = {}                                   # consumer plan op -> BN plan op whose normalise pass its loader applies
-        upd = self.update_moving_stats
+    def _start_packs(self, w):
+        """Every filter's bf16 packs, refreshed once per step.  The walk's first layers need only THEIR forward packs: those are
+        made here; the rest -- the other layers' forward packs, every HWIO pack (read by the backward pass only) and the
+        grouped convs' packs -- are made on the side stream under the first layers, and the first conv outside the head
+        waits for them (0.27 ms of launches off the ResNeXt-50 step's critical path at 128 images)."""
+        if self.side is None or self.packs.head_names == set(self.w16t):
+            self.packs.refresh(self.params, w.st)
+            return
+        self.packs.refresh_head(self.params, w.st)
+        # A 7x7 stem's im2col (150-200 MB of strided traffic) and the packs (the same again) choke each other when they run
+        # side by side: im2col 74 -> 240-260 us beside ResNet-50's 47 MB of packs (profiles/r5_resnet50_*).  The packs start
+        # behind the im2col instead, under the stem's GEMM (FTE_PACK_AFTER_STEM=0: at the start of the walk, as before).
+        first = self.plan[0]
+        stem_cols = first[0] == 'conv' and self.shapes[first.inp][-1] < 32 and \
+            not self._direct_stem(self.spec[first.wname][0][0], self.shapes[first.inp][-1], self.shapes[first.out][-1])
+        if stem_cols and self.opt.pack_after_stem:
+            w.packs_pending = True
+        else:
+            w.pack_ev = self._side_packs(w)
 
-        def folds(bj):
-            """does the consumer of BN plan op bj take the normalise pass into its loader? (bf16 storage, training, statistics fused)"""
-            cj = self.fold_apply.get(bj)
-            if cj is None or not (s16 and is_training and bj in stats_done):
-                return False
-            cop = self.plan[cj]
-            ih_, iw_, cin_ = self.shapes[cop[2]]
-            if cop[0] == 'gconv':                       # (its fused launch carries the fold: FTE_BN_FUSE_3X3=0 takes both away)
-                return cop[4] == 1 and self._gconv_pack(cop) is not None and self.fuse_3x3
-            return bool(_lib.query('fte_conv2d_bn_fwd_folds', n, ih_, iw_, cin_, self.shapes[cop[1]][-1], self.spec[cop[3]][0][0], cop[4], 1))
-
-        def fold_args(j):
-            """(x, in_scale, in_shift, y_side) of consumer plan op j"""
-            bj = folded_in.get(j)
-            if bj is None:
-                return T[self.plan[j][2]], None, None, None
-            bop = self.plan[bj]
-            b = self.bn[bop[1]]
-            return T[bop[2]], b['scale'], b['shift'], T[bop[1]]
-
-        def bn_args(j):
-            bop = self.plan[j]
-            b, pre = self.bn[bop[1]], bop[3]
-            return (self.view(pre + '/gamma'), self.view(pre + '/beta'), b['mean'], b['rstd'], b['scale'], b['shift'],
-                    self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None, self.bn_eps, self.bn_decay)
-        main_s = torch.cuda.current_stream()
-        sc_side = self.side if (self.side is not None and is_training and self.shortcut_fwd) else None
-        sc_ev = {}                                       # shortcut tensor -> event of the side stream that completes it
-        st_main, ws_main = st, self.ws
-        for j, op in enumerate(self.plan):
-            kind, out = op[0], op[1]
-            on_side = sc_side is not None and j in self.shortcut_fwd
-            st, ws_j = (sc_side.cuda_stream, self.ws_side) if on_side else (st_main, ws_main)
-            if kind == 'conv':
-                _, _, inp, wname, stride = op
-                ih, iw, cin = self.shapes[inp]
-                k = self.spec[wname][0][0]
-                cout = self.shapes[out][-1]
-                if on_side:
-                    sc_side.wait_event(main_s.record_event())          # the block's input is complete (the packs were made on this stream)
-                if not on_side and pack_ev is not None and cin >= 32 and wname not in self.packs.head_names:
-                    torch.cuda.current_stream().wait_event(pack_ev)          # the side stream's packs (once: every later layer is behind this wait)
-                    pack_ev = None
-                if cin >= 32 and is_training and j in self.fuse_fwd and (k == 1 or not s16 or self.fuse_3x3):          # conv + the batch statistics of its output ("BN fusion")
-                    xin, isc, ish, yside = fold_args(j)
-                    call('fte_conv2d_bn_fwd', xin, self.w16t[wname] if s16 else self.view(wname), T[out], *bn_args(self.fuse_fwd[j]),
-                         isc, ish, yside, n, ih, iw, cin, cout, k, stride, 1 if s16 else 0, ws_j, self.ws_bytes, st)
-                    stats_done.add(self.fuse_fwd[j])
-                elif cin >= 32 and s16:          # bf16 storage: bf16 x in, bf16 z out, filters packed once per step
-                    call('fte_conv2d_fwd_s16', T[inp], self.w16t[wname], None, None, None, None, T[out], None, None,
-                         n, ih, iw, cin, cout, k, stride, ws_j, self.ws_bytes, st)
-                elif cin >= 32:
-                    call('fte_conv2d_fwd', T[inp], self.view(wname), None, None, None, None, T[out],
-                         n, ih, iw, cin, cout, k, stride, ws_j, self.ws_bytes, st)
-                elif self._direct_stem(k, cin, cout):          # 3x3 stem of 32 / 64 stored filters: the direct MFMA kernel
-                    if s16:
-                        call('fte_conv3x3_first_fwd_s16', T[inp], self.view(wname), None, None, None, T[out], n, ih, iw, cin, cout, stride, st)
-                    else:
-                        call('fte_conv3x3_first_fwd', T[inp], self.view(wname), None, None, None, T[out], n, ih, iw, cin, cout, stride, st)
-                elif s16:                                      # other stems (7x7), bf16 storage: bf16 columns, then a 1x1 conv of kpad channels
-                    oh, ow, _ = self.shapes[out]
-                    kpad = stem_kpad(k, cin)
-                    call('fte_im2col_first_s16', T[inp], self.cols, n, ih, iw, cin, k, stride, kpad, st)
-                    if side_packs is not None:                 # the rest of the filter packs, from here on (see above)
-                        pack_ev = side_packs()
-                        side_packs = None
-                    if is_training and j in self.fuse_fwd:
-                        call('fte_conv2d_bn_fwd', self.cols, self.w16t[wname], T[out], *bn_args(self.fuse_fwd[j]), None, None, None,
-                             n, oh, ow, kpad, cout, 1, 1, 1, self.ws, self.ws_bytes, st)
-                        stats_done.add(self.fuse_fwd[j])
-                    else:
-                        call('fte_conv2d_fwd_s16', self.cols, self.w16t[wname], None, None, None, None, T[out], None, None,
-                             n, oh, ow, kpad, cout, 1, 1, self.ws, self.ws_bytes, st)
-                else:                                          # other stems (7x7): im2col + dense MFMA GEMM
-                    oh, ow, _ = self.shapes[out]
-                    kpad = stem_kpad(k, cin)
-                    call('fte_im2col_first', T[inp], self.cols, n, ih, iw, cin, k, stride, kpad, st)
-                    call('fte_gemm_nn', self.cols, self.view(wname), None, T[out], n * oh * ow, cout, kpad,
-                         self.ws, self.ws_bytes, st)
-            elif kind == 'dwconv':
-                ih, iw, c = self.shapes[op[2]]
-                call('fte_dwconv3x3_fwd_s16' if s16 else 'fte_dwconv3x3_fwd', T[op[2]], self.view(op[3]), T[out], n, ih, iw, c, op[4], st)
-            elif kind == 'gather':
-                a, b = op[2]['ins']
-                fa, fb = self.folded.get(a), self.folded.get(b)
-                outs = op[2]['outs']
-                if fa is None and fb is None and len(outs) == 1:
-                    name, table = outs[0]
-                    co = self.shapes[name][-1]
-                    call('fte_channel_gather_s16' if s16 else 'fte_channel_gather', T[a], T[b] if b else None, T[name], table, T[name].numel() // co,
-                         self.shapes[a][-1], self.shapes[b][-1] if b else 0, co, st)
-                else:                                          # both halves in one launch, BN applied to a folded source
-                    sa = (T[fa[0]], self.bn[a]['scale'], self.bn[a]['shift'], fa[1]) if fa else (T[a], None, None, 0)
-                    sb = (T[fb[0]], self.bn[b]['scale'], self.bn[b]['shift'], fb[1]) if fb else (T[b] if b else None, None, None, 0)
-                    (n0, t0), (n1, t1) = outs[0], (outs[1] if len(outs) > 1 else (None, None))
-                    co0 = self.shapes[n0][-1]
-                    call('fte_channel_gather_affine_s16' if s16 else 'fte_channel_gather_affine', sa[0], sb[0], T[n0], t0, co0, T[n1] if n1 else None, t1,
-                         self.shapes[n1][-1] if n1 else 0, T[n0].numel() // co0, self.shapes[a][-1],
-                         self.shapes[b][-1] if b else 0, sa[1], sa[2], sa[3], sb[1], sb[2], sb[3], st)
-            elif kind == 'bnstats':
-                _, _, inp, pre, _, _ = op
-                b = self.bn[out]
-                c = self.shapes[out][-1]
-                rows = T[inp].numel() // c
-                if j in stats_done:
-                    pass
-                elif is_training and s16:
-                    upd = self.update_moving_stats
-                    call('fte_bn_train_stats_s16', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         b['mean'], b['rstd'], b['scale'], b['shift'],
-                         self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                         rows, c, self.bn_eps, self.bn_decay, 1 if inp in h16 else 0, self.ws, self.ws_bytes, st)
-                elif is_training:
-                    upd = self.update_moving_stats
-                    call('fte_bn_train_stats', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         b['mean'], b['rstd'], b['scale'], b['shift'],
-                         self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                         rows, c, self.bn_eps, self.bn_decay, self.ws, self.ws_bytes, st)
-                else:
-                    call('fte_bn_infer_coef', self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], b['scale'], b['shift'], c, self.bn_eps, st)
-            elif kind == 'bn':
-                _, _, inp, pre, res, relu = op
-                b = self.bn[out]
-                c = self.shapes[out][-1]
-                rows = T[out].numel() // c
-                resbuf = T[res] if res is not None else None
-                if res is not None and res in sc_ev:
-                    main_s.wait_event(sc_ev.pop(res))                  # the shortcut branch (side stream) has written it
-                if j in stats_done and folds(j):  # ... which the consumer's operand loader takes over (it also writes T[out])
-                    folded_in[self.fold_apply[j]] = j
-                elif j in stats_done:            # scale / shift are there already: the normalise pass alone
-                    assert res is None or not s16 or res in h16, 'bf16 storage: the shortcut of %s is an fp32 tensor' % out
-                    call('fte_bn_apply', T[inp], b['scale'], b['shift'], resbuf, T[out], rows, c, relu, ((1 if inp in h16 else 0) | 2) if s16 else 0, st)
-                elif s16:
-                    assert res is None or res in h16, 'bf16 storage: the shortcut of %s is an fp32 tensor' % out
-                    fl = (1 if inp in h16 else 0) | 2
-                    if is_training:
-                        upd = self.update_moving_stats
-                        call('fte_bn_train_fwd_s16', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'), resbuf, T[out],
-                             b['mean'], b['rstd'], b['scale'], b['shift'],
-                             self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                             rows, c, self.bn_eps, self.bn_decay, relu, fl, ws_j, self.ws_bytes, st)
-                    else:
-                        call('fte_bn_infer_fwd_s16', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                             self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], resbuf, T[out],
-                             b['scale'], b['shift'], rows, c, self.bn_eps, relu, fl, st)
-                elif is_training:
-                    upd = self.update_moving_stats
-                    call('fte_bn_train_fwd', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'), resbuf, T[out],
-                         b['mean'], b['rstd'], b['scale'], b['shift'],
-                         self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                         rows, c, self.bn_eps, self.bn_decay, relu, ws_j, self.ws_bytes, st)
-                else:
-                    call('fte_bn_infer_fwd', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], resbuf, T[out],
-                         b['scale'], b['shift'], rows, c, self.bn_eps, relu, st)
-                if on_side:
-                    sc_ev[out] = sc_side.record_event()
-            elif kind == 'bnprelu':
-                _, _, inp, pre, aname = op
-                b = self.bn[out]
-                c = self.shapes[out][-1]
-                rows = T[out].numel() // c
-                if not is_training:                            # moving statistics -> scale / shift, then the apply (fte.h)
-                    call('fte_bn_prelu_infer_fwd', T[inp], self.view(pre + '/gamma'), self.view(pre + '/beta'), self.state[pre + '/moving_mean'],
-                         self.state[pre + '/moving_variance'], self.view(aname), T[out], b['scale'], b['shift'], rows, c, self.bn_eps, st)
-                else:
-                    if j not in stats_done:                    # (else the producing conv's epilogue left the batch statistics)
-                        ba = bn_args(j)
-                        call('fte_bn_train_stats', T[inp], *ba[:8], rows, c, ba[8], ba[9], ws_j, self.ws_bytes, st)
-                    call('fte_bn_prelu_apply', T[inp], b['scale'], b['shift'], self.view(aname), T[out], rows, c, st)
-            elif kind == 'gconv':
-                ih, iw, c = self.shapes[op[2]]
+    def _side_packs(self, w):
+        """the packs the head of the walk does not need, on the side stream -> the event that completes them"""
+        side = self.side
+        side.wait_stream(w.main)
+        sst = side.cuda_stream
+        self.packs.refresh_rest(self.params, sst)
+        for op in self.plan:
+            if op[0] == 'gconv':
                 pk = self._gconv_pack(op)
-                if pk is not None:                             # bf16 MFMA mode: block-diagonal slices on the matrix cores
-                    if not s16 or self.side is None or self.packs.head_names == set(self.w16t):
-                        call('fte_gconv3x3_pack_bf16', self.view(op[3]), pk[0], pk[1], c, op[5], st)
-                    elif pack_ev is not None:                  # (packed on the side stream at the start of the walk)
-                        torch.cuda.current_stream().wait_event(pack_ev)
-                        pack_ev = None
-                    if s16 and is_training and j in self.fuse_fwd and self.fuse_3x3:
-                        xin, isc, ish, yside = fold_args(j)
-                        call('fte_gconv3x3_bn_fwd_bf16_s16', xin, pk[0], T[out], *bn_args(self.fuse_fwd[j]), isc, ish, yside, n, ih, iw, c, op[4],
-                             self.ws, self.ws_bytes, st)
-                        stats_done.add(self.fuse_fwd[j])
-                    else:
-                        call('fte_gconv3x3_bf16_s16' if s16 else 'fte_gconv3x3_bf16', T[op[2]], pk[0], T[out], n, ih, iw, c, op[4], 0, st)
-                else:
-                    call('fte_gconv3x3_fwd', T[op[2]], self.view(op[3]), T[out], n, ih, iw, c, op[5], op[4], st)
-            elif kind == 'se':
-                inp = op[2]
-                w1, b1, w2, b2, hd = self._se_names(op)
-                ih, iw, c = self.shapes[inp]
-                sq, hid, gate = T[out + '/sq'], T[out + '/hid'], T[out + '/gate']
-                call('fte_gap_fwd_s16' if s16 else 'fte_gap_fwd', T[inp], sq, n, ih * iw, c, st)
-                if os.environ.get('FTE_SE_ACT_FUSE', '1') != '0':
-                    # the gate's two dense layers with their activation (ReLU, sigmoid) in the same pass over the output
-                    call('fte_gemm_nn_act', sq, self.view(w1), self.view(b1), hid, n, hd, c, 1, self.ws, self.ws_bytes, st)
-                    call('fte_gemm_nn_act', hid, self.view(w2), self.view(b2), gate, n, c, hd, 2, self.ws, self.ws_bytes, st)
-                else:                                          # (A/B hook: the activations as launches of their own)
-                    call('fte_gemm_nn', sq, self.view(w1), self.view(b1), hid, n, hd, c, self.ws, self.ws_bytes, st)
-                    call('fte_act_fwd', hid, hid, hid.numel(), 0, st)
-                    call('fte_gemm_nn', hid, self.view(w2), self.view(b2), gate, n, c, hd, self.ws, self.ws_bytes, st)
-                    call('fte_act_fwd', gate, gate, gate.numel(), 1, st)
-                call('fte_channel_scale_fwd_s16' if s16 else 'fte_channel_scale_fwd', T[inp], gate, T[out], n, ih * iw, c, st)
-            elif kind == 'seblock':
-                _, _, zin, pre, scn, seop, _, _ = op
-                w1, b1, w2, b2, hd = self._se_names(seop)
-                ih, iw, c = self.shapes[out]
-                hw = ih * iw
-                b = self.bn[out]
-                fl = ((1 if zin in h16 else 0) | 2) if s16 else 0
-                if j in stats_done:                            # the producing conv's epilogue left the batch statistics
-                    pass
-                elif is_training:
-                    upd = self.update_moving_stats
-                    args = (T[zin], self.view(pre + '/gamma'), self.view(pre + '/beta'), b['mean'], b['rstd'], b['scale'], b['shift'],
-                            self.state[pre + '/moving_mean'] if upd else None, self.state[pre + '/moving_variance'] if upd else None,
-                            n * hw, c, self.bn_eps, self.bn_decay)
-                    if s16:
-                        call('fte_bn_train_stats_s16', *args, 1 if zin in h16 else 0, self.ws, self.ws_bytes, st)
-                    else:
-                        call('fte_bn_train_stats', *args, self.ws, self.ws_bytes, st)
-                else:
-                    call('fte_bn_infer_coef', self.view(pre + '/gamma'), self.view(pre + '/beta'),
-                         self.state[pre + '/moving_mean'], self.state[pre + '/moving_variance'], b['scale'], b['shift'], c, self.bn_eps, st)
-                sq, hid, gate = T[out + '/sq'], T[out + '/hid'], T[out + '/gate']
-                call('fte_se_squeeze', T[zin], b['scale'], b['shift'], b['mean'], b['rstd'], sq, T[out + '/xm'] if is_training else None,
-                     n, hw, c, fl & 1, st)
-                if self._se_small(c, hd):                      # the gate's dense layers, one launch each
-                    call('fte_dense_small', sq, self.view(w1), self.view(b1), None, hid, n, hd, c, 0, 1, st)
-                    call('fte_dense_small', hid, self.view(w2), self.view(b2), None, gate, n, c, hd, 0, 2, st)
-                else:
-                    call('fte_gemm_nn_act', sq, self.view(w1), self.view(b1), hid, n, hd, c, 1, self.ws, self.ws_bytes, st)
-                    call('fte_gemm_nn_act', hid, self.view(w2), self.view(b2), gate, n, c, hd, 2, self.ws, self.ws_bytes, st)
-                if scn in sc_ev:
-                    main_s.wait_event(sc_ev.pop(scn))          # the shortcut branch (side stream) has written it
-                call('fte_se_apply_fwd', T[zin], b['scale'], b['shift'], gate, T[scn], T[out], n, hw, c, fl, st)
-            elif kind == 'addrelu':
-                c = self.shapes[out][-1]
-                one, zero = self.ident[c]
-                for nm in (op[2], op[3]):
-                    if nm in sc_ev:
-                        main_s.wait_event(sc_ev.pop(nm))
-                if s16:
-                    assert op[2] in h16 and op[3] in h16
-                    call('fte_bn_infer_fwd_s16', T[op[2]], one, zero, zero, one, T[op[3]], T[out], self._scr(c, 0), self._scr(c, 1),
-                         T[out].numel() // c, c, 0.0, 1, 3, st)
-                else:
-                    call('fte_bn_infer_fwd', T[op[2]], one, zero, zero, one, T[op[3]], T[out], self._scr(c, 0), self._scr(c, 1),
-                         T[out].numel() // c, c, 0.0, 1, st)
-            elif kind == 'maxpool':
-                ih, iw, c = self.shapes[op[2]]
-                call('fte_maxpool3x3s2_fwd_s16' if s16 else 'fte_maxpool3x3s2_fwd', T[op[2]], T[out], T[out + '/idx'], n, ih, iw, c, st)
-            elif kind == 'gap':
-                ih, iw, c = self.shapes[op[2]]
-                call('fte_gap_fwd_s16' if op[2] in h16 else 'fte_gap_fwd', T[op[2]], T[out], n, ih * iw, c, st)
-            elif kind == 'dropout':
-                if is_training:
-                    seed = (self.dropout_seed * 1000003 + self.global_step) & 0x7FFFFFFFFFFFFFFF
-                    call('fte_dropout_fwd', T[op[2]], T[out + '/mask'], T[out], T[out].numel(), op[3], seed, st)
-                else:
-                    T[out].copy_(T[op[2]])
-            elif kind == 'fc' and self.spec[op[3]][1] == 'embed_w':      # [n, h, w, c] read as one row-major [n, h w c] operand; no bias
-                fin, d = self.spec[op[3]][0]
-                call('fte_gemm_nn', T[op[2]], self.view(op[3]), None, T[out], n, d, fin, self.ws, self.ws_bytes, st)
-            elif kind == 'fc':
-                k = self.shapes[op[2]][0]
-                call('fte_gemm_nn', T[op[2]], self.view(op[3]), None, T[out], n, self.sub_centers * self.cpad, k, self.ws, self.ws_bytes, st)
+                if pk is not None:
+                    w.call('fte_gconv3x3_pack_bf16', self.view(op.wname), pk[0], pk[1], self.shapes[op.inp][-1], op.groups, sst)
+        w.packs_pending = False
+        return side.record_event()
+
+    def _wait_packs(self, w):
+        """the side stream's packs (once: every later layer is behind this wait)"""
+        torch.cuda.current_stream().wait_event(w.pack_ev)
+        w.pack_ev = None
+
+    # ---- backward ---------------------------------------------------------------------------------------
+    def backward_body(self, lo=0, hi=None):
+        """The backward walk over plan ops [lo, hi) (default: the whole body), last op first.  Segments are walked from the end of
+        the plan: the gradients in flight between two calls stay in self._grad; when a call returns its filter gradients are final."""
+        nops = len(self.plan) - (1 if self.has_classifier else 0)
+        hi = nops if hi is None else hi
+        if hi == nops and not self.has_classifier:
+            self._grad = {self.feature_name: self._dfeat}
+            self._dfeat = None
+        if hi == nops:
+            self._reduced = set()
+        w = _Walk()
+        w.call, w.n, w.s16, w.sfx = _lib.call, self._act_n, self._act_s16, '_s16' if self._act_s16 else ''
+        # Filter gradients (conv / depthwise / grouped wgrad + their slab reductions) depend only on the layer's dz and its
+        # stored input, and nothing but the optimizer reads them: they go to a second stream and overlap the dgrad -> BN
+        # backward chain (these nets' kernels are 5-60 us long and leave CUs idle at their ramps and tails).  An event on
+        # the main stream costs it a ~7 us bubble, so the launches are queued and released a few layers at a time.
+        w.main, w.side = torch.cuda.current_stream(), self.side
+        w.st = w.main.cuda_stream
+        w.wst, w.wws = (w.side.cuda_stream, self.ws_side) if w.side is not None else (w.st, self.ws)
+        w.pending = []
+        w.reduced = self._reduced  # BN outputs whose mask / reduction pass ran in the epilogue of the data gradient that produced G[name]
+        G = w.G = self._grad
+        plan_ops, handlers, feat = self.plan, self._bwd_ops, self.feature_name
+        for j in range(hi - 1, lo - 1, -1):
+            op = plan_ops[j]
+            out = op[1]
+            if out == feat and self._dfeat is not None and out in G:
+                # the pooled features also feed the center loss: add its gradient to the classifier path's
+                d = G[out].shape[1]
+                w.call('fte_add_scaled_rows_cols', G[out], self._dfeat, self.ones_n, None, w.n, d, d, w.st)
+                self._dfeat = None
+            if out not in G:                             # (a gather: the first of its outputs)
+                continue
+            if handlers[j] is None:
+                raise RuntimeError(op[0])
+            handlers[j](w, op, G.pop(out))
+        if w.side is not None:
+            self._flush(w)
+            w.main.wait_stream(w.side)
+        if lo == 0:
+            self._grad = {}
+
+    # ---- the plan kinds: buffers, forward, backward of each ----------------------------------------------
+    def _alloc_conv(self, w, op):
+        # every conv writes bf16 under bf16 storage: the MFMA convs, the direct 3x3 stem, and the im2col stem (a 1x1 conv of `kpad` bf16
+        # columns on the bf16-source kernels)
+        n, q, s16 = w.n, _lib.query, w.s16
+        shape = self._alloc_out(w, op, True)
+        ih, iw, cin = self.shapes[op.inp]
+        k, stride, cout = self.spec[op.wname][0][0], op.stride, shape[-1]
+        if cin >= 32:
+            self._reads16(w, op, op.inp)
+            w.need = max(w.need, *[q('fte_conv2d_%s_ws_bytes' % what, n, ih, iw, cin, cout, k, stride)
+                                   for what in ('fwd', 'dgrad', 'wgrad', 'bn_fwd', 'dgrad_bn')])
+            if s16:          # bf16 packs of the filter: HWIO (data gradient) and [tap][cout][cin] (forward), refreshed every step
+                self._pack_entries.append((op.wname, self.variables[op.wname].offset, k, cin, cout))
+        elif self._direct_stem(k, cin, cout):
+            w.need = max(w.need, q('fte_conv3x3_first_wgrad_ws_bytes', n, ih, iw, cin, cout, stride))
+        else:
+            oh, ow, _ = self.shapes[op.out]
+            kpad = stem_kpad(k, cin)
+            self.cols = torch.empty(n * oh * ow, kpad, dtype=torch.int16 if s16 else torch.float32, device=self.device)
+            w.need = max(w.need, q('fte_gemm_ws_bytes', n * oh * ow, cout, kpad))
+            if s16:          # the stem as a 1x1 conv of kpad bf16 columns: packs like any other conv's, [1, 1, kpad, cout]
+                self._pack_entries.append((op.wname, self.variables[op.wname].offset, 1, kpad, cout))
+                w.need = max(w.need, q('fte_conv2d_fwd_ws_bytes', n, oh, ow, kpad, cout, 1, 1), q('fte_conv2d_bn_fwd_ws_bytes', n, oh, ow, kpad, cout, 1, 1),
+                             q('fte_conv2d_wgrad_ws_bytes', n, oh, ow, kpad, cout, 1, 1))
+
+    def _fwd_conv(self, w, j, op):
+        call, T, s16, n, st = w.call, self.t, w.s16, w.n, w.st
+        out, inp, wname, stride = op.out, op.inp, op.wname, op.stride
+        ih, iw, cin = self.shapes[inp]
+        k = self.spec[wname][0][0]
+        cout = self.shapes[out][-1]
+        if w.on_side:
+            w.side.wait_event(w.main.record_event())          # the block's input is complete (the packs were made on this stream)
+        if cin < 32:
+            self._fwd_stem(w, j, op, k, cin, cout)
+            return
+        if not w.on_side and w.pack_ev is not None and wname not in self.packs.head_names:
+            self._wait_packs(w)
+        bj = self.fuse_fwd.get(j) if w.is_training else None
+        if bj is not None and (k == 1 or not s16 or self.fuse_3x3):          # conv + the batch statistics of its output ("BN fusion")
+            xin, isc, ish, yside = self._fold_args(w, j)
+            call('fte_conv2d_bn_fwd', xin, self.w16t[wname] if s16 else self.view(wname), T[out], *self._bn_args(self.plan[bj], w.upd),
+                 isc, ish, yside, n, ih, iw, cin, cout, k, stride, 1 if s16 else 0, w.ws, self.ws_bytes, st)
+            w.stats_done.add(bj)
+        elif s16:          # bf16 storage: bf16 x in, bf16 z out, filters packed once per step
+            call('fte_conv2d_fwd_s16', T[inp], self.w16t[wname], None, None, None, None, T[out], None, None,
+                 n, ih, iw, cin, cout, k, stride, w.ws, self.ws_bytes, st)
+        else:
+            call('fte_conv2d_fwd', T[inp], self.view(wname), None, None, None, None, T[out],
+                 n, ih, iw, cin, cout, k, stride, w.ws, self.ws_bytes, st)
+
+    def _fwd_stem(self, w, j, op, k, cin, cout):
+        """the first conv (image channels)"""
+        call, T, s16, n, st = w.call, self.t, w.s16, w.n, w.st
+        out, inp, wname, stride = op.out, op.inp, op.wname, op.stride
+        ih, iw, _ = self.shapes[inp]
+        if self._direct_stem(k, cin, cout):          # 3x3 stem of 32 / 64 stored filters: the direct MFMA kernel
+            call('fte_conv3x3_first_fwd' + w.sfx, T[inp], self.view(wname), None, None, None, T[out], n, ih, iw, cin, cout, stride, st)
+            return
+        oh, ow, _ = self.shapes[out]
+        kpad = stem_kpad(k, cin)
+        if not s16:                                    # other stems (7x7): im2col + dense MFMA GEMM
+            call('fte_im2col_first', T[inp], self.cols, n, ih, iw, cin, k, stride, kpad, st)
+            call('fte_gemm_nn', self.cols, self.view(wname), None, T[out], n * oh * ow, cout, kpad, self.ws, self.ws_bytes, st)
+            return
+        # ... under bf16 storage: bf16 columns, then a 1x1 conv of kpad channels
+        call('fte_im2col_first_s16', T[inp], self.cols, n, ih, iw, cin, k, stride, kpad, st)
+        if w.packs_pending:                            # the rest of the filter packs, from here on (_start_packs)
+            w.pack_ev = self._side_packs(w)
+        if w.is_training and j in self.fuse_fwd:
+            bj = self.fuse_fwd[j]
+            call('fte_conv2d_bn_fwd', self.cols, self.w16t[wname], T[out], *self._bn_args(self.plan[bj], w.upd), None, None, None,
+                 n, oh, ow, kpad, cout, 1, 1, 1, self.ws, self.ws_bytes, st)
+            w.stats_done.add(bj)
+        else:
+            call('fte_conv2d_fwd_s16', self.cols, self.w16t[wname], None, None, None, None, T[out], None, None,
+                 n, oh, ow, kpad, cout, 1, 1, self.ws, self.ws_bytes, st)
+
+    def _bwd_conv(self, w, op, dy):
+        call, T, s16, n, st, G = w.call, self.t, w.s16, w.n, w.st, w.G
+        out, inp, wname, stride = op.out, op.inp, op.wname, op.stride
+        ih, iw, cin = self.shapes[inp]
+        k = self.spec[wname][0][0]
+        cout = self.shapes[out][-1]
+        gw = self.view(wname, self.grads)
+        if cin < 32 and self._direct_stem(k, cin, cout):
+            call('fte_conv3x3_first_wgrad' + w.sfx, T[inp], dy, gw, n, ih, iw, cin, cout, stride, self.ws, self.ws_bytes, st)
+            return
+        if cin < 32:                             # stem: filter gradient only
+            oh, ow, _ = self.shapes[out]
+            if s16:
+                call('fte_conv2d_wgrad16', self.cols, dy, gw, n, oh, ow, stem_kpad(k, cin), cout, 1, 1, self.ws, self.ws_bytes, st)
             else:
-                raise RuntimeError('op %s must have been fused away' % kind)
+                call('fte_gemm_tn', self.cols, dy, gw, n * oh * ow, cout, stem_kpad(k, cin), self.ws, self.ws_bytes, st)
+            return
+        self._wgrad(w, 'fte_conv2d_wgrad16' if s16 else 'fte_conv2d_wgrad', dy, T[inp], dy, gw, n, ih, iw, cin, cout, k, stride, w.wws, self.ws_bytes, w.wst)
+        self._flush(w, self.side_batch)
+        prev = G.pop(inp, None)                  # accumulate into an existing contribution through `addin`
+        dx = self._new(inp)
+        bnb = self._bn_below(w, inp) if self.fuse_bwd_conv else None
+        if bnb is not None:          # the last contribution to the gradient of a BN output: mask + BN sums in the epilogue
+            ins, outs = bnb
+            call('fte_conv2d_dgrad_bn', dy, self.w16[wname] if s16 else self.view(wname), prev, *ins, dx, *outs,
+                 n, ih, iw, cin, cout, k, stride, 1 if s16 else 0, self.ws, self.ws_bytes, st)
+            w.reduced.add(inp)
+        else:          # bf16 storage: bf16 dz in, bf16 dx out (+ the bf16 contribution already there); the HWIO pack is this step's
+            call('fte_conv2d_dgrad' + w.sfx, dy, self.w16[wname] if s16 else self.view(wname), prev, None, None, None, dx, None, None,
+                 n, ih, iw, cin, cout, k, stride, self.ws, self.ws_bytes, st)
+        G[inp] = dx
 
-    def _gconv_pack(self, op):
-        """(forward, dgrad) packed bf16 filters of a grouped 3x3 that runs on the matrix cores -- bf16 MFMA mode,
-        4 / 8 / 16 / 32 channels per group -- else None (fp32 vector kernels)."""
-        _, _, inp, wname, stride, groups = op
-        c = self.shapes[inp][-1]
-        if c % 32 or (c // groups) not in (4, 8, 16, 32) or _lib.get_mfma_dtype() != 'bf16' \
-                or os.environ.get('FTE_GCONV_MFMA', '1') == '0':
-            return None
-        pk = self._gpacks.get(wname)
+    def _alloc_gconv(self, w, op):
+        n, q = w.n, _lib.query
+        self._alloc_out(w, op, True)
+        self._reads16(w, op, op.inp)
+        ih, iw, cc = self.shapes[op.inp]
+        w.need = max(w.need, q('fte_gconv3x3_wgrad_ws_bytes', n, ih, iw, cc, op.groups, op.stride))
+        if cc % 32 == 0 and cc // op.groups in (4, 8, 16, 32):
+            w.need = max(w.need, q('fte_gconv3x3_wgrad_bf16_ws_bytes', n, ih, iw, cc, op.groups, op.stride),
+                         q('fte_gconv3x3_bn_ws_bytes', n, ih, iw, cc, op.stride))
+
+    def _fwd_gconv(self, w, j, op):
+        call, T, s16, n, st = w.call, self.t, w.s16, w.n, w.st
+        out, inp, wname, stride, groups = op.out, op.inp, op.wname, op.stride, op.groups
+        ih, iw, c = self.shapes[inp]
+        pk = self._gconv_pack(op)
         if pk is None:
-            words = (c // 32) * 9 * 1024
-            pk = self._gpacks[wname] = (torch.empty(words, dtype=torch.int16, device=self.device),
-                                        torch.empty(words, dtype=torch.int16, device=self.device))
-        return pk
+            call('fte_gconv3x3_fwd', T[inp], self.view(wname), T[out], n, ih, iw, c, groups, stride, st)
+            return
+        # bf16 MFMA mode: block-diagonal slices on the matrix cores
+        if not s16 or self.side is None or self.packs.head_names == set(self.w16t):
+            call('fte_gconv3x3_pack_bf16', self.view(wname), pk[0], pk[1], c, groups, st)
+        elif w.pack_ev is not None:                  # (packed on the side stream at the start of the walk)
+            self._wait_packs(w)
+        if s16 and w.is_training and j in self.fuse_fwd and self.fuse_3x3:
+            bj = self.fuse_fwd[j]
+            xin, isc, ish, yside = self._fold_args(w, j)
+            call('fte_gconv3x3_bn_fwd_bf16_s16', xin, pk[0], T[out], *self._bn_args(self.plan[bj], w.upd), isc, ish, yside, n, ih, iw, c, stride,
+                 self.ws, self.ws_bytes, st)
+            w.stats_done.add(bj)
+        else:
+            call('fte_gconv3x3_bf16' + w.sfx, T[inp], pk[0], T[out], n, ih, iw, c, stride, 0, st)
 
-    @staticmethod
-    def _direct_stem(k, cin, cout):
-        """3x3 first conv on 1 / 3 image channels with 32 or 64 stored filters: fte_conv3x3_first_* (K = 9*cin is too short for
-        the GEMM path's im2col round trip through HBM)"""
-        return k == 3 and cin in (1, 3) and cout in (32, 64) and os.environ.get('FTE_DIRECT_STEM', '1') != '0'
+    def _bwd_gconv(self, w, op, dy):
+        call, T, s16, n, st = w.call, self.t, w.s16, w.n, w.st
+        inp, wname, stride, groups = op.inp, op.wname, op.stride, op.groups
+        ih, iw, c = self.shapes[inp]
+        pk = self._gconv_pack(op)
+        self._wgrad(w, ('fte_gconv3x3_wgrad_bf16' + w.sfx) if pk is not None else 'fte_gconv3x3_wgrad',      # (bf16 MFMA mode, or the vector kernel)
+                    dy, T[inp], dy, self.view(wname, self.grads), n, ih, iw, c, groups, stride, w.wws, self.ws_bytes, w.wst)
+        dx = self._new(inp)
+        bnb = self._bn_below(w, inp) if (pk is not None and s16 and self.fuse_bwd_gconv) else None
+        if bnb is not None:                      # ... with the mask / sums of the BN layer below in the epilogue
+            (zbn, _, gam, mean, rstd, sc, sh), outs = bnb
+            call('fte_gconv3x3_dgrad_bn_bf16_s16', dy, pk[1], zbn, gam, mean, rstd, sc, sh, dx, *outs, n, ih, iw, c, stride,
+                 self.ws, self.ws_bytes, st)
+            w.reduced.add(inp)
+        elif pk is not None:                     # packed by this step's forward pass (the weights have not changed since)
+            call('fte_gconv3x3_bf16' + w.sfx, dy, pk[1], dx, n, ih, iw, c, stride, 1, st)
+        else:
+            call('fte_gconv3x3_dgrad', dy, self.view(wname), dx, n, ih, iw, c, groups, stride, st)
+        self._put(inp, dx)
 
-    def _se_names(self, op):
-        """('se', out, inp, prefix[, scope1, scope2]) -> weight / bias names of the two FCs and the (padded) hidden width"""
-        pre = op[3]
-        s1, s2 = (op[4], op[5]) if len(op) > 4 else ('fc1', 'fc2')
-        w1 = pre + '/%s/weights' % s1
-        return w1, pre + '/%s/biases' % s1, pre + '/%s/weights' % s2, pre + '/%s/biases' % s2, self.ishape[w1][1]
+    def _alloc_dwconv(self, w, op):
+        self._alloc_out(w, op, True)
+        self._reads16(w, op, op.inp)
+        ih, iw, cc = self.shapes[op.inp]
+        w.need = max(w.need, _lib.query('fte_dwconv3x3_wgrad_ws_bytes', w.n, ih, iw, cc, op.stride))
 
-    @staticmethod
-    def _se_small(c, hd):
-        """the SE gate's dense layers through fte_dense_small (one launch each)?  FTE_SE_DENSE=0: fte_gemm_* (A/B hook)"""
-        return c % 128 == 0 and hd % 128 == 0 and os.environ.get('FTE_SE_DENSE', '1') != '0'
+    def _fwd_dwconv(self, w, j, op):
+        ih, iw, c = self.shapes[op.inp]
+        w.call('fte_dwconv3x3_fwd' + w.sfx, self.t[op.inp], self.view(op.wname), self.t[op.out], w.n, ih, iw, c, op.stride, w.st)
 
-    def _scr(self, c, i):
-        key = ('scr', c, i)
-        if key not in self.ident:
-            self.ident[key] = torch.empty(c, dtype=torch.float32, device=self.device)
-        return self.ident[key]
+    def _bwd_dwconv(self, w, op, dy):
+        inp, wname, n = op.inp, op.wname, w.n
+        ih, iw, c = self.shapes[inp]
+        self._wgrad(w, 'fte_dwconv3x3_wgrad' + w.sfx, dy, self.t[inp], dy, self.view(wname, self.grads), n, ih, iw, c, op.stride, w.wws, self.ws_bytes, w.wst)
+        dx = self._new(inp)
+        w.call('fte_dwconv3x3_dgrad' + w.sfx, dy, self.view(wname), dx, n, ih, iw, c, op.stride, w.st)
+        self._put(inp, dx)
+
+    def _alloc_gather(self, w, op):
+        for name, _ in op.outs:
+            self._alloc_out(w, op, True, name)
+
+    def _fwd_gather(self, w, j, op):
+        call, T, st = w.call, self.t, w.st
+        a, b = op.ins
+        fa, fb = self.folded.get(a), self.folded.get(b)
+        outs = op.outs
+        if fa is None and fb is None and len(outs) == 1:
+            name, table = outs[0]
+            co = self.shapes[name][-1]
+            call('fte_channel_gather' + w.sfx, T[a], T[b] if b else None, T[name], table, T[name].numel() // co,
+                 self.shapes[a][-1], self.shapes[b][-1] if b else 0, co, st)
+        else:                                          # both halves in one launch, BN applied to a folded source
+            sa = (T[fa[0]], self.bn[a]['scale'], self.bn[a]['shift'], fa[1]) if fa else (T[a], None, None, 0)
+            sb = (T[fb[0]], self.bn[b]['scale'], self.bn[b]['shift'], fb[1]) if fb else (T[b] if b else None, None, None, 0)
+            (n0, t0), (n1, t1) = outs[0], (outs[1] if len(outs) > 1 else (None, None))
+            co0 = self.shapes[n0][-1]
+            call('fte_channel_gather_affine' + w.sfx, sa[0], sb[0], T[n0], t0, co0, T[n1] if n1 else None, t1,
+                 self.shapes[n1][-1] if n1 else 0, T[n0].numel() // co0, self.shapes[a][-1],
+                 self.shapes[b][-1] if b else 0, sa[1], sa[2], sa[3], sb[1], sb[2], sb[3], st)
+
+    def _bwd_gather(self, w, op, da):
+        call, st, G = w.call, w.st, w.G
+        gb = op.gouts[1]
+        db = G.pop(gb) if gb else None
+        gs = [(name, table, torch.empty((w.n,) + self.shapes[name], dtype=torch.int16 if w.s16 else torch.float32, device=self.device))
+              for name, table in op.bwd]
+        (n0, t0, g0), (n1, t1, g1) = gs[0], (gs[1] if len(gs) > 1 else (None, None, None))
+        co0 = self.shapes[n0][-1]
+        if g1 is None:
+            call('fte_channel_gather' + w.sfx, da, db, g0, t0, g0.numel() // co0, da.shape[-1],
+                 db.shape[-1] if db is not None else 0, co0, st)
+        else:                                    # the gradients of both sources in one launch
+            call('fte_channel_gather_affine' + w.sfx, da, db, g0, t0, co0, g1, t1, self.shapes[n1][-1], g0.numel() // co0,
+                 da.shape[-1], db.shape[-1] if db is not None else 0, None, None, 0, None, None, 0, st)
+        for name, _, g in gs:
+            self._put(name, g)
+
+    def _alloc_bnstats(self, w, op):
+        self._alloc_bn(w, op, stored=False)              # (applied inside the gather that consumes it: the output is never stored)
+
+    def _fwd_bnstats(self, w, j, op):
+        if j not in w.stats_done:
+            self._bn_stats(w, op, self.t[op.inp], op.inp in self.h16)
+
+    def _fwd_bn(self, w, j, op):
+        call, T, s16, st = w.call, self.t, w.s16, w.st
+        out, inp, res, relu = op.out, op.inp, op.res, op.relu
+        b = self.bn[out]
+        c = self.shapes[out][-1]
+        rows = T[out].numel() // c
+        resbuf = T[res] if res is not None else None
+        if res is not None:
+            self._wait_shortcut(w, res)
+            assert not s16 or res in self.h16, 'bf16 storage: the shortcut of %s is an fp32 tensor' % out
+        if j in w.stats_done and self._folds(w, j):  # ... which the consumer's operand loader takes over (it also writes T[out])
+            w.folded_in[self.fold_apply[j]] = j
+        elif j in w.stats_done:            # scale / shift are there already: the normalise pass alone
+            call('fte_bn_apply', T[inp], b['scale'], b['shift'], resbuf, T[out], rows, c, relu, self._sflag(w, inp), st)
+        elif w.is_training:
+            ba = self._bn_args(op, w.upd)
+            args = (T[inp], ba[0], ba[1], resbuf, T[out]) + ba[2:8] + (rows, c, ba[8], ba[9], relu)
+            if s16:
+                call('fte_bn_train_fwd_s16', *args, self._sflag(w, inp), w.ws, self.ws_bytes, st)
+            else:
+                call('fte_bn_train_fwd', *args, w.ws, self.ws_bytes, st)
+        else:
+            ba = self._bn_args(op, True)
+            args = (T[inp], ba[0], ba[1], ba[6], ba[7], resbuf, T[out], b['scale'], b['shift'], rows, c, self.bn_eps, relu)
+            if s16:
+                call('fte_bn_infer_fwd_s16', *args, self._sflag(w, inp), st)
+            else:
+                call('fte_bn_infer_fwd', *args, st)
+        if w.on_side:
+            w.sc_ev[out] = w.side.record_event()
+
+    def _bwd_bn(self, w, op, dy):
+        call, T, st = w.call, self.t, w.st
+        out, inp, pre, res, relu = op.out, op.inp, op.pre, op.res, op.relu
+        b = self.bn[out]
+        c = self.shapes[out][-1]
+        rows = dy.numel() // c
+        dz = torch.empty_like(T[inp])
+        gam, dgam, dbet = self.view(pre + '/gamma'), self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads)
+        tail = (rows, c, self.ws, self.ws_bytes, st)
+        if out in w.reduced:             # dy is the masked gradient already, dgamma / dbeta / coef are there: the apply pass alone
+            call('fte_bn_bwd_apply', dy, T[inp], b['coef'], dz, rows, c, 3 if w.s16 else 0, st)
+            if res is not None:
+                self._put(res, dy)               # the shortcut sees the same (read-only) masked gradient
+        elif w.s16:                      # one entry point: y (the mask of a residual BN), scale / shift (the mask recomputed from z) or neither
+            g = self._new(out) if res is not None else None
+            zmask = relu and res is None
+            call('fte_bn_train_bwd_s16', dy, T[out] if res is not None else None, T[inp], gam, b['mean'], b['rstd'],
+                 b['scale'] if zmask else None, b['shift'] if zmask else None, g, dz, dgam, dbet, rows, c, self._sflag(w, inp), self.ws, self.ws_bytes, st)
+            if res is not None:
+                self._put(res, g)
+        elif res is not None and not relu:         # BN + shortcut, no activation: dy goes unmasked into the BN backward and
+            call('fte_bn_train_bwd', dy, None, T[inp], gam, b['mean'], b['rstd'], dz, dgam, dbet, *tail)      # unchanged (no copy) to the shortcut
+            self._add(res, dy)
+        elif res is not None:                      # the shortcut gets g = dy * (out > 0): a by-product of the reduce pass
+            g = self._new(out)
+            call('fte_bn_train_bwd_res', dy, T[out], T[inp], gam, b['mean'], b['rstd'], g, dz, dgam, dbet, *tail)
+            self._put(res, g)
+        elif relu:                                 # ReLU mask recomputed from z: the output is not read
+            call('fte_bn_train_bwd_zmask', dy, T[inp], gam, b['mean'], b['rstd'], b['scale'], b['shift'], dz, dgam, dbet, *tail)
+        else:
+            call('fte_bn_train_bwd', dy, None, T[inp], gam, b['mean'], b['rstd'], dz, dgam, dbet, *tail)
+        if inp in self.shortcut_shared:
+            self._add(inp, dz)               # ... plus the gradient the shortcut passed on
+        else:
+            self._put(inp, dz)
+
+    _bwd_bnstats = _bwd_bn
+
+    def _alloc_bnprelu(self, w, op):
+        w.need = max(w.need, _lib.query('fte_bn_prelu_ws_bytes', self.shapes[op.out][-1]))
+        self._alloc_bn(w, op)
+
+    def _fwd_bnprelu(self, w, j, op):
+        T = self.t
+        x, y = T[op.inp], T[op.out]
+        b = self.bn[op.out]
+        c = self.shapes[op.out][-1]
+        rows = y.numel() // c
+        if not w.is_training:                            # moving statistics -> scale / shift, then the apply (fte.h)
+            ba = self._bn_args(op, True)
+            w.call('fte_bn_prelu_infer_fwd', x, ba[0], ba[1], ba[6], ba[7], self.view(op.alpha), y, b['scale'], b['shift'], rows, c, self.bn_eps, w.st)
+            return
+        if j not in w.stats_done:                    # (else the producing conv's epilogue left the batch statistics)
+            self._bn_stats(w, op, x, False)
+        w.call('fte_bn_prelu_apply', x, b['scale'], b['shift'], self.view(op.alpha), y, rows, c, w.st)
+
+    def _bwd_bnprelu(self, w, op, dy):
+        inp, pre, alpha = op.inp, op.pre, op.alpha
+        b = self.bn[op.out]
+        c = self.shapes[op.out][-1]
+        dz = torch.empty_like(self.t[inp])
+        w.call('fte_bn_prelu_train_bwd', dy, self.t[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], b['scale'], b['shift'], self.view(alpha),
+               dz, self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), self.view(alpha, self.grads), dy.numel() // c, c,
+               self.ws, self.ws_bytes, w.st)
+        self._put(inp, dz)
+
+    def _alloc_seblock(self, w, op):
+        self._alloc_out(w, op, True)
+        self._reads16(w, op, op.inp, op.shortcut)
+        self._alloc_bn(w, op, stored=False)
+        c = self.shapes[op.out][-1]
+        for nm in ('xm', 's1', 's2'):                  # per-image sums of the backward pass, the squeeze in xhat units
+            self.t[op.out + '/' + nm] = self._f32(w.n, c)
+        self._alloc_se_gate(w, op.out, op.se, c)
+
+    def _fwd_seblock(self, w, j, op):
+        call, T, n, st = w.call, self.t, w.n, w.st
+        out, zin, scn, se = op.out, op.inp, op.shortcut, op.se
+        ih, iw, c = self.shapes[out]
+        hw = ih * iw
+        b = self.bn[out]
+        fl = self._sflag(w, zin)
+        if j not in w.stats_done:                      # (else the producing conv's epilogue left the batch statistics)
+            self._bn_stats(w, op, T[zin], zin in self.h16)
+        sq, _, gate = self._se_buffers(out)
+        call('fte_se_squeeze', T[zin], b['scale'], b['shift'], b['mean'], b['rstd'], sq, T[out + '/xm'] if w.is_training else None,
+             n, hw, c, fl & 1, st)
+        self._se_gate_fwd(w, out, se, c, 'small' if self._se_small(c, se.hidden) else 'act')
+        self._wait_shortcut(w, scn)
+        call('fte_se_apply_fwd', T[zin], b['scale'], b['shift'], gate, T[scn], T[out], n, hw, c, fl, st)
+
+    def _bwd_seblock(self, w, op, dy):
+        call, T, n, st = w.call, self.t, w.n, w.st
+        out, zin, pre, se = op.out, op.inp, op.pre, op.se
+        ih, iw, c = self.shapes[out]
+        hw = ih * iw
+        b = self.bn[out]
+        fl = self._sflag(w, zin)
+        gate = T[out + '/gate']
+        s1, s2, xm = T[out + '/s1'], T[out + '/s2'], T[out + '/xm']
+        gam, bet = self.view(pre + '/gamma'), self.view(pre + '/beta')
+        g = self._new(out)                             # dy * (out > 0): the shortcut's gradient, and the gate path's input
+        call('fte_se_bwd_gate', dy, T[out], T[zin], gam, bet, b['mean'], b['rstd'], gate, g, s1, s2, self.ident[('se', out, 'dgate')], n, hw, c, fl, st)
+        dsq = self._se_gate_bwd(w, out, se, c, self._se_small(c, se.hidden))
+        call('fte_se_bn_bwd_coef', s1, s2, gate, dsq, xm, gam, b['mean'], b['rstd'], self.view(pre + '/gamma', self.grads),
+             self.view(pre + '/beta', self.grads), b['coef'], n, hw, c, st)
+        dz = torch.empty_like(T[zin])
+        call('fte_se_bn_bwd_apply', g, T[zin], b['coef'], gate, dsq, dz, n, hw, c, fl, st)
+        self._put(op.shortcut, g)
+        self._put(zin, dz)
+
+    def _alloc_se(self, w, op):
+        self._alloc_out(w, op, True)
+        self._reads16(w, op, op.inp)
+        self._alloc_se_gate(w, op.out, op, self.shapes[op.out][-1])
+
+    def _fwd_se(self, w, j, op):
+        call, T, n, st = w.call, self.t, w.n, w.st
+        out, inp = op.out, op.inp
+        ih, iw, c = self.shapes[inp]
+        sq, _, gate = self._se_buffers(out)
+        call('fte_gap_fwd' + w.sfx, T[inp], sq, n, ih * iw, c, st)
+        self._se_gate_fwd(w, out, op, c, 'act' if self.opt.se_act_fuse else 'plain')      # ('plain': A/B hook)
+        call('fte_channel_scale_fwd' + w.sfx, T[inp], gate, T[out], n, ih * iw, c, st)
+
+    def _bwd_se(self, w, op, dy):
+        call, T, n, st = w.call, self.t, w.n, w.st
+        out, inp = op.out, op.inp
+        ih, iw, c = self.shapes[inp]
+        hw = ih * iw
+        gate = T[out + '/gate']
+        dgate = self.ident[('se', out, 'dgate')]
+        dx = self._new(inp)
+        if w.s16:          # reduction only; dx is written once by the apply pass below
+            call('fte_channel_scale_bwd_s16', dy, T[inp], gate, dgate, n, hw, c, 1, st)
+        else:
+            call('fte_channel_scale_bwd', dy, T[inp], gate, dx, dgate, n, hw, c, 1, st)         # dgate = d(pre-sigmoid)
+        dsq = self._se_gate_bwd(w, out, op, c, False)
+        if w.s16:
+            call('fte_channel_scale_bwd_apply_s16', dy, gate, dsq, dx, n, hw, c, 1.0 / hw, st)
+        else:
+            call('fte_bcast_add', dx, dsq, n, hw, c, 1.0 / hw, st)
+        self._put(inp, dx)
+
+    def _alloc_addrelu(self, w, op):
+        self._alloc_out(w, op, True)
+        c = self.shapes[op.out][-1]
+        if c not in self.ident:
+            self.ident[c] = (torch.ones(c, dtype=torch.float32, device=self.device), torch.zeros(c, dtype=torch.float32, device=self.device))
+
+    def _fwd_addrelu(self, w, j, op):
+        T, out, a, b = self.t, op.out, op.a, op.b
+        c = self.shapes[out][-1]
+        one, zero = self.ident[c]
+        self._wait_shortcut(w, a, b)
+        args = (T[a], one, zero, zero, one, T[b], T[out], self._scr(c, 0), self._scr(c, 1), T[out].numel() // c, c, 0.0, 1)
+        if w.s16:
+            assert a in self.h16 and b in self.h16
+            w.call('fte_bn_infer_fwd_s16', *args, 3, w.st)
+        else:
+            w.call('fte_bn_infer_fwd', *args, w.st)
+
+    def _bwd_addrelu(self, w, op, dy):
+        g = self._new(op.out)
+        w.call('fte_relu_bwd' + w.sfx, dy, self.t[op.out], g, dy.numel(), w.st)
+        self._put(op.a, g)
+        self._put(op.b, g)                      # both addends see the same (read-only) gradient
+
+    def _alloc_maxpool(self, w, op):
+        shape = self._alloc_out(w, op, True)
+        self._reads16(w, op, op.inp)
+        self.t[op.out + '/idx'] = torch.empty(shape, dtype=torch.uint8, device=self.device)
+
+    def _fwd_maxpool(self, w, j, op):
+        T = self.t
+        ih, iw, c = self.shapes[op.inp]
+        w.call('fte_maxpool3x3s2_fwd' + w.sfx, T[op.inp], T[op.out], T[op.out + '/idx'], w.n, ih, iw, c, w.st)
+
+    def _bwd_maxpool(self, w, op, dy):
+        ih, iw, c = self.shapes[op.inp]
+        g = self._new(op.inp)
+        w.call('fte_maxpool3x3s2_bwd' + w.sfx, dy, self.t[op.out + '/idx'], g, w.n, ih, iw, c, w.st)
+        self._put(op.inp, g)
+
+    def _alloc_gap(self, w, op):
+        self._alloc_out(w, op, False)
+
+    def _fwd_gap(self, w, j, op):
+        ih, iw, c = self.shapes[op.inp]
+        w.call('fte_gap_fwd_s16' if op.inp in self.h16 else 'fte_gap_fwd', self.t[op.inp], self.t[op.out], w.n, ih * iw, c, w.st)
+
+    def _bwd_gap(self, w, op, dy):
+        ih, iw, c = self.shapes[op.inp]
+        g = self._new(op.inp)
+        w.call('fte_gap_bwd_s16' if op.inp in self.h16 else 'fte_gap_bwd', dy, g, w.n, ih * iw, c, w.st)
+        self._put(op.inp, g)
+
+    def _alloc_dropout(self, w, op):
+        shape = self._alloc_out(w, op, False)
+        self.t[op.out + '/mask'] = self._f32(shape)
+
+    def _fwd_dropout(self, w, j, op):
+        T = self.t
+        if w.is_training:
+            seed = (self.dropout_seed * 1000003 + self.global_step) & 0x7FFFFFFFFFFFFFFF
+            w.call('fte_dropout_fwd', T[op.inp], T[op.out + '/mask'], T[op.out], T[op.out].numel(), op.keep, seed, w.st)
+        else:
+            T[op.out].copy_(T[op.inp])
+
+    def _bwd_dropout(self, w, op, dy):
+        g = self._new(op.inp)
+        w.call('fte_dropout_bwd', dy, self.t[op.out + '/mask'], g, dy.numel(), op.keep, w.st)
+        self._put(op.inp, g)
+
+    def _fc_dims(self, op):
+        """(inputs, outputs) of a dense layer: an 'embed_w' FC reads [n, h, w, c] as one row-major [n, h w c] operand (no bias); the
+        classifier writes the padded class columns"""
+        if op.embed:
+            return self.spec[op.wname][0]
+        return self.shapes[op.inp][0], self.sub_centers * self.cpad
+
+    def _alloc_fc(self, w, op):
+        self._alloc_out(w, op, False)
+        fin, d = self._fc_dims(op)
+        w.need = max(w.need, _lib.query('fte_gemm_ws_bytes', w.n, d, fin))
+
+    def _fwd_fc(self, w, j, op):
+        fin, d = self._fc_dims(op)
+        w.call('fte_gemm_nn', self.t[op.inp], self.view(op.wname), None, self.t[op.out], w.n, d, fin, self.ws, self.ws_bytes, w.st)
+
+    def _bwd_fc(self, w, op, dy):
+        """a dense layer inside the body (the classifier is backward_head's)"""
+        fin, d = self.spec[op.wname][0]
+        x = self.t[op.inp]
+        self._wgrad(w, 'fte_gemm_tn', dy, x, dy, self.view(op.wname, self.grads), w.n, d, fin, w.wws, self.ws_bytes, w.wst)
+        dx = self._new(op.inp)
+        w.call('fte_gemm_nt', dy, self.view(op.wname), None, None, 0, None, dx, None, w.n, d, fin, self.ws, self.ws_bytes, w.st)
+        self._put(op.inp, dx)
 
     def _ensure_built(self, images, num_classes):
         if not self.built:
@@ -1267,8 +1318,8 @@ class GraphNet(Network):
                      self.num_classes, self.cpad, self.focal_gamma, self.focal_alpha, self.tower_scale / n, st)
             elif self.head in NORMALISED_HEADS:              # the margin on the raw classifier output; backward_head adds the norm terms
                 op = self.plan[-1]                           # (the running statistics of AdaFace move with BN's: heads.describe)
-                heads.margin_forward(self, self.t[op[2]], self.view(op[3]), self.t['logits'], labels, None, heads.describe(self), n,
-                                     self.shapes[op[2]][0], self.num_classes, self.cpad, self.tower_scale / n, st)
+                heads.margin_forward(self, self.t[op.inp], self.view(op.wname), self.t['logits'], labels, None, heads.describe(self), n,
+                                     self.shapes[op.inp][0], self.num_classes, self.cpad, self.tower_scale / n, st)
             else:
                 call('fte_softmax_ce_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.tower_scale / n, st)
@@ -1311,55 +1362,11 @@ class GraphNet(Network):
         body = [(lambda lo=lo, hi=hi: self.backward_body(lo, hi)) for lo, hi, _, _ in reversed(segs)]
         return ([self.backward_head] if self.has_classifier else []) + body
 
-    def _op_weight_names(self, op):
-        if op[0] in ('conv', 'gconv', 'dwconv') or (op[0] == 'fc' and self.spec[op[3]][1] == 'embed_w'):
-            return [op[3]]
-        if op[0] in ('se', 'seblock'):
-            w1, _, w2, _, _ = self._se_names(op[5] if op[0] == 'seblock' else op)
-            return [w1, w2]
-        return []
-
     def _segments(self):
-        """[(plan lo, plan hi, arena a, arena b)] in forward order: the body's plan split into FTE_GRAD_BUCKETS (default 4) runs of
-        about equal filter bytes.  The filters lie in the arena in the order the plan uses them, so a run of ops owns a contiguous
-        arena range; the first segment's range starts at 0 and so carries gamma / beta / biases of the whole net (0.1 - 0.4 MB: final
-        early, reduced last, at no cost).  A net whose filters are not in plan order keeps ONE body segment."""
-        if getattr(self, '_segs', None) is not None:
-            return self._segs
-        nops = len(self.plan) - (1 if self.has_classifier else 0)
-        one = [(0, nops, 0, self.cls_start)]
-        want = int(os.environ.get('FTE_GRAD_BUCKETS', '4'))
-        offs = []                                        # (plan index, first arena offset, end offset) of every op with filters
-        owned = set()
-        for j in range(nops):
-            names = self._op_weight_names(self.plan[j])
-            if names:
-                vs = [self.variables[w] for w in names]
-                owned.update(names)
-                offs.append((j, min(v.offset for v in vs), max(v.offset + v.size for v in vs)))
-        mono = all(offs[i][2] <= offs[i + 1][1] for i in range(len(offs) - 1)) and (not offs or offs[0][1] >= self.small_end)
-        # every variable of the body range that SOME plan op names must belong to an op seen above: a bucket's all-reduce is issued when
-        # the ops of its plan range have been walked, so a variable of another kind of op (none today; e.g. a mid-plan fc) could land in a
-        # bucket reduced before its gradient is final.  (Variables no op names -- ShuffleNet-v2-large's dead convs -- have no gradient.)
-        named = {x for op in self.plan[:nops] for x in op if isinstance(x, str) and x in self.variables}
-        stray = [k for k in named if self.small_end <= self.variables[k].offset < self.cls_start and k not in owned]
-        if want <= 1 or not mono or stray or len(offs) < want:
-            self._segs = one
-            return one
-        total = offs[-1][2] - offs[0][1]
-        cuts, acc, k = [], 0, 1                          # cut BEFORE the op at which the running size passes k / want of the total
-        for i, (j, a, b) in enumerate(offs):
-            if k < want and i > 0 and acc >= total * k / want:
-                cuts.append((j, a))
-                k += 1
-            acc += b - a
-        segs, lo, a0 = [], 0, 0
-        for j, a in cuts:
-            segs.append((lo, j, a0, a))
-            lo, a0 = j, a
-        segs.append((lo, nops, a0, self.cls_start))
-        self._segs = segs
-        return segs
+        """[(plan lo, plan hi, arena a, arena b)] in forward order: the body's all-reduce buckets (plan.segments)"""
+        if getattr(self, '_segs', None) is None:
+            self._segs = plan.segments(self.plan, self.variables, self.small_end, self.cls_start, self.has_classifier, self.opt.grad_buckets)
+        return self._segs
 
     def backward_head(self, join=True):
         """Classifier gradient (first all-reduce bucket) and the gradient wrt its input.  The filter gradient goes to the side stream
@@ -1368,323 +1375,23 @@ class GraphNet(Network):
         n = self._act_n
         st = _stream()
         op = self.plan[-1]
-        k = self.shapes[op[2]][0]
+        k = self.shapes[op.inp][0]
         self._grad = {}
         gin = torch.empty(n, k, dtype=torch.float32, device=self.device)
-        side = self.side if os.environ.get('FTE_HEAD_SIDE', '1') != '0' else None
+        side = self.side if self.opt.head_side else None
         norm = self.head in NORMALISED_HEADS             # their norm corrections ride on the stream of the product they correct
-        x, W = self.t[op[2]], self.view(op[3])
+        x, W = self.t[op.inp], self.view(op.wname)
         wst, wws = st, self.ws
         if side is not None:
             main = torch.cuda.current_stream()
             side.wait_event(main.record_event())         # G (the loss head's gradient) and the features are complete
             wst, wws = side.cuda_stream, self.ws_side
-        heads.classifier_dw(self, x, W, self.view(op[3], self.grads), n, k, self.sub_centers * self.cpad, wws, self.ws_bytes, wst, norm)      # (before the bucket is reduced)
+        heads.classifier_dw(self, x, W, self.view(op.wname, self.grads), n, k, self.sub_centers * self.cpad, wws, self.ws_bytes, wst, norm)      # (before the bucket is reduced)
         heads.classifier_dx(self, x, W, gin, n, k, self.sub_centers * self.cpad, self.ws, self.ws_bytes, st, norm)
         if side is not None and join:
             torch.cuda.current_stream().wait_stream(side)
-        self._grad[op[2]] = gin
+        self._grad[op.inp] = gin
 
-    def _new(self, name):
-        """a gradient buffer for tensor `name`: bf16 where the tensor (or, for a BN output folded into a gather, its gradient) is"""
-        if name in self.folded:                  # never stored: no tensor to take the layout from
-            z = self.t[self.folded[name][0]]
-            return torch.empty(z.shape, dtype=torch.int16 if name in self.g16 else torch.float32, device=self.device)
-        return torch.empty_like(self.t[name])
-
-    def backward_body(self, lo=0, hi=None):
-        """The backward walk over plan ops [lo, hi) (default: the whole body), last op first.  Segments are walked from the end of
-        the plan: the gradients in flight between two calls stay in self._grad; when a call returns its filter gradients are final."""
-        n = self._act_n
-        st = _stream()
-        call = _lib.call
-        T = self.t
-        s16 = self._act_s16
-        h16 = self.h16
-        nops = len(self.plan) - (1 if self.has_classifier else 0)
-        hi = nops if hi is None else hi
-        if hi == nops and not self.has_classifier:
-            self._grad = {self.feature_name: self._dfeat}
-            self._dfeat = None
-        G = self._grad
-        ops = self.plan[lo:hi]
-        # Filter gradients (conv / depthwise / grouped wgrad + their slab reductions) depend only on the layer's dz and its
-        # stored input, and nothing but the optimizer reads them: they go to a second stream and overlap the dgrad -> BN
-        # backward chain (these nets' kernels are 5-60 us long and leave CUs idle at their ramps and tails).  An event on
-        # the main stream costs it a ~7 us bubble, so the launches are queued and released a few layers at a time.
-        main, side = torch.cuda.current_stream(), self.side
-        wst, wws = (side.cuda_stream, self.ws_side) if side is not None else (st, self.ws)
-        pending = []
-        if hi == nops:
-            self._reduced = set()
-        reduced = self._reduced  # BN outputs whose mask / reduction pass ran in the epilogue of the data gradient that produced G[name]
-
-        def bn_below(name):
-            """arguments of the BN layer whose output `name` a fused data gradient lands on, or None"""
-            bj = self.fuse_bwd.get(name)
-            if bj is None:
-                return None
-            _, bout, binp, pre, res, relu = self.plan[bj]
-            if s16 and not (binp in h16 and bout in h16):
-                return None
-            b = self.bn[bout]
-            zmask = relu and res is None
-            return (T[binp], T[bout] if res is not None else None, self.view(pre + '/gamma'), b['mean'], b['rstd'],
-                    b['scale'] if zmask else None, b['shift'] if zmask else None), \
-                   (self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), b['coef'])
-
-        def wgrad(name, dy, *args):
-            if side is None:
-                call(name, *args)
-            else:
-                pending.append((name, dy, args))
-
-        def flush(limit=0):
-            if len(pending) > limit:
-                side.wait_event(main.record_event())
-                for name, dy, args in pending:
-                    dy.record_stream(side)
-                    call(name, *args)
-                del pending[:]
-        for op in reversed(ops):
-            kind, out = op[0], op[1]
-            if out == self.feature_name and self._dfeat is not None and out in G:
-                # the pooled features also feed the center loss: add its gradient to the classifier path's
-                d = G[out].shape[1]
-                call('fte_add_scaled_rows_cols', G[out], self._dfeat, self.ones_n, None, n, d, d, st)
-                self._dfeat = None
-            if kind == 'gather':
-                ga, gb = op[2]['gouts']
-                if ga not in G:
-                    continue
-                da = G.pop(ga)
-                db = G.pop(gb) if gb else None
-                gs = [(name, table, torch.empty((n,) + self.shapes[name], dtype=torch.int16 if s16 else torch.float32, device=self.device))
-                      for name, table in op[2]['bwd']]
-                (n0, t0, g0), (n1, t1, g1) = gs[0], (gs[1] if len(gs) > 1 else (None, None, None))
-                co0 = self.shapes[n0][-1]
-                if g1 is None:
-                    call('fte_channel_gather_s16' if s16 else 'fte_channel_gather', da, db, g0, t0, g0.numel() // co0, da.shape[-1],
-                         db.shape[-1] if db is not None else 0, co0, st)
-                else:                                    # the gradients of both sources in one launch
-                    call('fte_channel_gather_affine_s16' if s16 else 'fte_channel_gather_affine', da, db, g0, t0, co0, g1, t1, self.shapes[n1][-1], g0.numel() // co0,
-                         da.shape[-1], db.shape[-1] if db is not None else 0, None, None, 0, None, None, 0, st)
-                for name, _, g in gs:
-                    self._put(name, g)
-                continue
-            if out not in G:
-                continue
-            dy = G.pop(out)
-            if kind == 'dwconv':
-                _, _, inp, wname, stride = op
-                ih, iw, c = self.shapes[inp]
-                wgrad('fte_dwconv3x3_wgrad_s16' if s16 else 'fte_dwconv3x3_wgrad', dy, T[inp], dy, self.view(wname, self.grads), n, ih, iw, c, stride, wws, self.ws_bytes, wst)
-                dx = self._new(inp)
-                call('fte_dwconv3x3_dgrad_s16' if s16 else 'fte_dwconv3x3_dgrad', dy, self.view(wname), dx, n, ih, iw, c, stride, st)
-                self._put(inp, dx)
-            elif kind == 'dropout':
-                g = self._new(op[2])
-                call('fte_dropout_bwd', dy, T[out + '/mask'], g, dy.numel(), op[3], st)
-                self._put(op[2], g)
-            elif kind == 'gap':
-                ih, iw, c = self.shapes[op[2]]
-                g = self._new(op[2])
-                call('fte_gap_bwd_s16' if op[2] in h16 else 'fte_gap_bwd', dy, g, n, ih * iw, c, st)
-                self._put(op[2], g)
-            elif kind == 'maxpool':
-                ih, iw, c = self.shapes[op[2]]
-                g = self._new(op[2])
-                call('fte_maxpool3x3s2_bwd_s16' if s16 else 'fte_maxpool3x3s2_bwd', dy, T[out + '/idx'], g, n, ih, iw, c, st)
-                self._put(op[2], g)
-            elif kind == 'addrelu':
-                g = self._new(out)
-                call('fte_relu_bwd_s16' if s16 else 'fte_relu_bwd', dy, T[out], g, dy.numel(), st)
-                self._put(op[2], g)
-                self._put(op[3], g)                      # both addends see the same (read-only) gradient
-            elif kind == 'seblock':
-                _, _, zin, pre, scn, seop, _, _ = op
-                w1, b1, w2, b2, hd = self._se_names(seop)
-                ih, iw, c = self.shapes[out]
-                hw = ih * iw
-                b = self.bn[out]
-                fl = ((1 if zin in h16 else 0) | 2) if s16 else 0
-                sq, hid, gate = T[out + '/sq'], T[out + '/hid'], T[out + '/gate']
-                s1, s2, xm = T[out + '/s1'], T[out + '/s2'], T[out + '/xm']
-                dgate, dhid, dsq = self.ident[('se', out, 'dgate')], self.ident[('se', out, 'dhid')], self.ident[('se', 'dsq', c)]
-                gam, bet = self.view(pre + '/gamma'), self.view(pre + '/beta')
-                g = self._new(out)                             # dy * (out > 0): the shortcut's gradient, and the gate path's input
-                call('fte_se_bwd_gate', dy, T[out], T[zin], gam, bet, b['mean'], b['rstd'], gate, g, s1, s2, dgate, n, hw, c, fl, st)
-                wgrad('fte_gemm_tn', dgate, hid, dgate, self.view(w2, self.grads), n, c, hd, wws, self.ws_bytes, wst)
-                wgrad('fte_reduce_rows', dgate, dgate, self.view(b2, self.grads), None, 1, n, c, 1, 1.0, wst)
-                small = self._se_small(c, hd)
-                if small:                                      # d(pre-ReLU) = (dgate W2^T) * (hid > 0) in one launch
-                    call('fte_dense_small', dgate, self.view(w2), None, hid, dhid, n, hd, c, 1, 0, st)
-                else:
-                    call('fte_gemm_nt', dgate, self.view(w2), None, None, 0, None, dhid, None, n, c, hd, self.ws, self.ws_bytes, st)
-                    call('fte_act_bwd', dhid, hid, dhid, dhid.numel(), 0, st)                        # -> d(pre-ReLU)
-                wgrad('fte_gemm_tn', dhid, sq, dhid, self.view(w1, self.grads), n, hd, c, wws, self.ws_bytes, wst)
-                wgrad('fte_reduce_rows', dhid, dhid, self.view(b1, self.grads), None, 1, n, hd, 1, 1.0, wst)
-                if small:
-                    call('fte_dense_small', dhid, self.view(w1), None, None, dsq, n, c, hd, 1, 0, st)
-                else:
-                    call('fte_gemm_nt', dhid, self.view(w1), None, None, 0, None, dsq, None, n, hd, c, self.ws, self.ws_bytes, st)
-                call('fte_se_bn_bwd_coef', s1, s2, gate, dsq, xm, gam, b['mean'], b['rstd'], self.view(pre + '/gamma', self.grads),
-                     self.view(pre + '/beta', self.grads), b['coef'], n, hw, c, st)
-                dz = torch.empty_like(T[zin])
-                call('fte_se_bn_bwd_apply', g, T[zin], b['coef'], gate, dsq, dz, n, hw, c, fl, st)
-                self._put(scn, g)
-                self._put(zin, dz)
-            elif kind == 'se':
-                inp = op[2]
-                w1, b1, w2, b2, hd = self._se_names(op)
-                ih, iw, c = self.shapes[inp]
-                hw = ih * iw
-                sq, hid, gate = T[out + '/sq'], T[out + '/hid'], T[out + '/gate']
-                f32 = dict(dtype=torch.float32, device=self.device)
-                dx = self._new(inp)
-                # scratch preallocated in _alloc (three allocator calls per SE block and step otherwise)
-                dgate, dhid, dsq = self.ident[('se', out, 'dgate')], self.ident[('se', out, 'dhid')], self.ident[('se', 'dsq', c)]
-                if s16:          # reduction only; dx is written once by the apply pass below
-                    call('fte_channel_scale_bwd_s16', dy, T[inp], gate, dgate, n, hw, c, 1, st)
-                else:
-                    call('fte_channel_scale_bwd', dy, T[inp], gate, dx, dgate, n, hw, c, 1, st)         # dgate = d(pre-sigmoid)
-                # the gate's four parameter gradients feed nothing but the optimizer: side stream, like every filter gradient
-                wgrad('fte_gemm_tn', dgate, hid, dgate, self.view(w2, self.grads), n, c, hd, wws, self.ws_bytes, wst)
-                wgrad('fte_reduce_rows', dgate, dgate, self.view(b2, self.grads), None, 1, n, c, 1, 1.0, wst)
-                call('fte_gemm_nt', dgate, self.view(w2), None, None, 0, None, dhid, None, n, c, hd, self.ws, self.ws_bytes, st)
-                call('fte_act_bwd', dhid, hid, dhid, dhid.numel(), 0, st)                            # -> d(pre-ReLU)
-                wgrad('fte_gemm_tn', dhid, sq, dhid, self.view(w1, self.grads), n, hd, c, wws, self.ws_bytes, wst)
-                wgrad('fte_reduce_rows', dhid, dhid, self.view(b1, self.grads), None, 1, n, hd, 1, 1.0, wst)
-                call('fte_gemm_nt', dhid, self.view(w1), None, None, 0, None, dsq, None, n, hd, c, self.ws, self.ws_bytes, st)
-                if s16:
-                    call('fte_channel_scale_bwd_apply_s16', dy, gate, dsq, dx, n, hw, c, 1.0 / hw, st)
-                else:
-                    call('fte_bcast_add', dx, dsq, n, hw, c, 1.0 / hw, st)
-                self._put(inp, dx)
-            elif kind == 'gconv':
-                _, _, inp, wname, stride, groups = op
-                ih, iw, c = self.shapes[inp]
-                if self._gconv_pack(op) is not None:     # bf16 MFMA mode
-                    wgrad('fte_gconv3x3_wgrad_bf16_s16' if s16 else 'fte_gconv3x3_wgrad_bf16', dy, T[inp], dy, self.view(wname, self.grads), n, ih, iw, c, groups, stride, wws, self.ws_bytes, wst)
-                else:
-                    wgrad('fte_gconv3x3_wgrad', dy, T[inp], dy, self.view(wname, self.grads), n, ih, iw, c, groups, stride, wws, self.ws_bytes, wst)
-                dx = self._new(inp)
-                pk = self._gconv_pack(op)
-                bnb = bn_below(inp) if (pk is not None and s16 and self.fuse_bwd_gconv) else None
-                if bnb is not None:                      # ... with the mask / sums of the BN layer below in the epilogue
-                    (zbn, _, gam, mean, rstd, sc, sh), outs = bnb
-                    call('fte_gconv3x3_dgrad_bn_bf16_s16', dy, pk[1], zbn, gam, mean, rstd, sc, sh, dx, *outs, n, ih, iw, c, stride,
-                         self.ws, self.ws_bytes, st)
-                    reduced.add(inp)
-                elif pk is not None:                     # packed by this step's forward pass (the weights have not changed since)
-                    call('fte_gconv3x3_bf16_s16' if s16 else 'fte_gconv3x3_bf16', dy, pk[1], dx, n, ih, iw, c, stride, 1, st)
-                else:
-                    call('fte_gconv3x3_dgrad', dy, self.view(wname), dx, n, ih, iw, c, groups, stride, st)
-                self._put(inp, dx)
-            elif kind in ('bn', 'bnstats'):
-                _, _, inp, pre, res, relu = op
-                b = self.bn[out]
-                c = self.shapes[out][-1]
-                rows = dy.numel() // c
-                dz = torch.empty_like(T[inp])
-                if out in reduced:               # dy is the masked gradient already, dgamma / dbeta / coef are there: the apply pass alone
-                    call('fte_bn_bwd_apply', dy, T[inp], b['coef'], dz, rows, c, 3 if s16 else 0, st)
-                    if res is not None:
-                        self._put(res, dy)               # the shortcut sees the same (read-only) masked gradient
-                elif s16:
-                    fl = (1 if inp in h16 else 0) | 2
-                    gam, dgam, dbet = self.view(pre + '/gamma'), self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads)
-                    if res is not None:
-                        g = self._new(out)
-                        call('fte_bn_train_bwd_s16', dy, T[out], T[inp], gam, b['mean'], b['rstd'], None, None, g, dz, dgam, dbet,
-                             rows, c, fl, self.ws, self.ws_bytes, st)
-                        self._put(res, g)
-                    elif relu:
-                        call('fte_bn_train_bwd_s16', dy, None, T[inp], gam, b['mean'], b['rstd'], b['scale'], b['shift'], None, dz, dgam, dbet,
-                             rows, c, fl, self.ws, self.ws_bytes, st)
-                    else:
-                        call('fte_bn_train_bwd_s16', dy, None, T[inp], gam, b['mean'], b['rstd'], None, None, None, dz, dgam, dbet,
-                             rows, c, fl, self.ws, self.ws_bytes, st)
-                elif res is not None and not relu:         # BN + shortcut, no activation: dy goes unmasked into the BN backward and
-                    call('fte_bn_train_bwd', dy, None, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], dz,      # unchanged (no copy) to the shortcut
-                         self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), rows, c,
-                         self.ws, self.ws_bytes, st)
-                    self._add(res, dy)
-                elif res is not None:                      # the shortcut gets g = dy * (out > 0): a by-product of the reduce pass
-                    g = self._new(out)
-                    call('fte_bn_train_bwd_res', dy, T[out], T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], g, dz,
-                         self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), rows, c,
-                         self.ws, self.ws_bytes, st)
-                    self._put(res, g)
-                elif relu:                                 # ReLU mask recomputed from z: the output is not read
-                    call('fte_bn_train_bwd_zmask', dy, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], b['scale'], b['shift'],
-                         dz, self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), rows, c,
-                         self.ws, self.ws_bytes, st)
-                else:
-                    call('fte_bn_train_bwd', dy, None, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], dz,
-                         self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), rows, c,
-                         self.ws, self.ws_bytes, st)
-                if inp in self.shortcut_shared:
-                    self._add(inp, dz)               # ... plus the gradient the shortcut passed on
-                else:
-                    self._put(inp, dz)
-            elif kind == 'bnprelu':
-                _, _, inp, pre, aname = op
-                b = self.bn[out]
-                c = self.shapes[out][-1]
-                rows = dy.numel() // c
-                dz = torch.empty_like(T[inp])
-                call('fte_bn_prelu_train_bwd', dy, T[inp], self.view(pre + '/gamma'), b['mean'], b['rstd'], b['scale'], b['shift'], self.view(aname),
-                     dz, self.view(pre + '/gamma', self.grads), self.view(pre + '/beta', self.grads), self.view(aname, self.grads), rows, c,
-                     self.ws, self.ws_bytes, st)
-                self._put(inp, dz)
-            elif kind == 'fc':                           # a dense layer inside the body (the classifier is backward_head's)
-                fin, d = self.spec[op[3]][0]
-                x = T[op[2]]
-                wgrad('fte_gemm_tn', dy, x, dy, self.view(op[3], self.grads), n, d, fin, wws, self.ws_bytes, wst)
-                dx = self._new(op[2])
-                call('fte_gemm_nt', dy, self.view(op[3]), None, None, 0, None, dx, None, n, d, fin, self.ws, self.ws_bytes, st)
-                self._put(op[2], dx)
-            elif kind == 'conv':
-                _, _, inp, wname, stride = op
-                ih, iw, cin = self.shapes[inp]
-                k = self.spec[wname][0][0]
-                cout = self.shapes[out][-1]
-                gw = self.view(wname, self.grads)
-                if cin < 32 and self._direct_stem(k, cin, cout):
-                    call('fte_conv3x3_first_wgrad_s16' if s16 else 'fte_conv3x3_first_wgrad', T[inp], dy, gw, n, ih, iw, cin, cout, stride, self.ws, self.ws_bytes, st)
-                    continue
-                if cin < 32:                             # stem: filter gradient only
-                    oh, ow, _ = self.shapes[out]
-                    if s16:
-                        call('fte_conv2d_wgrad16', self.cols, dy, gw, n, oh, ow, stem_kpad(k, cin), cout, 1, 1, self.ws, self.ws_bytes, st)
-                    else:
-                        call('fte_gemm_tn', self.cols, dy, gw, n * oh * ow, cout, stem_kpad(k, cin), self.ws, self.ws_bytes, st)
-                    continue
-                wgrad('fte_conv2d_wgrad16' if s16 else 'fte_conv2d_wgrad', dy, T[inp], dy, gw, n, ih, iw, cin, cout, k, stride, wws, self.ws_bytes, wst)
-                flush(self.side_batch)
-                prev = G.pop(inp, None)                  # accumulate into an existing contribution through `addin`
-                dx = self._new(inp)
-                bnb = bn_below(inp) if self.fuse_bwd_conv else None
-                if bnb is not None:          # the last contribution to the gradient of a BN output: mask + BN sums in the epilogue
-                    ins, outs = bnb
-                    call('fte_conv2d_dgrad_bn', dy, self.w16[wname] if s16 else self.view(wname), prev, *ins, dx, *outs,
-                         n, ih, iw, cin, cout, k, stride, 1 if s16 else 0, self.ws, self.ws_bytes, st)
-                    reduced.add(inp)
-                elif s16:          # bf16 dz in, bf16 dx out (+ the bf16 contribution already there); the HWIO pack is this step's
-                    call('fte_conv2d_dgrad_s16', dy, self.w16[wname], prev, None, None, None, dx, None, None,
-                         n, ih, iw, cin, cout, k, stride, self.ws, self.ws_bytes, st)
-                else:
-                    call('fte_conv2d_dgrad', dy, self.view(wname), prev, None, None, None, dx, None, None,
-                         n, ih, iw, cin, cout, k, stride, self.ws, self.ws_bytes, st)
-                G[inp] = dx
-            else:
-                raise RuntimeError(kind)
-        if side is not None:
-            flush()
-            main.wait_stream(side)
-        if lo == 0:
-            self._grad = {}
 
     def _put(self, name, g):
         if name in self._grad:

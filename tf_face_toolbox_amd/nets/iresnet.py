@@ -10,8 +10,6 @@ the net the margin-head papers (ArcFace, sub-center ArcFace, Partial FC, AdaFace
 Variable names follow the ResNet scheme: `IResNet-50/stage2/block_0/conv1_3x3/weights`, `.../BatchNorm/{gamma,beta,moving_mean,
 moving_variance}`, `.../prelu/alpha`, `classifier/fc_classifier/weights`.  BN + PReLU pairs run fused (csrc/iresnet.hip); batch norm uses
 epsilon 1e-5 and momentum 0.9, the published code's values.  Differences from that code are listed in DESIGN.md section 8."""
-import os
-
 from .. import _lib
 from .graph import GraphNet
 
@@ -52,7 +50,7 @@ class IResNet(GraphNet):
         whole of stage 4's backward."""
         if getattr(self, '_segs', None) is None:
             nops = len(self.plan) - (1 if self.has_classifier else 0)
-            if int(os.environ.get('FTE_GRAD_BUCKETS', '4')) <= 1:
+            if self.opt.grad_buckets <= 1:
                 self._segs = [(0, nops, 0, self.cls_start)]
             else:
                 at = {op[1]: j for j, op in enumerate(self.plan)}
