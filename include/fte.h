@@ -64,7 +64,10 @@ int fte_get_mfma_dtype(void);
  * nets/sphere.py:41-42).  Process-wide; initialised from the environment variable FTE_CONV_ALGO = direct | winograd | auto.
  *   FTE_CONV_DIRECT   implicit GEMM over the nine taps (csrc/igemm.hip)
  *   FTE_CONV_WINOGRAD F(2x2,3x3) -- and F(3x3,2x2) for the filter gradient -- wherever the kernels exist (channels % 64 == 0)
- *   FTE_CONV_AUTO     (default) Winograd for the layers where it measured faster (>= 256 channels), direct elsewhere
+ *   FTE_CONV_AUTO     (default) Winograd for the layers where it measured faster, direct elsewhere: all three products of the layers
+ *                     with >= 128 channels (min(cin, cout); FTE_WINO_MIN_C, ops by the bit mask FTE_WINO_OPS, default 7), and the
+ *                     forward pass and filter gradient -- not the data gradient -- of 64-channel layers (FTE_WINO_OPS64, default 5:
+ *                     bit op of fte_conv3x3_algo).  The 64-channel packs are the large ones: 1.6 GB at 512 images of 56x56
  * Winograd needs the workspace fte_*_ws_bytes reports UNDER THE CURRENT SETTING (transformed tiles: 64 bytes per tile and channel);
  * with less the call runs the direct algorithm.  Same results to fp32 rounding (tests/test_gpu_wino.py: <= 2e-5 of max|ref|).
  * ------------------------------------------------------------------------- */
@@ -124,6 +127,18 @@ int fte_conv3x3_fwd_keep(const float* x, const float* w, const float* bias, cons
                          const float* res, float* z, float* y,
                          int n, int h, int wd, int cin, int cout, int stride, float* vpack,
                          void* ws, size_t ws_bytes, void* stream);
+/* fte_conv3x3_fwd_keep for the two convs of a residual block that both run the Winograd algorithm, so that the first conv's
+ * y = prelu(z) -- read by the second conv's tile transform and by nothing else -- never goes to memory:
+ *   xalpha != NULL: x is the PRE-activation z of the producing layer and xalpha its PReLU slopes [cin]; the tile transform forms
+ *                   x > 0 ? x : xalpha[c] * x itself (the forward epilogue's own expression: V equals the pack of that layer's y);
+ *                   xalpha = NULL: x is taken as it is
+ *   y = NULL:       only z is written (z must not be NULL then), by an epilogue that issues nothing for y and res
+ * vpack is required.  The call runs the Winograd algorithm or fails (FTE_EWORKSPACE; FTE_EINVAL without vpack): the direct and the bf16
+ * paths need the activated input and write y, and are never entered from here. */
+int fte_conv3x3_fwd_keep_act(const float* x, const float* xalpha, const float* w, const float* bias, const float* alpha,
+                             const float* res, float* z, float* y,
+                             int n, int h, int wd, int cin, int cout, int stride, float* vpack,
+                             void* ws, size_t ws_bytes, void* stream);
 
 /* Replaces Conv2DBackpropInput fused with the PReLU gradient of the PRODUCING
  * layer (tf.gradients, data_parallel.py:33):
@@ -146,9 +161,9 @@ int fte_conv3x3_wgrad(const float* x, const float* dz, float* dw,
                       int n, int h, int wd, int cin, int cout, int stride,
                       void* ws, size_t ws_bytes, void* stream);
 size_t fte_conv3x3_wgrad_ws_bytes(int n, int h, int wd, int cin, int cout, int stride);
-/* fte_conv3x3_wgrad reading the V pack fte_conv3x3_fwd_keep left for this layer instead of transforming x again (x is still the
- * layer's input and must be valid).  With vpack != NULL the call runs the Winograd algorithm or fails; vpack = NULL: exactly
- * fte_conv3x3_wgrad. */
+/* fte_conv3x3_wgrad reading the V pack fte_conv3x3_fwd_keep left for this layer instead of transforming x again.  With vpack != NULL
+ * the call runs the Winograd algorithm or fails and x is never read (it may be NULL: fte_conv3x3_fwd_keep_act leaves no activated
+ * input behind); vpack = NULL: exactly fte_conv3x3_wgrad. */
 int fte_conv3x3_wgrad_kept(const float* x, const float* dz, float* dw,
                            int n, int h, int wd, int cin, int cout, int stride, const float* vpack,
                            void* ws, size_t ws_bytes, void* stream);

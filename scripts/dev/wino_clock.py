@@ -22,8 +22,16 @@ for hw, c in ((28, 128), (14, 256), (7, 512)):
     al = torch.full((c,), 0.25, device='cuda'); da = torch.empty(c, device='cuda'); db = torch.empty(c, device='cuda')
     need = max(_lib.query('fte_conv3x3_fwd_ws_bytes', B, hw, hw, c, c, 1), _lib.query('fte_conv3x3_dgrad_ws_bytes', B, hw, hw, c, c, 1))
     ws = torch.empty(need // 4 + 1024, device='cuda'); wsb = ws.numel() * 4
+    vp = torch.empty(_lib.query('fte_wino_pack_bytes', B, hw, hw, c) // 4, device='cuda')
+    lean = lambda v: os.environ.__setitem__('FTE_WINO_LEAN', v)      # (the library reads it at every call)
+    # 'first' = the first conv of a residual block (no shortcut; y has one reader), 'second' = the data gradient of a block's second conv
+    # (no addin, no raw): generic epilogue on descriptors of zero records against the lean one (profiles/lean_epilogue.md)
     for op, f in (('fwd', lambda: _lib.call('fte_conv3x3_fwd', x, w, None, al, res, z, y, B, hw, hw, c, c, 1, ws, wsb, st)),
-                  ('dgrad', lambda: _lib.call('fte_conv3x3_dgrad', x, w, res, z, al, raw, dzp, da, db, B, hw, hw, c, c, 1, ws, wsb, st))):
+                  ('fwd first, generic', lambda: (lean('0'), _lib.call('fte_conv3x3_fwd_keep', x, w, None, al, None, z, y, B, hw, hw, c, c, 1, vp, ws, wsb, st))),
+                  ('fwd first, lean', lambda: (lean('1'), _lib.call('fte_conv3x3_fwd_keep_act', x, None, w, None, al, None, z, None, B, hw, hw, c, c, 1, vp, ws, wsb, st))),
+                  ('dgrad', lambda: _lib.call('fte_conv3x3_dgrad', x, w, res, z, al, raw, dzp, da, db, B, hw, hw, c, c, 1, ws, wsb, st)),
+                  ('dgrad second, generic', lambda: (lean('0'), _lib.call('fte_conv3x3_dgrad', x, w, None, z, al, None, dzp, da, None, B, hw, hw, c, c, 1, ws, wsb, st))),
+                  ('dgrad second, lean', lambda: (lean('1'), _lib.call('fte_conv3x3_dgrad', x, w, None, z, al, None, dzp, da, None, B, hw, hw, c, c, 1, ws, wsb, st)))):
         lib.fte_debug_set_wino_stamp(None)
         f(); torch.cuda.synchronize()
         t0 = time.time()

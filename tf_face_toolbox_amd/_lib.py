@@ -122,6 +122,7 @@ _SIGS = {
     'fte_conv3x3_algo': (c_int, [c_int] * 7),
     'fte_wino_pack_bytes': (c_size_t, [c_int] * 4),
     'fte_conv3x3_fwd_keep': (c_int, [_P] * 7 + [c_int] * 6 + [_P, _P, c_size_t, _P]),
+    'fte_conv3x3_fwd_keep_act': (c_int, [_P] * 8 + [c_int] * 6 + [_P, _P, c_size_t, _P]),
     'fte_conv3x3_wgrad_kept': (c_int, [_P] * 3 + [c_int] * 6 + [_P, _P, c_size_t, _P]),
     'fte_get_conv_algo': (c_int, []),
     'fte_l2_normalize_rows': (c_int, [_P] * 3 + [c_int] * 2 + [_P]),

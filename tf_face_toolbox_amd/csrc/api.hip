@@ -463,8 +463,13 @@ size_t fte_conv2d_fwd_ws_bytes(int n, int h, int wd, int cin, int cout, int ksiz
 static int conv2d_fwd_impl(const void* x, const void* w, bool src16, const float* bias, const float* alpha, const float* res,
                            float* z, float* y, uint16_t* y16, int n, int h, int wd, int cin, int cout, int ksize, int stride,
                            void* ws, size_t ws_bytes, void* stream, const uint16_t* res16 = nullptr, uint16_t* z16 = nullptr,
-                           float* stat_part = nullptr, int* stat_rows = nullptr, float* vpack = nullptr) {
-    if (!x || !w || (!y && !(src16 && y16)) || n <= 0 || cin % 32 || cout % 64 || (stride != 1 && stride != 2) || (ksize != 1 && ksize != 3))
+                           float* stat_part = nullptr, int* stat_rows = nullptr, float* vpack = nullptr,
+                           const float* xalpha = nullptr, bool z_only_ok = false) {
+    // xalpha / z_only_ok (fte_conv3x3_fwd_keep_act): x is the producing layer's z, activated in the tile transform; y may be absent.  Both
+    // exist on the Winograd path with a kept V only -- every other path below needs x as it is and writes y
+    const bool z_only = z_only_ok && !y && z && vpack;
+    if ((xalpha || z_only_ok) && !vpack) return FTE_EINVAL;
+    if (!x || !w || (!y && !(src16 && y16) && !z_only) || n <= 0 || cin % 32 || cout % 64 || (stride != 1 && stride != 2) || (ksize != 1 && ksize != 3))
         return FTE_EINVAL;
     const Pads ph = same_pads(h, ksize, stride), pw = same_pads(wd, ksize, stride);
     IgemmParams p;
@@ -487,16 +492,16 @@ static int conv2d_fwd_impl(const void* x, const void* w, bool src16, const float
         p.b_ld = cout;
     }
     if (!set_bytes(&p, (size_t)n * h * wd * cin, (size_t)ksize * ksize * cin * cout, src16 ? 2 : 4)) return FTE_EINVAL;
-    if (!src16 && !stat_part && y && wino_wanted(n, h, wd, cin, cout, ksize, stride, 0)) {
+    if (!src16 && !stat_part && (y || z_only) && wino_wanted(n, h, wd, cin, cout, ksize, stride, 0)) {
         WinoWs wl = wino_ws(n, h, wd, cin, cout, 0, 0);
         if (vpack) { wl.u_off = 0; wl.total = align_up((size_t)16 * cin * cout * 4); }      // the caller keeps V (fte_conv3x3_fwd_keep): ws holds the filters only
         if (ws && ws_bytes >= wl.total) {          // Winograd F(2x2,3x3): filter transform, tile transform, 16 products + output transform + epilogue
-            if (!aligned16({x, w, bias, alpha, res, z, y, ws, vpack})) return FTE_EINVAL;
+            if (!aligned16({x, w, bias, alpha, res, z, y, ws, vpack, xalpha})) return FTE_EINVAL;
             float* V = vpack ? vpack : (float*)((char*)ws + wl.v_off);
             float* U = (float*)((char*)ws + wl.u_off);
             hipError_t e = wino_transform_filter((const float*)w, U, cin, cout, 0, (hipStream_t)stream);
             if (e != hipSuccess) return (int)e;
-            e = wino_transform_tiles((const float*)x, V, n, h, wd, cin, 0, (hipStream_t)stream, wino_fwd_small_tiles());
+            e = wino_transform_tiles((const float*)x, V, n, h, wd, cin, 0, (hipStream_t)stream, wino_fwd_small_tiles(), xalpha);
             if (e != hipSuccess) return (int)e;
             WinoMMParams q;
             memset(&q, 0, sizeof(q));
@@ -550,6 +555,13 @@ int fte_conv3x3_fwd_keep(const float* x, const float* w, const float* bias, cons
     if (vpack && ((uintptr_t)vpack & 15)) return FTE_EINVAL;
     return conv2d_fwd_impl(x, w, false, bias, alpha, res, z, y, nullptr, n, h, wd, cin, cout, 3, stride, ws, ws_bytes, stream,
                            nullptr, nullptr, nullptr, nullptr, vpack);
+}
+int fte_conv3x3_fwd_keep_act(const float* x, const float* xalpha, const float* w, const float* bias, const float* alpha, const float* res,
+                             float* z, float* y, int n, int h, int wd, int cin, int cout, int stride, float* vpack,
+                             void* ws, size_t ws_bytes, void* stream) {
+    if (!vpack || ((uintptr_t)vpack & 15) || (!y && !z)) return FTE_EINVAL;
+    return conv2d_fwd_impl(x, w, false, bias, alpha, res, z, y, nullptr, n, h, wd, cin, cout, 3, stride, ws, ws_bytes, stream,
+                           nullptr, nullptr, nullptr, nullptr, vpack, xalpha, true);
 }
 int fte_conv3x3_algo(int n, int h, int wd, int cin, int cout, int stride, int op) {
     if (op < 0 || op > 2) return FTE_EINVAL;
@@ -904,7 +916,8 @@ size_t fte_conv3x3_wgrad_ws_bytes(int n, int h, int wd, int cin, int cout, int s
 static int conv2d_wgrad_impl(const void* x, const void* dz, bool src16, float* dw, int n, int h, int wd, int cin, int cout, int ksize, int stride,
                              void* ws, size_t ws_bytes, void* stream, const float* vpack = nullptr) {
     if (src16 && (cin % 8 || cout % 8)) return FTE_EINVAL;
-    if (!x || !dz || !dw || n <= 0 || cin % 4 || cout % 64 || (stride != 1 && stride != 2) || (ksize != 1 && ksize != 3)) return FTE_EINVAL;
+    // (x may be absent beside a kept V: that call reads the pack or fails below, it never reaches a path that reads x)
+    if ((!x && !vpack) || !dz || !dw || n <= 0 || cin % 4 || cout % 64 || (stride != 1 && stride != 2) || (ksize != 1 && ksize != 3)) return FTE_EINVAL;
     const Pads ph = same_pads(h, ksize, stride), pw = same_pads(wd, ksize, stride);
     {       // tensors of 2 GiB or more (32-bit buffer offsets): an argument error, reported before any workspace question
         const size_t lim = (size_t)1 << 31, es = src16 ? 2 : 4;

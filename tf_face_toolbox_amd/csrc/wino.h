@@ -23,7 +23,9 @@ inline size_t wino_pack_floats(long rows, int c) { return (size_t)((rows + 63) /
 // mode 0: V = B^T d B of the 4x4 input patch of every tile (forward: d = x; data gradient: d = dz)
 // mode 1: U' = G' d G'^T of the 2x2 tile itself (filter gradient: d = dz), G' = [[1,0],[.5,.5],[.5,-.5],[0,1]]
 // small: 256-thread blocks of half a row block each (mode 0; fits on a CU beside a resident block of the forward product)
-hipError_t wino_transform_tiles(const float* x, float* pack, int n, int h, int w, int c, int mode, hipStream_t st, bool small = false);
+// alpha (mode 0 only): x is the producing layer's pre-activation z, d = z > 0 ? z : alpha[c] * z is formed on the way in
+hipError_t wino_transform_tiles(const float* x, float* pack, int n, int h, int w, int c, int mode, hipStream_t st, bool small = false,
+                                const float* alpha = nullptr);
 // U = G g G^T of every 3x3 filter, packed with rows = the product's output channels.  w is HWIO [3][3][cin][cout];
 // dgrad = 0: rows = cout, k = cin (forward);  dgrad = 1: rows = cin, k = cout, taps rotated by 180 degrees (data gradient)
 hipError_t wino_transform_filter(const float* w, float* pack, int cin, int cout, int dgrad, hipStream_t st);
@@ -40,7 +42,10 @@ struct WinoMMParams {
     const float* ADD; float* RAW; const float* Zin; float* DZ; float* PA; float* PB;
     int amod;
 };
+// Absent tensors select a lean epilogue that issues nothing for them -- forward: R and Y both NULL (Z is the only result); data gradient:
+// ADD and RAW both NULL.  FTE_WINO_LEAN=0 keeps the generic epilogues (equal results; where the generic one adds the absent tensor's 0.0 a zero may change its sign).
 hipError_t wino_mm(const WinoMMParams& p, int epi, hipStream_t st);
+bool wino_lean_enabled();
 
 // filter gradient: slabs[s][t][cin][cout] = sum over the tiles of split s of V_t[tile][cin] * U'_t[tile][cout] with U' = G' e G'^T of
 // the 2x2 tiles of dz computed inside the kernel (dz: [n, h, w, cout] NHWC); then

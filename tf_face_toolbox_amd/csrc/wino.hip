@@ -68,8 +68,10 @@ constexpr int SLAB_B = SLAB_F * 4;             // 32 KiB
 // under the MFMA-bound kernel of the other stream (nets/sphere.py _body_walk: one stream 34.85 ms per step, two 33.9-34.1).
 // TPB = 256: half a row block (32 tiles) per block, one wave per SIMD -- 72 registers per SIMD, what is left beside a resident block of
 // the FORWARD product (2 x 216): the forward walk's two half shards (nets/sphere.py backbone) run one half's transform under the other's product.
-template <int MODE, int TPB>
-__global__ __launch_bounds__(TPB) void wino_tiles_kernel(const float* __restrict__ x, float* __restrict__ pack, int H, int W, int C,
+// ACT: x is the PRE-activation z of the producing layer and the patch is d = z > 0 ? z : alpha[c] * z -- the forward epilogue's own
+// expression, so V is what the transform of that layer's y = prelu(z) gives (a padding zero stays a zero) and the producer need not write y.
+template <int MODE, int TPB, bool ACT>
+__global__ __launch_bounds__(TPB) void wino_tiles_kernel(const float* __restrict__ x, const float* __restrict__ alpha, float* __restrict__ pack, int H, int W, int C,
                                                          int TH, int TW, long M, int MB, unsigned x_bytes) {
     constexpr int P = MODE == 0 ? 4 : 2;
     constexpr int SUB = 512 / TPB;             // blocks per row block
@@ -98,6 +100,15 @@ __global__ __launch_bounds__(TPB) void wino_tiles_kernel(const float* __restrict
             const bool ok = mv && yy >= 0 && yy < H && xx >= 0 && xx < W;
             d[i][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (unsigned)(((n * H + yy) * W + xx) * C) * 4u + choff : OOB, 0, 0));
         }
+    if constexpr (ACT) {
+        const f32x4 al4 = *reinterpret_cast<const f32x4*>(alpha + blockIdx.y * 32 + c4 * 4);
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) d[i][j][e] = d[i][j][e] > 0.f ? d[i][j][e] : al4[e] * d[i][j][e];
+    }
     const int ks = blockIdx.y * 4 + (c4 >> 1), sw = (r >> 4) & 1;
     float* o = pack + (((size_t)mb * KS + ks) * 16 * 64 + r) * 8 + (((c4 & 1) ^ sw) << 2);
     if constexpr (MODE == 0) {
@@ -170,9 +181,14 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restric
 // -> 0.087 ms).  Measured and NOT used for the last, partly filled round of a many-round launch: a launch of its own costs ~11 us of
 // ramp and epilogue beside its loop, as much as the resident blocks' last round saves (14x14x256 at 512 images: 0.482 -> 0.479 ms);
 // four extra loader waves in the half-tile block changed nothing (r6_notes.md 7).
-template <int EPI, int NWN>
+// LEAN: the epilogue of a launch whose optional tensors are absent, chosen by the launcher (wino_mm) -- forward: no shortcut R and no Y (the
+// first conv of a residual block, whose only reader takes z and applies the PReLU in its tile transform); data gradient: no ADD and no RAW
+// (a block's second conv).  The generic epilogue reaches the same results through descriptors of zero records, but still ISSUES those 16
+// of its 24 / 32 sixteen-byte instructions per wave and tile, and the epilogue is bound by vector-memory issue (profiles/lean_epilogue.md).
+template <int EPI, int NWN, bool LEAN>
 __global__ __launch_bounds__(256 * NWN, 1) void wino_mm_kernel(const WinoMMParams p, int NBX, int GRP, int vid0, int nvirt) {
     constexpr int NW = 4 * NWN;                    // waves per block
+    constexpr int NST = LEAN ? 8 : 16;             // 16-byte stores per wave and tile epilogue
     constexpr int BSTG = NWN * (SLAB_B / 2);       // bytes of a stage's filter image (NWN = 1: the block's 32 rows of the 64-row slab)
     constexpr int STG = SLAB_B + BSTG;             // bytes per stage
     extern __shared__ __attribute__((aligned(16))) char wsm[];
@@ -300,9 +316,9 @@ __global__ __launch_bounds__(256 * NWN, 1) void wino_mm_kernel(const WinoMMParam
                 __builtin_amdgcn_sched_barrier(0);
             });
             // this wave's pieces of step g + 1 have landed.  In a tile's first step behind an epilogue they are OLDER than the epilogue's
-            // 16 stores (vector-memory operations retire in issue order): vmcnt(16) leaves the stores draining under the MFMAs
+            // NST stores (vector-memory operations retire in issue order): vmcnt(NST) leaves the stores draining under the MFMAs
             if constexpr (WMM_ABL & 4) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            else if (s == 0 && !first) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            else if (s == 0 && !first) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NST) : "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
             // ---- half 1 ----
             // step g + 2: of this tile, or step 0 / 1 of the block's next tile (step 1 of the next tile waits for the epilogue)
@@ -389,13 +405,15 @@ __global__ __launch_bounds__(256 * NWN, 1) void wino_mm_kernel(const WinoMMParam
         f32x4 bias4 = {0.f, 0.f, 0.f, 0.f}, al4 = {1.f, 1.f, 1.f, 1.f};
         bool act = false;
         if constexpr (EPI == EPI_FWD) {
-            const __amdgpu_buffer_rsrc_t rsR = rsrc_of(p.R);
+            if constexpr (!LEAN) {
+                const __amdgpu_buffer_rsrc_t rsR = rsrc_of(p.R);
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+                for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2)
+                    for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) in0[b][h2][j] = ld4(rsR, off[b][h2][j]);
+                        for (int j = 0; j < 2; ++j) in0[b][h2][j] = ld4(rsR, off[b][h2][j]);
+            }
             if (p.bias) bias4 = *reinterpret_cast<const f32x4*>(p.bias + ch0);
             act = p.alpha != nullptr;
             if (act) al4 = *reinterpret_cast<const f32x4*>(p.alpha + ch0);
@@ -406,7 +424,10 @@ __global__ __launch_bounds__(256 * NWN, 1) void wino_mm_kernel(const WinoMMParam
 #pragma unroll
                 for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) { in0[b][h2][j] = ld4(rsA, off[b][h2][j]); in1[b][h2][j] = ld4(rsZ, off[b][h2][j]); }
+                    for (int j = 0; j < 2; ++j) {
+                        if constexpr (!LEAN) in0[b][h2][j] = ld4(rsA, off[b][h2][j]);
+                        in1[b][h2][j] = ld4(rsZ, off[b][h2][j]);
+                    }
             act = p.Zin != nullptr;
             if (act) al4 = *reinterpret_cast<const f32x4*>(p.alpha + ch0 % p.amod);
         }
@@ -437,13 +458,17 @@ __global__ __launch_bounds__(256 * NWN, 1) void wino_mm_kernel(const WinoMMParam
                     if constexpr (EPI == EPI_FWD) {
                         v += bias4;
                         st4(rsO0, o, v);
+                        if constexpr (!LEAN) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : al4[e] * v[e];          // (no activation: al = 1)
-                        v += in0[b][h2][j];
-                        st4(rsO1, o, v);
+                            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : al4[e] * v[e];          // (no activation: al = 1)
+                            v += in0[b][h2][j];
+                            st4(rsO1, o, v);
+                        }
                     } else {
-                        v += in0[b][h2][j];
-                        st4(rsO0, o, v);
+                        if constexpr (!LEAN) {
+                            v += in0[b][h2][j];
+                            st4(rsO0, o, v);
+                        }
                         const bool in = o != OOB;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -666,20 +691,32 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad_kernel(const float* __restr
 }
 
 // dw[kh][kw][ci][co] = A'^T (sum over shares, in share order) A',  A'^T = [[1,1,1,0],[0,1,-1,0],[0,1,1,-1]]
-__global__ __launch_bounds__(256) void wino_wgrad_finish_kernel(const float* __restrict__ slabs, float* __restrict__ dw, int S, long plane) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= plane) return;
+// Block = 32 filter elements x the 16 planes, thread = (plane t, element): its own ordered sum over the shares (the order, and so every
+// bit, of the one-thread-per-element form), then the 16 sums of an element meet in LDS and one thread applies A'^T . A'.  One thread per
+// element left a 64 x 64 layer with 16 blocks of threads that each walked 256 shares x 16 planes one load behind the other: 0.58 ms for
+// 67 MB, at the end of the step where nothing else runs (profiles/lean_epilogue.md).
+constexpr int WF_E = 32;                       // elements per block: a plane's 128-byte line per share
+__global__ __launch_bounds__(16 * WF_E) void wino_wgrad_finish_kernel(const float* __restrict__ slabs, float* __restrict__ dw, int S, long plane) {
+    __shared__ float sums[16][WF_E + 1];
+    const int t = threadIdx.x / WF_E, e = threadIdx.x % WF_E;
+    const long idx = (long)blockIdx.x * WF_E + e;
+    float acc = 0.f;
+    if (idx < plane) {
+        const float* src = slabs + (size_t)t * plane + idx;
+#pragma unroll 8
+        for (int s = 0; s < S; ++s) acc += src[(size_t)s * 16 * plane];
+    }
+    sums[t][e] = acc;
+    __syncthreads();
+    if (t != 0 || idx >= plane) return;
     float m[16];
 #pragma unroll
-    for (int t = 0; t < 16; ++t) m[t] = 0.f;
-    for (int s = 0; s < S; ++s)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) m[t] += slabs[((size_t)s * 16 + t) * plane + idx];
+    for (int k = 0; k < 16; ++k) m[k] = sums[k][e];
     // the 1/2 factors of G' = diag(1, 1/2, 1/2, 1) [[1,0],[1,1],[1,-1],[0,1]], left out of the kernel's U' (exact: powers of two)
 #pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        const float sc = (((t >> 2) == 1 || (t >> 2) == 2) ? 0.5f : 1.f) * (((t & 3) == 1 || (t & 3) == 2) ? 0.5f : 1.f);
-        m[t] *= sc;
+    for (int k = 0; k < 16; ++k) {
+        const float sc = (((k >> 2) == 1 || (k >> 2) == 2) ? 0.5f : 1.f) * (((k & 3) == 1 || (k & 3) == 2) ? 0.5f : 1.f);
+        m[k] *= sc;
     }
     float pr[3][4];
 #pragma unroll
@@ -708,15 +745,17 @@ WinoGeom wino_geom(int n, int h, int w) {
     return g;
 }
 
-hipError_t wino_transform_tiles(const float* x, float* pack, int n, int h, int w, int c, int mode, hipStream_t st, bool small) {
-    if (c % 32) return hipErrorInvalidValue;
+hipError_t wino_transform_tiles(const float* x, float* pack, int n, int h, int w, int c, int mode, hipStream_t st, bool small, const float* alpha) {
+    if (c % 32 || (alpha && mode != 0)) return hipErrorInvalidValue;
     const WinoGeom g = wino_geom(n, h, w);
     const size_t xb = (size_t)n * h * w * c * 4;
     if (xb >= ((size_t)1 << 31)) return hipErrorInvalidValue;
     const dim3 grid(8 * ((g.MB + 7) / 8) * (small ? 2 : 1), c / 32);
-    if (mode == 0 && small) hipLaunchKernelGGL((wino_tiles_kernel<0, 256>), grid, dim3(256), 0, st, x, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
-    else if (mode == 0) hipLaunchKernelGGL((wino_tiles_kernel<0, 512>), grid, dim3(512), 0, st, x, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
-    else hipLaunchKernelGGL((wino_tiles_kernel<1, 512>), grid, dim3(512), 0, st, x, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
+    if (mode == 0 && small && alpha) hipLaunchKernelGGL((wino_tiles_kernel<0, 256, true>), grid, dim3(256), 0, st, x, alpha, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
+    else if (mode == 0 && alpha) hipLaunchKernelGGL((wino_tiles_kernel<0, 512, true>), grid, dim3(512), 0, st, x, alpha, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
+    else if (mode == 0 && small) hipLaunchKernelGGL((wino_tiles_kernel<0, 256, false>), grid, dim3(256), 0, st, x, alpha, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
+    else if (mode == 0) hipLaunchKernelGGL((wino_tiles_kernel<0, 512, false>), grid, dim3(512), 0, st, x, alpha, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
+    else hipLaunchKernelGGL((wino_tiles_kernel<1, 512, false>), grid, dim3(512), 0, st, x, alpha, pack, h, w, c, g.th, g.tw, g.M, g.MB, (unsigned)xb);
     return hipGetLastError();
 }
 
@@ -728,7 +767,7 @@ hipError_t wino_transform_filter(const float* w, float* pack, int cin, int cout,
 }
 
 namespace {
-template <int EPI, int NWN>
+template <int EPI, int NWN, bool LEAN>
 hipError_t wino_mm_launch(const WinoMMParams& p, int NBX, int GRP, int vid0, int vid1, int grid, int tiles, hipStream_t st) {
     constexpr int NW = 4 * NWN;
     const size_t lds = 2 * ((size_t)SLAB_B + NWN * (SLAB_B / 2)) + 2560 + (size_t)NW * 16 * 36 * 4;      // two stages, row table + column partials, transpose patches
@@ -737,7 +776,7 @@ hipError_t wino_mm_launch(const WinoMMParams& p, int NBX, int GRP, int vid0, int
     (void)hipGetDevice(&dev);
     const unsigned bit = 1u << (dev & 31);
     if (!(attr.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_mm_kernel<EPI, NWN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_mm_kernel<EPI, NWN, LEAN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr.fetch_or(bit, std::memory_order_release);
     }
@@ -747,15 +786,34 @@ hipError_t wino_mm_launch(const WinoMMParams& p, int NBX, int GRP, int vid0, int
     const double bytes = frac * ((double)wino_pack_floats(p.g.M, p.K) * 4.0 + 16.0 * p.N * p.K * 4.0 + (double)p.g.n * p.g.h * p.g.w * p.N * 4.0 *
                                  (EPI == EPI_FWD ? (1 + (p.Z ? 1 : 0) + (p.R ? 1 : 0)) : (1 + (p.ADD ? 1 : 0) + (p.RAW ? 1 : 0) + (p.Zin ? 1 : 0))));
     const int h = igemm_prof_begin(sig, (int)((long)tiles * 64 / (p.N / 64)), p.N, 16 * p.K, flops, bytes, st);      // rows = tiles of the launch
-    hipLaunchKernelGGL((wino_mm_kernel<EPI, NWN>), dim3(grid), dim3(256 * NWN), lds, st, p, NBX, GRP, vid0, vid1);
-    igemm_prof_end(h, EPI == EPI_FWD ? (NWN == 2 ? "wino_mm_kernel<0,2>" : "wino_mm_kernel<0,1>") : (NWN == 2 ? "wino_mm_kernel<1,2>" : "wino_mm_kernel<1,1>"), st);
+    hipLaunchKernelGGL((wino_mm_kernel<EPI, NWN, LEAN>), dim3(grid), dim3(256 * NWN), lds, st, p, NBX, GRP, vid0, vid1);
+    // (the generic epilogues keep the names they have had; a lean one carries the third template argument)
+    static const char* const names[2][2][2] = {{{"wino_mm_kernel<0,1>", "wino_mm_kernel<0,1,1>"}, {"wino_mm_kernel<0,2>", "wino_mm_kernel<0,2,1>"}},
+                                               {{"wino_mm_kernel<1,1>", "wino_mm_kernel<1,1,1>"}, {"wino_mm_kernel<1,2>", "wino_mm_kernel<1,2,1>"}}};
+    igemm_prof_end(h, names[EPI == EPI_FWD ? 0 : 1][NWN - 1][LEAN ? 1 : 0], st);
     return hipGetLastError();
 }
+template <int NWN>
+hipError_t wino_mm_pick(const WinoMMParams& p, int epi, bool lean, int NBX, int GRP, int vid0, int vid1, int grid, int tiles, hipStream_t st) {
+    if (epi == EPI_FWD) return lean ? wino_mm_launch<EPI_FWD, NWN, true>(p, NBX, GRP, vid0, vid1, grid, tiles, st)
+                                    : wino_mm_launch<EPI_FWD, NWN, false>(p, NBX, GRP, vid0, vid1, grid, tiles, st);
+    return lean ? wino_mm_launch<EPI_DGRAD, NWN, true>(p, NBX, GRP, vid0, vid1, grid, tiles, st)
+                : wino_mm_launch<EPI_DGRAD, NWN, false>(p, NBX, GRP, vid0, vid1, grid, tiles, st);
+}
 }  // namespace
+
+// FTE_WINO_LEAN=0 (A/B hook, read at every call so that one process can run both): the generic epilogues everywhere
+bool wino_lean_enabled() {
+    const char* e = getenv("FTE_WINO_LEAN");
+    return !e || strcmp(e, "0") != 0;
+}
 
 hipError_t wino_mm(const WinoMMParams& p, int epi, hipStream_t st) {
     if (p.K % 64 || p.N % 64 || p.g.MB <= 0) return hipErrorInvalidValue;
     if ((size_t)p.g.n * p.g.h * p.g.w * p.N >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+    if (epi == EPI_FWD ? (!p.Y && !p.Z) : !p.DZ) return hipErrorInvalidValue;
+    // the lean epilogues: the absent tensors cost no instruction (the kernel's LEAN)
+    const bool lean = wino_lean_enabled() && (epi == EPI_FWD ? (!p.R && !p.Y) : (!p.ADD && !p.RAW));
     const int NB = p.N / 64;
     int NBX = NB < 2 ? NB : 2, GRP = NB / NBX;
     static const int plain = getenv("FTE_WINO_PLAIN_ORDER") ? atoi(getenv("FTE_WINO_PLAIN_ORDER")) : 0;      // A/B hook: no XCD-aware block order
@@ -786,13 +844,10 @@ hipError_t wino_mm(const WinoMMParams& p, int epi, hipStream_t st) {
     if (halves && L > 0 && 2 * L <= cus && (rounds == 1 || halves == 2)) tail_base = last;
     hipError_t e = hipSuccess;
     if (tail_base > 0) {
-        e = epi == EPI_FWD ? wino_mm_launch<EPI_FWD, 2>(p, NBX, GRP, 0, tail_base, grid, total - (tail_base < nvirt ? L : 0), st)
-                           : wino_mm_launch<EPI_DGRAD, 2>(p, NBX, GRP, 0, tail_base, grid, total - (tail_base < nvirt ? L : 0), st);
+        e = wino_mm_pick<2>(p, epi, lean, NBX, GRP, 0, tail_base, grid, total - (tail_base < nvirt ? L : 0), st);
         if (e != hipSuccess) return e;
     }
-    if (tail_base < nvirt)
-        e = epi == EPI_FWD ? wino_mm_launch<EPI_FWD, 1>(p, NBX, GRP, tail_base, nvirt, 2 * L, L, st)
-                           : wino_mm_launch<EPI_DGRAD, 1>(p, NBX, GRP, tail_base, nvirt, 2 * L, L, st);
+    if (tail_base < nvirt) e = wino_mm_pick<1>(p, epi, lean, NBX, GRP, tail_base, nvirt, 2 * L, L, st);
     return e;
 }
 
@@ -827,7 +882,7 @@ hipError_t wino_wgrad(const float* V, const float* dz, float* slabs, float* dw, 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const long plane = (long)cin * cout;
-    hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, slabs, dw, S, plane);
+    hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3((unsigned)((plane + WF_E - 1) / WF_E)), dim3(16 * WF_E), 0, st, slabs, dw, S, plane);
     return hipGetLastError();
 }
 

@@ -225,6 +225,7 @@ class SphereNet(Network):
             keep32 = not s16 or l == last
             self.z.append(torch.empty(n, c.hout, c.wout, c.cout, **f32) if keep32 else None)
             self.y.append(torch.empty(n, c.hout, c.wout, c.cout, **f32) if keep32 else None)
+        self.lean = [False] * len(self.convs)             # filled below, with the V packs
         if s16:
             self.z16 = [torch.empty(n, c.hout, c.wout, c.cout, **i16) for c in self.convs]
         self.emb = torch.empty(n, EMBED, **f32)
@@ -260,6 +261,15 @@ class SphereNet(Network):
                 if l > 0 and c.stride == 1 and q('fte_conv3x3_algo', n, c.hin, c.win, c.cin, c.cout, 1, 0) == 1 \
                         and q('fte_conv3x3_algo', n, c.hin, c.win, c.cin, c.cout, 1, 2) == 1:
                     self.vpack[l] = torch.empty(q('fte_wino_pack_bytes', n, c.hin, c.win, c.cin) // 4, **f32)
+            # Residual blocks whose two convs both keep a V pack (lean[l], l = the block's second conv): the training forward does not
+            # write the first conv's y = prelu(z).  Its readers are the second conv's tile transform, which takes z and alpha instead
+            # (fte_conv3x3_fwd_keep_act), and that conv's filter gradient, which reads the kept pack; the data gradient reads z.  Those
+            # y buffers (1.3 GB of writes per step at 512 images) are allocated only when another walk asks for them (_y_buf).
+            # FTE_WINO_LEAN=0: the walk that writes every y (A/B hook; the library reads the same variable for its epilogues).
+            for l, c in enumerate(self.convs):
+                if c.second == 1 and self.vpack[l] is not None and self.vpack[l - 1] is not None:
+                    self.lean[l] = True
+                    self.y[l - 1] = None
         for c in self.convs[1:]:
             need = max(need, q('fte_conv3x3_fwd_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride),
                        q('fte_conv3x3_wgrad_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride),
@@ -276,6 +286,13 @@ class SphereNet(Network):
         self._alloc_head(n)
         self._act_n = n
         self.y16 = None                                   # allocated on first use (_alloc_copies)
+
+    def _y_buf(self, l):
+        """y of layer l; the first conv of a lean block (_alloc_acts) gets its buffer on the first walk that writes it"""
+        if self.y[l] is None and not self._storage16():
+            c = self.convs[l]
+            self.y[l] = torch.empty(self._act_n, c.hout, c.wout, c.cout, dtype=torch.float32, device=self.device)
+        return self.y[l]
 
     def _head_width(self):
         """columns of the head's [n, .] buffers (s_raw, G, logits_buf)"""
@@ -371,9 +388,22 @@ class SphereNet(Network):
         self._copies_live = copies and keep              # backward of THIS forward may use the bf16 copies
         self._s16_live = s16 and keep
         self._vpack_live = keep and not copies           # ... or the V packs the Winograd layers keep
+        lean_live = self._vpack_live and os.environ.get('FTE_WINO_LEAN', '1') != '0'
+        self._lean_live = lean_live                      # ... with no y of the first conv of a lean block
+        nl = len(self.convs)
+        if not lean_live:                                # (before any stream forks: the part shards write them from two streams)
+            for l in range(nl):
+                self._y_buf(l)
         if copies:
             self._alloc_copies()
             self._pack_weights(st)
+        def part_pack(l, c, lo, hi, m):
+            vp = self.vpack[l]
+            if m != n:                               # a part shard's V pack is its part of the shard's (whole row blocks: _fwd_split)
+                per = ((c.hin + 1) // 2) * ((c.win + 1) // 2) * c.cin * 16      # floats per image
+                vp = vp[lo * per:hi * per] if hi < n else vp[lo * per:]        # (the last part keeps the shard's padding rows)
+            return vp
+
         def layer(l, c, lo, hi, ws, st):
             """layer l over images [lo, hi) on stream st (every forward kernel is per image: no statistics, nets/sphere.py:38-45)"""
             m = hi - lo
@@ -390,6 +420,13 @@ class SphereNet(Network):
                     call('fte_conv2d_fwd_s16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, self.y16[l - 2][lo:hi] if c.second == 1 else None,
                          z16, self.y16[l][lo:hi], zz, self.y[l][lo:hi] if self.y[l] is not None else None, m, c.hin, c.win, c.cin, c.cout, 3, c.stride,
                          ws, self.ws_bytes, st)
+            elif lean_live and self.lean[l]:             # second conv of a lean block: the input is prelu(z) of the first, formed in the tile transform
+                p = self.convs[l - 1]
+                call('fte_conv3x3_fwd_keep_act', self.z[l - 1][lo:hi], self.view(p.name + '/alpha'), wv, bv, av, self.y[l - 2][lo:hi], zz,
+                     self.y[l][lo:hi], m, c.hin, c.win, c.cin, c.cout, c.stride, part_pack(l, c, lo, hi, m), ws, self.ws_bytes, st)
+            elif lean_live and l + 1 < nl and self.lean[l + 1]:      # first conv of a lean block: z only
+                call('fte_conv3x3_fwd_keep_act', self.y[l - 1][lo:hi], None, wv, bv, av, None, zz, None,
+                     m, c.hin, c.win, c.cin, c.cout, c.stride, part_pack(l, c, lo, hi, m), ws, self.ws_bytes, st)
             elif l == 0:
                 call('fte_conv3x3_first_fwd', x[lo:hi], wv, bv, av, zz, self.y[0][lo:hi], m, c.hin, c.win, c.cin, c.cout, c.stride, st)
                 if copies:
@@ -397,17 +434,13 @@ class SphereNet(Network):
             else:
                 res = self.y[l - 2][lo:hi] if c.second == 1 else None
                 if copies:
-                    call('fte_conv2d_fwd16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, res, zz, self.y[l][lo:hi], self.y16[l][lo:hi],
+                    call('fte_conv2d_fwd16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, res, zz, self._y_buf(l)[lo:hi], self.y16[l][lo:hi],
                          m, c.hin, c.win, c.cin, c.cout, 3, c.stride, ws, self.ws_bytes, st)
                 elif keep and self.vpack[l] is not None:
-                    vp = self.vpack[l]
-                    if m != n:                               # a part shard's V pack is its part of the shard's (whole row blocks: _fwd_split)
-                        per = ((c.hin + 1) // 2) * ((c.win + 1) // 2) * c.cin * 16      # floats per image
-                        vp = vp[lo * per:hi * per] if hi < n else vp[lo * per:]        # (the last part keeps the shard's padding rows)
-                    call('fte_conv3x3_fwd_keep', self.y[l - 1][lo:hi], wv, bv, av, res, zz, self.y[l][lo:hi],
-                         m, c.hin, c.win, c.cin, c.cout, c.stride, vp, ws, self.ws_bytes, st)
+                    call('fte_conv3x3_fwd_keep', self._y_buf(l - 1)[lo:hi], wv, bv, av, res, zz, self._y_buf(l)[lo:hi],
+                         m, c.hin, c.win, c.cin, c.cout, c.stride, part_pack(l, c, lo, hi, m), ws, self.ws_bytes, st)
                 else:
-                    call('fte_conv3x3_fwd', self.y[l - 1][lo:hi], wv, bv, av, res, zz, self.y[l][lo:hi],
+                    call('fte_conv3x3_fwd', self._y_buf(l - 1)[lo:hi], wv, bv, av, res, zz, self._y_buf(l)[lo:hi],
                          m, c.hin, c.win, c.cin, c.cout, c.stride, ws, self.ws_bytes, st)
 
         split = self._fwd_split(n, copies)
@@ -611,7 +644,8 @@ class SphereNet(Network):
                 call('fte_conv2d_wgrad16', self.y16[l - 1], dz16_cur, gw, n, c.hin, c.win, c.cin, c.cout, 3, c.stride,
                      wws, self.ws_bytes, wst)
             elif getattr(self, '_vpack_live', False) and self.vpack[l] is not None:
-                call('fte_conv3x3_wgrad_kept', self.y[l - 1], dz_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
+                # (x is never read beside a kept pack -- fte.h -- and in a lean block y[l - 1] was not written)
+                call('fte_conv3x3_wgrad_kept', None if getattr(self, '_lean_live', False) and self.lean[l] else self.y[l - 1], dz_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
                      self.vpack[l], wws, self.ws_bytes, wst)
             else:
                 call('fte_conv3x3_wgrad', self.y[l - 1], dz_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
