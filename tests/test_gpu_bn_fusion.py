@@ -43,6 +43,23 @@ def _pack16(wt):
     return w16, w16t
 
 
+def _symbols(fn):
+    """kernel symbols of the MFMA launches `fn` makes"""
+    call('fte_prof_enable', 1)
+    fn()
+    torch.cuda.synchronize()
+    call('fte_prof_enable', 0)
+    return [r[5] for r in _lib.prof_records(shapes=True)]
+
+
+def _assert_family(syms, n, h, w, cin, cout, ks, stride):
+    """the streaming pointwise kernel exactly where fte_conv2d_bn_fwd_folds says so, and nowhere else"""
+    if query('fte_conv2d_bn_fwd_folds', n, h, w, cin, cout, ks, stride, 1) == 1:
+        assert len(syms) == 1 and syms[0].startswith('pw16_kernel<'), syms
+    else:
+        assert syms and not [s for s in syms if 'pw16' in s], syms
+
+
 def _stats_ref(z, gamma, beta, mm, mv):
     c = z.shape[-1]
     rows = z.size // c
@@ -108,10 +125,12 @@ def test_conv_bn_fwd_bf16_storage(n, h, w, cin, cout, ks, stride):
     wsb, nb = ws(query('fte_conv2d_bn_fwd_ws_bytes', n, h, w, cin, cout, ks, stride))
     _lib.set_mfma_dtype('bf16s')
     try:
-        call('fte_conv2d_bn_fwd', _dev16(x), w16t, z16, dev(gamma), dev(beta), mean, rstd, scale, shift, mmd, mvd, EPS, DECAY,
-             None, None, None, n, h, w, cin, cout, ks, stride, 1, wsb, nb, stream())
+        x16 = _dev16(x)
+        syms = _symbols(lambda: call('fte_conv2d_bn_fwd', x16, w16t, z16, dev(gamma), dev(beta), mean, rstd, scale, shift, mmd, mvd, EPS, DECAY,
+                                     None, None, None, n, h, w, cin, cout, ks, stride, 1, wsb, nb, stream()))
     finally:
         _lib.set_mfma_dtype('f32')
+    _assert_family(syms, n, h, w, cin, cout, ks, stride)
     zs = _host16(z16)
     # one bf16 rounding of an fp32 accumulation of exact products: within half an ulp (2^-9 relative) plus the fp32 noise
     assert np.abs(zs - z_ref).max() <= 2.0 ** -8 * np.abs(z_ref).max()
@@ -120,6 +139,41 @@ def test_conv_bn_fwd_bf16_storage(n, h, w, cin, cout, ks, stride):
     check_maxabs(host(mean), cache['mean'], 2e-6, 'mean'); check_maxabs(host(rstd), cache['rstd'], 4e-6, 'rstd')
     check_maxabs(host(scale), sc_ref, 4e-6, 'scale'); check_maxabs(host(shift), sh_ref, 1e-5, 'shift')
     check_maxabs(host(mmd), mm_ref, 2e-6, 'moving mean'); check_maxabs(host(mvd), mv_ref, 2e-6, 'moving variance')
+
+
+# The forward forms of igemm16_bn_kernel<BM,BN,4,2,0,NST,MINW> (csrc/igemm16.hip igemm16_launch: the three-stage ring while the launch
+# has at most 256 tiles and at least six 64-deep K-steps, else the two-stage ring; the tile from csrc/api.hip plan_rows / pick_tile, whose
+# bf16 floor is 120 tiles), each at a shape that reaches it NATURALLY under bf16 storage, with a neighbour on the other side of every
+# boundary.  M = n h w; tiles = ceil(M / 128) x (N / BN).  (n, h, w, cin, cout, ks), the symbol that must run, exact-placement check too?
+IGEMM16_BN_CASES = [
+    ((77, 7, 7, 512, 512, 1), 'igemm16_bn_kernel<128,128,4,2,0,3,2>', True),      # 30 x 4 = 120 tiles of 128x128: the floor, three stages
+    ((58, 8, 8, 512, 512, 1), 'igemm16_bn_kernel<128,64,4,2,0,3,4>', False),      # 29 x 4 = 116 < 120: the 128x64 tile (232), three stages
+    ((43, 14, 14, 512, 512, 1), 'igemm16_bn_kernel<128,128,4,2,0,2,4>', True),    # 66 x 4 = 264 > 256: two stages
+    ((8192, 1, 1, 512, 512, 1), 'igemm16_bn_kernel<128,128,4,2,0,3,2>', False),   # 256 tiles: the last three-stage launch
+    ((8193, 1, 1, 512, 512, 1), 'igemm16_bn_kernel<128,128,4,2,0,2,4>', False),   # 260 tiles, one row in the last tile row
+    ((77, 10, 20, 512, 64, 1), 'igemm16_bn_kernel<128,64,4,2,0,3,4>', False),     # 121 tiles of 128x64 (61 of 256x64 miss the floor)
+    ((119, 8, 16, 512, 64, 1), 'igemm_bn_kernel<64,64,', False),                  # 119 tiles of 128x64: below the floor, the 64x64 tile kernel
+    ((77, 10, 20, 320, 64, 1), 'igemm16_bn_kernel<128,64,4,2,0,2,6>', False),     # five K-steps: two stages at any tile count
+    ((77, 10, 20, 384, 64, 1), 'igemm16_bn_kernel<128,64,4,2,0,3,4>', False),     # six K-steps: three stages
+    ((112, 14, 14, 512, 192, 1), 'igemm16_bn_kernel<128,64,4,2,0,2,6>', False),   # 172 x 3 = 516 tiles: the unsplit bf16-storage plan (>= 512)
+    ((170, 8, 16, 512, 192, 1), 'igemm_bn_kernel<256,64,', False),                # 170 x 3 = 510 < 512: pick_tile's 256x64 (255 tiles)
+    ((10, 27, 29, 64, 128, 3), 'igemm16_bn_kernel<128,64,4,2,0,3,4>', False),     # 3x3, gathered A: 62 x 2 = 124 tiles of 128x64, nine K-steps
+]
+
+
+@pytest.mark.parametrize('dims,symbol,exact', IGEMM16_BN_CASES, ids=['x'.join(map(str, d)) for d, _, _ in IGEMM16_BN_CASES])
+def test_conv_bn_fwd_bf16_storage_igemm16_forms(dims, symbol, exact):
+    """z element by element (|got - ref| <= 2^-8 |ref| + 2e-5 max|ref|), the statistics against float64 statistics of the stored z with this
+    module's limits, every output poisoned first (tests/tile_worker.py bn_random); on the 120- and 264-tile shapes the selection-filter
+    check too: z bit for bit (bn_exact)"""
+    import tile_worker as tw
+    n, h, w, cin, cout, ks = dims
+    assert query('fte_conv2d_bn_fwd_folds', n, h, w, cin, cout, ks, 1, 1) == 0
+    for fn in ([tw.bn_exact] if exact else []) + [tw.bn_random]:
+        syms, errs, fails = fn(dims + (1,), False, None)
+        print('IGEMM16_BN %-22s %-9s %s  %s' % ('x'.join(map(str, dims)), fn.__name__, ','.join(syms), ' '.join('%s=%.3e' % kv for kv in sorted(errs.items()))))
+        assert len(syms) == 1 and (syms[0] == symbol if symbol.endswith('>') else syms[0].startswith(symbol)), (syms, symbol)
+        assert not fails, fails
 
 
 DGRAD_SHAPES = [
@@ -328,11 +382,12 @@ def test_conv_bn_fwd_folds_the_normalise_pass_of_the_bn_in_front(n, h, w, cin, c
             mm, mv = torch.zeros(cout, device='cuda'), torch.ones(cout, device='cuda')
             ys = torch.full((n, h, w, cin), 0x4100, dtype=torch.int16, device='cuda')
             if fold:
-                call('fte_conv2d_bn_fwd', zp16, w16t, z16, dev(gamma), dev(beta), st[0], st[1], st[2], st[3], mm, mv, EPS, DECAY,
-                     dev(isc), dev(ish), ys, n, h, w, cin, cout, 1, 1, 1, wsb, nb, stream())
+                syms = _symbols(lambda: call('fte_conv2d_bn_fwd', zp16, w16t, z16, dev(gamma), dev(beta), st[0], st[1], st[2], st[3], mm, mv, EPS, DECAY,
+                                             dev(isc), dev(ish), ys, n, h, w, cin, cout, 1, 1, 1, wsb, nb, stream()))
             else:
-                call('fte_conv2d_bn_fwd', y_ref, w16t, z16, dev(gamma), dev(beta), st[0], st[1], st[2], st[3], mm, mv, EPS, DECAY,
-                     None, None, None, n, h, w, cin, cout, 1, 1, 1, wsb, nb, stream())
+                syms = _symbols(lambda: call('fte_conv2d_bn_fwd', y_ref, w16t, z16, dev(gamma), dev(beta), st[0], st[1], st[2], st[3], mm, mv, EPS, DECAY,
+                                             None, None, None, n, h, w, cin, cout, 1, 1, 1, wsb, nb, stream()))
+            assert len(syms) == 1 and syms[0].startswith('pw16_kernel<') and syms[0].endswith(',%d,1>' % (1 if fold else 0)), syms
             outs.append((z16, st, mm, mv, ys))
     finally:
         _lib.set_mfma_dtype('f32')

@@ -5,6 +5,10 @@ every result with the float64 oracle (oracle/ops.py), image block by image block
 
     python tests/tile_worker.py '[["wgrad", n, h, w, cin, cout, stride], ["fwd", ...], ["dgrad", ...]]'
 
+The case kinds 'bnfwd1' / 'bnfold1' run fte_conv2d_bn_fwd of a 1x1 conv under bf16 storage, plain / with the BN in front folded in (the
+FTE_PW16_* hooks of csrc/pw16.hip are read once per process too); their checks are the functions tests/test_gpu_pw16_edges.py calls
+in-process for the default environment.
+
 Prints one JSON line: {"cases": [{"case": [...], "symbols": [...kernel symbols the launch records name...], "splits": [...],
 "errors": {...}}], "ok": true|false}.  Tolerances are tests/util_gpu.py's (2e-5 max-abs / rel-L2 against float64)."""
 import json
@@ -243,6 +247,219 @@ def run_s16wgrad(n, h, w, cin, cout, stride, r):
     return syms, splits, {'dw_maxabs_rel': e / s}, e / s <= TOL_MAXABS
 
 
+# ---- fte_conv2d_bn_fwd under bf16 storage (tests/test_gpu_pw16_edges.py, tests/test_gpu_bn_fusion.py): conv, rounded z, the batch
+# statistics of the stored values; folded: the BN in front of the conv in the loader, y side-stored.  Called in-process by those modules
+# for the default environment and through main() ('bnfwd1' / 'bnfold1') where a hook of csrc/pw16.hip is set.
+BN_EPS, BN_DECAY = 1e-3, 0.999
+CANARY16 = 0x7fc1       # a bf16 NaN no kernel stores: an element still holding it was never written
+GUARD = 8               # rows behind row M of z and y_side that must keep the canary
+# the limits of tests/test_gpu_bn_fusion.py on the statistics of the stored z (max-abs over the channels, relative to the largest reference)
+BN_LIMITS = {'mean': 2e-6, 'rstd': 4e-6, 'scale': 4e-6, 'shift': 1e-5, 'moving_mean': 2e-6, 'moving_var': 2e-6}
+
+
+def _bf64(a):
+    return ops.bf16_round(np.asarray(a, np.float64))
+
+
+def _dev16(a):
+    """float64 array of bf16-exact values -> int16 device tensor holding the bf16 bits"""
+    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float32).to(torch.bfloat16).view(torch.int16).cuda()
+
+
+def _host16(t):
+    return t.view(torch.bfloat16).float().cpu().numpy().astype(np.float64)
+
+
+def selection_filter(K, N, a=5, b=3, unit=False):
+    """HWIO [1, 1, K, N] filter with ONE non-zero per output channel: W[n][k] = 2^e at k = (a n + b) mod K (a odd), e = n mod 5 - 2 (0 with
+    `unit`).  Returns (filter, the selected input channel per n, the power of two per n)."""
+    n = np.arange(N)
+    k, g = (a * n + b) % K, 2.0 ** (((n % 5) - 2) * (0 if unit else 1))
+    wt = np.zeros((1, 1, K, N))
+    wt[0, 0, k, n] = g
+    return wt, k, g
+
+
+def coded_input(M, K):
+    """x[m][k] = (((7 m + 13 k) mod 251) - 125) / 64: every value bf16-exact (|numerator| < 2^7), no two neighbours alike"""
+    m, k = np.arange(M, dtype=np.int64)[:, None], np.arange(K, dtype=np.int64)[None, :]
+    return (((7 * m + 13 * k) % 251) - 125) / 64.0
+
+
+def stats64(zs, gamma, beta, mm, mv):
+    """float64 statistics of the stored rows [M, C] and what bn_finalize derives from them"""
+    mean, var = zs.mean(axis=0), zs.var(axis=0)
+    rstd = 1.0 / np.sqrt(var + BN_EPS)
+    scale = gamma * rstd
+    mmr, mvr = ops.bn_moving_update(mm, mv, mean, var, zs.shape[0])
+    return {'mean': mean, 'rstd': rstd, 'scale': scale, 'shift': beta - mean * scale, 'moving_mean': mmr, 'moving_var': mvr}
+
+
+def bn_fwd_call(x16, wt, dims, gamma, beta, mm, mv, fold=None, nrb=None):
+    """One fte_conv2d_bn_fwd call (s16 = 1) on x16 [M, cin] bf16 bits with every output poisoned first: z and y_side hold CANARY16 and carry
+    GUARD rows behind row M, the statistics and the WHOLE workspace hold NaN.  fold = (in_scale, in_shift) device tensors or None.  nrb: the
+    partial rows the streaming kernel must write (rows [nrb, granted) must stay NaN), or None for the tile kernels.
+    -> dict(z16 [M, cout], y16 [M, cin] | None, stats {name: float64 [cout]}, symbols, fails [messages])"""
+    n, h, w, cin, cout, ks, stride = dims
+    M = n * h * w
+    assert stride == 1
+    wd = torch.tensor(np.ascontiguousarray(wt), dtype=torch.float32, device='cuda')
+    w16 = torch.empty(ks * ks * cin * cout, dtype=torch.int16, device='cuda'); w16t = torch.empty_like(w16)
+    call('fte_pack_weights_bf16', wd, w16, w16t, ks, cin, cout, stream())
+    z16 = torch.full((M + GUARD, cout), CANARY16, dtype=torch.int16, device='cuda')
+    ys = torch.full((M + GUARD, cin), CANARY16, dtype=torch.int16, device='cuda') if fold else None
+    st = [torch.full((cout,), float('nan'), device='cuda') for _ in range(4)]
+    f32 = lambda a: torch.tensor(a, dtype=torch.float32, device='cuda')
+    mmd, mvd = f32(mm), f32(mv)
+    nbytes = query('fte_conv2d_bn_fwd_ws_bytes', n, h, w, cin, cout, ks, stride)
+    wsb = torch.full((nbytes // 4 + 1024,), float('nan'), device='cuda')       # 4 KB behind the grant: must stay NaN too
+    prev = _lib.precision_mode()
+    _lib.set_mfma_dtype('bf16s')
+    try:
+        _lib.query('fte_prof_enable', 1)
+        call('fte_conv2d_bn_fwd', x16, w16t, z16, f32(gamma), f32(beta), st[0], st[1], st[2], st[3], mmd, mvd, BN_EPS, BN_DECAY,
+             fold[0] if fold else None, fold[1] if fold else None, ys, n, h, w, cin, cout, ks, stride, 1, wsb, nbytes, stream())
+        torch.cuda.synchronize()
+        _lib.query('fte_prof_enable', 0)
+    finally:
+        _lib.set_mfma_dtype(prev)
+    syms = [r[5] for r in _lib.prof_records(shapes=True)]
+    fails = []
+    if not bool((z16[M:] == CANARY16).all()):
+        fails.append('z: a guard row behind row M was written')
+    if bool((z16[:M] == CANARY16).any()):
+        fails.append('z: %d elements never written' % int((z16[:M] == CANARY16).sum()))
+    if fold:
+        if not bool((ys[M:] == CANARY16).all()):
+            fails.append('y_side: a guard row behind row M was written')
+        if bool((ys[:M] == CANARY16).any()):
+            fails.append('y_side: %d elements never written' % int((ys[:M] == CANARY16).sum()))
+    if not bool(torch.isnan(wsb[nbytes // 4:]).all()):
+        fails.append('workspace: written behind the granted bytes')
+    if nrb is not None:
+        used = nrb * 3 * cout
+        if not bool(torch.isfinite(wsb[:used]).all()):
+            fails.append('workspace: %d words of the %d partial rows never written' % (int((~torch.isfinite(wsb[:used])).sum()), nrb))
+        if not bool(torch.isnan(wsb[used:]).all()):
+            fails.append('workspace: a partial row >= nrb = %d was written' % nrb)
+    names = ['mean', 'rstd', 'scale', 'shift']
+    stats = {k: st[i].cpu().numpy().astype(np.float64) for i, k in enumerate(names)}
+    stats['moving_mean'] = mmd.cpu().numpy().astype(np.float64); stats['moving_var'] = mvd.cpu().numpy().astype(np.float64)
+    for k, v in stats.items():
+        if not np.isfinite(v).all():
+            fails.append('%s: %d channels not finite' % (k, int((~np.isfinite(v)).sum())))
+    return dict(z16=z16[:M], y16=ys[:M] if fold else None, stats=stats, symbols=syms, fails=fails)
+
+
+def _fold_coef(r, cin):
+    """scale / shift of the BN in front: in_shift > 0 on EVERY channel, so that a row the loader fetched as zeros (beyond row M) becomes a
+    non-zero operand -- the statistics must still count M rows only"""
+    isc = (1 + 0.2 * r.standard_normal(cin)).astype(np.float32)
+    ish = (0.1 + 0.3 * np.abs(r.standard_normal(cin))).astype(np.float32)
+    return isc, ish
+
+
+def _bn_apply_ref(x16, isc, ish, M, cin):
+    y = torch.empty((M, cin), dtype=torch.int16, device='cuda')
+    call('fte_bn_apply', x16, torch.tensor(isc, device='cuda'), torch.tensor(ish, device='cuda'), None, y, M, cin, 1, 3, stream())
+    return y
+
+
+def _where2(mask, cout):
+    i = int(np.flatnonzero(mask.reshape(-1))[0])
+    return 'first at (row, channel) = (%d, %d), %d in all' % (i // cout, i % cout, int(mask.sum()))
+
+
+def bn_exact(dims, fold, nrb=None, seed=31):
+    """EXACT placement (1x1 only): selection filter x position-coded input -- every product and sum exact, so z must equal the expected
+    tensor bit for bit; folded: y_side bit-equal to fte_bn_apply, z bit-equal to the selection of that y.  -> (symbols, errors, fails)"""
+    n, h, w, cin, cout, ks, stride = dims
+    M = n * h * w
+    assert ks == 1
+    r = np.random.default_rng(seed)
+    wt, sel, g = selection_filter(cin, cout)
+    x16 = _dev16(coded_input(M, cin))
+    gamma = 1 + 0.2 * r.standard_normal(cout); beta = 0.3 * r.standard_normal(cout)
+    mm = r.standard_normal(cout) * 0.1; mv = 1 + 0.1 * r.random(cout)
+    coef = None
+    if fold:
+        isc, ish = _fold_coef(r, cin)
+        coef = (torch.tensor(isc, device='cuda'), torch.tensor(ish, device='cuda'))
+    o = bn_fwd_call(x16, wt, dims, gamma, beta, mm, mv, coef, nrb)
+    fails = list(o['fails'])
+    src16 = x16
+    if fold:
+        src16 = _bn_apply_ref(x16, isc, ish, M, cin)
+        if not torch.equal(o['y16'], src16):
+            fails.append('exact: y_side differs from fte_bn_apply, ' + _where2((o['y16'] != src16).cpu().numpy(), cin))
+    want = _dev16(_host16(src16)[:, sel] * g)          # one input element times a power of two: exact, bf16-exact
+    bad = (o['z16'] != want).cpu().numpy()
+    if bad.any():
+        fails.append('exact: z differs from the selected input, ' + _where2(bad, cout))
+    return o['symbols'], {'exact_wrong_elements': int(bad.sum())}, fails
+
+
+def bn_random(dims, fold, nrb=None, seed=32):
+    """the generator of tests/test_gpu_bn_fusion.py: z element by element against the float64 product (_stored_ok), the statistics against
+    float64 statistics of the STORED z with that module's limits.  -> (symbols, errors, fails)"""
+    n, h, w, cin, cout, ks, stride = dims
+    M = n * h * w
+    r = np.random.default_rng(seed)
+    wt = _bf64(r.standard_normal((ks, ks, cin, cout)) * 0.05)
+    gamma = 1 + 0.2 * r.standard_normal(cout); beta = 0.3 * r.standard_normal(cout)
+    mm = r.standard_normal(cout) * 0.1; mv = 1 + 0.1 * r.random(cout)
+    coef = None
+    if fold:
+        x = _bf64(r.standard_normal((M, cin)) * 1.5 + 0.3)
+        isc, ish = _fold_coef(r, cin)
+        coef = (torch.tensor(isc, device='cuda'), torch.tensor(ish, device='cuda'))
+    else:
+        x = _bf64(r.standard_normal((M, cin)) + 0.7)
+    x16 = _dev16(x)
+    o = bn_fwd_call(x16, wt, dims, gamma, beta, mm, mv, coef, nrb)
+    fails = list(o['fails'])
+    src = x
+    if fold:
+        y_ref = _bn_apply_ref(x16, isc, ish, M, cin)
+        if not torch.equal(o['y16'], y_ref):
+            fails.append('random: y_side differs from fte_bn_apply, ' + _where2((o['y16'] != y_ref).cpu().numpy(), cin))
+        src = _host16(y_ref)
+        y64 = _bf64(np.maximum(x * isc.astype(np.float64) + ish.astype(np.float64), 0))
+        e = float(np.sqrt(((src - y64) ** 2).sum() / (y64 ** 2).sum()))
+        if e > 2e-3:
+            fails.append('random: y vs the oracle rel-L2 %.3e > 2e-3' % e)
+    if ks == 1:
+        z_ref = src @ wt.reshape(cin, cout)
+    else:
+        z_ref = ops.conv2d_fwd(src.reshape(n, h, w, cin), wt, 1).reshape(M, cout)
+    worst, ok = _stored_ok(o['z16'], z_ref, np.abs(z_ref).max())
+    errs = {'z_worst_over_limit': worst}
+    if not ok:
+        fails.append('random: z beyond 2^-8 |ref| + 2e-5 max|ref| (worst / limit = %.3f)' % worst)
+    ref = stats64(_host16(o['z16']), gamma, beta, mm, mv)
+    for k, lim in BN_LIMITS.items():
+        e = float(np.abs(o['stats'][k] - ref[k]).max() / max(np.abs(ref[k]).max(), 1e-30))
+        errs[k + '_maxabs_rel'] = e
+        if not e <= lim:
+            fails.append('random: %s of the stored z off by %.3e > %.1e (relative to the largest)' % (k, e, lim))
+    return o['symbols'], errs, fails
+
+
+def _run_bn1(n, h, w, cin, cout, stride, r, fold):
+    """worker form of the two checks for a hooked 1x1 case: the partial-row count from tests/pw16_map.py under THIS process's hooks"""
+    import pw16_cases
+    import pw16_map
+    dims = (n, h, w, cin, cout, 1, stride)
+    p = pw16_map.plan(n * h * w, cin, cout, **pw16_cases.hooks(os.environ))
+    nrb = p['nrb'] if p else None
+    s1, e1, f1 = bn_exact(dims, fold, nrb)
+    s2, e2, f2 = bn_random(dims, fold, nrb)
+    errs = dict(e1, **e2)
+    errs['fails'] = f1 + f2
+    errs['symbols_per_call'] = [s1, s2]
+    return sorted(set(s1 + s2)), [], errs, not (f1 + f2)
+
+
 def main():
     cases = json.loads(sys.argv[1])
     out, ok_all = [], True
@@ -251,7 +468,8 @@ def main():
         r = np.random.default_rng(100 + ci)
         syms, splits, errs, ok = {'fwd': run_fwd, 'dgrad': run_dgrad, 'wgrad': run_wgrad, 's16fwd': run_s16fwd, 's16dgrad': run_s16dgrad,
                                   's16fwd1': lambda *a: run_s16fwd(*a, k=1), 's16dgrad1': lambda *a: run_s16dgrad(*a, k=1),
-                                  's16wgrad': run_s16wgrad, 's16wgrad1': run_s16wgrad1}[op](*dims, r)
+                                  's16wgrad': run_s16wgrad, 's16wgrad1': run_s16wgrad1,
+                                  'bnfwd1': lambda *a: _run_bn1(*a, fold=False), 'bnfold1': lambda *a: _run_bn1(*a, fold=True)}[op](*dims, r)
         out.append({'case': c, 'symbols': syms, 'splits': splits, 'errors': errs, 'ok': bool(ok)})
         ok_all = ok_all and ok
         torch.cuda.empty_cache()
