@@ -305,6 +305,32 @@ int fte_bn_prelu_infer_fwd(const float* z, const float* gamma, const float* beta
 int fte_bn_prelu_train_bwd(const float* dy, const float* z, const float* gamma, const float* mean, const float* rstd,
                            const float* scale, const float* shift, const float* alpha, float* dz, float* dgamma, float* dbeta,
                            float* dalpha, long rows, int c, void* ws, size_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------------------
+ * BN + SE + shortcut, no activation: the tail of an SE-IResNet block (nets/iresnet.py with se=True),
+ *   z -> u = BN(z) -> out = u * gate(mean_hw u) + shortcut.
+ * fp32 tensors only: z / shortcut / out / dy are [n, hw, c], c % 4 == 0, c >= 4; sq / xm / gate / s1 / s2 / dgate are [n, c].  scale /
+ * shift / mean / rstd are the BN layer's (fte_bn_train_stats, fte_conv2d_bn_fwd or fte_bn_infer_coef); u = fma(z, scale[c], shift[c]) as
+ * fte_bn_apply evaluates it, xhat = (z - mean) * rstd.
+ *   fte_se_lin_squeeze    sq = scale * mean_hw(z) + shift; xm (optional) = (mean_hw(z) - mean) * rstd: the values of fte_se_squeeze.
+ *   fte_se_lin_apply_fwd  out = u * gate[n, c] + shortcut, no clamp.  Product and sum are rounded on their own: gate = 1 gives the
+ *                         bytes of fte_bn_apply(res = shortcut, relu = 0).
+ *   fte_se_lin_bwd_sums   s1 = sum_hw dy, s2 = sum_hw dy * xhat, dgate = (gamma * s2 + beta * s1) * gate * (1 - gate) (the gradient of
+ *                         the gate's pre-sigmoid).  Reads dy and z only: no output tensor is read, no masked gradient is written.
+ * The rest of the backward is fte_se_bn_bwd_coef and fte_se_bn_bwd_apply with g = dy and flags = 0; dy itself is the shortcut's gradient.
+ * The two reductions split the pixels of an image over S blocks when ceil(c / 64) * n blocks cannot give every compute unit of the
+ * device one (S from the device's CU count, at most 64); the partial sums go to ws and are added in split order by a small second
+ * launch.  S = 1 writes the results from the one launch.  Sums are fp32 and merged in a fixed order without float atomics: two calls
+ * write identical bytes.  ws >= fte_se_lin_ws_bytes(n, hw, c) (0 for a shape the entry points refuse).
+ * FTE_EINVAL: a null pointer (xm excepted; mean / rstd may be NULL without xm), n < 1, hw < 1, c < 4 or c % 4, ws NULL or shorter than
+ * fte_se_lin_ws_bytes(n, hw, c), n > 65535 or hw * c >= 2^32.  Nothing is launched then.
+ * ------------------------------------------------------------------------- */
+size_t fte_se_lin_ws_bytes(int n, int hw, int c);
+int fte_se_lin_squeeze(const float* z, const float* scale, const float* shift, const float* mean, const float* rstd, float* sq, float* xm,
+                       int n, int hw, int c, void* ws, size_t ws_bytes, void* stream);
+int fte_se_lin_apply_fwd(const float* z, const float* scale, const float* shift, const float* gate, const float* shortcut, float* out,
+                         int n, int hw, int c, void* stream);
+int fte_se_lin_bwd_sums(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                        const float* gate, float* s1, float* s2, float* dgate, int n, int hw, int c, void* ws, size_t ws_bytes, void* stream);
 /* g = dy * (y > 0)  (tf.nn.relu gradient, materialised where a residual shortcut needs it) */
 int fte_relu_bwd(const float* dy, const float* y, float* g, long n, void* stream);
 

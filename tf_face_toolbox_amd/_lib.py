@@ -51,6 +51,10 @@ _SIGS = {
     'fte_bn_prelu_apply': (c_int, [_P] * 5 + [c_long, c_int, _P]),
     'fte_bn_prelu_infer_fwd': (c_int, [_P] * 9 + [c_long, c_int, c_float, _P]),
     'fte_bn_prelu_train_bwd': (c_int, [_P] * 12 + [c_long, c_int, _P, c_size_t, _P]),
+    'fte_se_lin_ws_bytes': (c_size_t, [c_int] * 3),
+    'fte_se_lin_squeeze': (c_int, [_P] * 7 + [c_int] * 3 + [_P, c_size_t, _P]),
+    'fte_se_lin_apply_fwd': (c_int, [_P] * 6 + [c_int] * 3 + [_P]),
+    'fte_se_lin_bwd_sums': (c_int, [_P] * 10 + [c_int] * 3 + [_P, c_size_t, _P]),
     'fte_relu_bwd': (c_int, [_P] * 3 + [c_long, _P]),
     'fte_maxpool3x3s2_fwd': (c_int, [_P] * 3 + [c_int] * 4 + [_P]),
     'fte_maxpool3x3s2_bwd': (c_int, [_P] * 3 + [c_int] * 4 + [_P]),

@@ -1407,6 +1407,26 @@ int fte_bn_prelu_train_bwd(const float* dy, const float* z, const float* gamma, 
     if (!ws || ws_bytes < fte_bn_prelu_ws_bytes(c)) return FTE_EINVAL;      // (fte.h: one refusal code for this block)
     return rc(l_bn_prelu_bwd(dy, z, gamma, mean, rstd, scale, shift, alpha, dz, dgamma, dbeta, dalpha, rows, c, (float*)ws, (hipStream_t)stream));
 }
+// BN + SE + shortcut, no activation (iresnet.hip)
+static bool se_lin_args_ok(int n, int hw, int c) { return n >= 1 && hw >= 1 && c >= 4 && c % 4 == 0; }
+size_t fte_se_lin_ws_bytes(int n, int hw, int c) { return se_lin_args_ok(n, hw, c) ? l_se_lin_ws_floats(n, hw, c) * sizeof(float) : 0; }
+int fte_se_lin_squeeze(const float* z, const float* scale, const float* shift, const float* mean, const float* rstd, float* sq, float* xm,
+                       int n, int hw, int c, void* ws, size_t ws_bytes, void* stream) {
+    if (!z || !scale || !shift || !sq || (xm && (!mean || !rstd)) || !se_lin_args_ok(n, hw, c)) return FTE_EINVAL;
+    if (!ws || ws_bytes < fte_se_lin_ws_bytes(n, hw, c)) return FTE_EINVAL;      // (fte.h: one refusal code for this block)
+    return rc(l_se_lin_squeeze(z, scale, shift, mean, rstd, sq, xm, n, hw, c, (float*)ws, (hipStream_t)stream));
+}
+int fte_se_lin_apply_fwd(const float* z, const float* scale, const float* shift, const float* gate, const float* shortcut, float* out,
+                         int n, int hw, int c, void* stream) {
+    if (!z || !scale || !shift || !gate || !shortcut || !out || !se_lin_args_ok(n, hw, c)) return FTE_EINVAL;
+    return rc(l_se_lin_apply(z, scale, shift, gate, shortcut, out, n, hw, c, (hipStream_t)stream));
+}
+int fte_se_lin_bwd_sums(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                        const float* gate, float* s1, float* s2, float* dgate, int n, int hw, int c, void* ws, size_t ws_bytes, void* stream) {
+    if (!dy || !z || !gamma || !beta || !mean || !rstd || !gate || !s1 || !s2 || !dgate || !se_lin_args_ok(n, hw, c)) return FTE_EINVAL;
+    if (!ws || ws_bytes < fte_se_lin_ws_bytes(n, hw, c)) return FTE_EINVAL;
+    return rc(l_se_lin_bwd_sums(dy, z, gamma, beta, mean, rstd, gate, s1, s2, dgate, n, hw, c, (float*)ws, (hipStream_t)stream));
+}
 int fte_relu_bwd(const float* dy, const float* y, float* g, long n, void* stream) {
     if (!dy || !y || !g || n <= 0 || n % 4) return FTE_EINVAL;
     return rc(l_relu_bwd(dy, y, g, n, (hipStream_t)stream));

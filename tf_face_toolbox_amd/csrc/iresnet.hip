@@ -13,7 +13,10 @@
 #include <stdlib.h>
 
 #include "iresnet.h"
+#include "igemm.h"
 #include "layers.h"
+
+#define SE_LIN_MAX_SPLITS 64
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -220,6 +223,184 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_apply_kernel(const float* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// BN + SE + shortcut, no activation (the SE-IResNet block tail: z -> u = BN(z) -> u * gate(mean_hw u) + shortcut; fte.h).  The SE
+// kernels of layers.hip give one block a whole image of 64 channels: at 128 x 56^2 x 64 that is 128 blocks.  Here the pixels of an
+// image are split over S blocks when the unsplit grid cannot fill the device (se_lin_split); the partial sums of a split go to the
+// workspace as part[split][sum][n][c] and a small launch adds them in split order.  S == 1 writes the results from the one kernel.
+// Block = Q channel quads x 256 / Q pixel lanes (Q = 16; 8 below 32 channels, with idle lanes where c / 4 is no multiple of Q), four
+// pixels in flight per lane, lanes of a wave by wave_rows_sum, the four waves in LDS in index order.
+// ---------------------------------------------------------------------------------------------------
+// NS sums per (image, channel) over the pixels [blockIdx.y * pps, ...) of image blockIdx.z: `load` walks a lane's pixels into acc[NS],
+// `finish` takes the block's sums of one channel quad
+template <int Q, int NS, class Load, class Finish>
+__device__ __forceinline__ void se_lin_block_sums(int hw, int c, int pps, Load load, Finish finish) {
+    constexpr int RL = 256 / Q;
+    __shared__ f32x4 sh[NS][4][Q];
+    const int q = threadIdx.x % Q, rl = threadIdx.x / Q;
+    const int ch = (blockIdx.x * Q + q) * 4;
+    const int r0 = blockIdx.y * pps, r1 = min(hw, r0 + pps);
+    f32x4 acc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool ok = ch < c;
+    if (ok) load(ch, (long)blockIdx.z * hw * c + ch, r0 + rl, r1, RL, acc);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = wave_rows_sum<Q>(acc[k]);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) < Q) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sh[k][wave][q] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < Q && ok) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            acc[k] = sh[k][0][q];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) acc[k] += sh[k][w][q];
+        }
+        finish(ch, acc);
+    }
+}
+
+// sq = scale * mean_hw(z) + shift, xm = (mean_hw(z) - mean) * rstd from the pixel sum of one image and channel quad
+__device__ __forceinline__ void se_lin_squeeze_finish(const f32x4 s, int hw, long o, int ch, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, const float* __restrict__ mean,
+                                                      const float* __restrict__ rstd, float* __restrict__ sq, float* __restrict__ xm) {
+    const f32x4 zm = s / (float)hw;
+    stq4(sq, o, affine4(zm, ldq4(scale, ch), ldq4(shift, ch)));
+    if (xm) stq4(xm, o, (zm - ldq4(mean, ch)) * ldq4(rstd, ch));
+}
+// s1, s2 -> dgate = (gamma * s2 + beta * s1) * gate * (1 - gate)      (sum_hw dy * u with u = gamma * xhat + beta)
+__device__ __forceinline__ void se_lin_sums_finish(const f32x4 t1, const f32x4 t2, long o, int ch, const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta, const float* __restrict__ gate,
+                                                   float* __restrict__ s1, float* __restrict__ s2, float* __restrict__ dgate) {
+    stq4(s1, o, t1);
+    stq4(s2, o, t2);
+    const f32x4 gt = ldq4(gate, o);
+    const f32x4 gy = ldq4(gamma, ch) * t2 + ldq4(beta, ch) * t1;
+    stq4(dgate, o, gy * gt * (1.f - gt));
+}
+
+// grid = (channel blocks, S, n).  part == nullptr (S == 1): sq / xm written here; else part[split][n][c]
+template <int Q>
+__global__ __launch_bounds__(256) void se_lin_squeeze_kernel(const float* __restrict__ z, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, const float* __restrict__ mean,
+                                                             const float* __restrict__ rstd, float* __restrict__ sq,
+                                                             float* __restrict__ xm, float* __restrict__ part, int hw, int c, int pps) {
+    const long img_c = (long)blockIdx.z * c, slab = (long)gridDim.z * c;
+    se_lin_block_sums<Q, 1>(hw, c, pps,
+        [&](int, long px, int r, int r1, int RL, f32x4* acc) {
+            f32x4 s0 = acc[0], s1 = acc[0];
+            for (; r + 3 * RL < r1; r += 4 * RL) {
+                f32x4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = ldq4(z, px + (long)(r + u * RL) * c);
+                s0 += v[0] + v[2]; s1 += v[1] + v[3];
+            }
+            for (; r < r1; r += RL) s0 += ldq4(z, px + (long)r * c);
+            acc[0] = s0 + s1;
+        },
+        [&](int ch, const f32x4* acc) {
+            if (part) stq4(part, blockIdx.y * slab + img_c + ch, acc[0]);
+            else se_lin_squeeze_finish(acc[0], hw, img_c + ch, ch, scale, shift, mean, rstd, sq, xm);
+        });
+}
+// one thread per (image, channel quad): the splits in index order, then the direct kernel's last step
+__global__ __launch_bounds__(256) void se_lin_squeeze_merge_kernel(const float* __restrict__ part, int splits, const float* __restrict__ scale,
+                                                                   const float* __restrict__ shift, const float* __restrict__ mean,
+                                                                   const float* __restrict__ rstd, float* __restrict__ sq,
+                                                                   float* __restrict__ xm, int n, int hw, int c) {
+    const int cq = c >> 2;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)n * cq) return;
+    const long o = i * 4, slab = (long)n * c;
+    f32x4 s = ldq4(part, o);
+    for (int k = 1; k < splits; ++k) s += ldq4(part, k * slab + o);
+    se_lin_squeeze_finish(s, hw, o, (int)(i % cq) * 4, scale, shift, mean, rstd, sq, xm);
+}
+
+// s1 = sum_hw dy, s2 = sum_hw dy * xhat.  part == nullptr (S == 1): s1 / s2 / dgate written here; else part[split][2][n][c]
+template <int Q>
+__global__ __launch_bounds__(256) void se_lin_bwd_sums_kernel(const float* __restrict__ dy, const float* __restrict__ z,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                              const float* __restrict__ gate, float* __restrict__ s1,
+                                                              float* __restrict__ s2, float* __restrict__ dgate, float* __restrict__ part,
+                                                              int hw, int c, int pps) {
+    const long img_c = (long)blockIdx.z * c, slab = (long)gridDim.z * c;
+    se_lin_block_sums<Q, 2>(hw, c, pps,
+        [&](int ch, long px, int r, int r1, int RL, f32x4* acc) {
+            const f32x4 mu = ldq4(mean, ch), rs = ldq4(rstd, ch);
+            f32x4 a = acc[0], b = acc[1];
+            for (; r + 3 * RL < r1; r += 4 * RL) {
+                f32x4 d4[4], z4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    d4[u] = ldq4(dy, px + (long)(r + u * RL) * c);
+                    z4[u] = ldq4(z, px + (long)(r + u * RL) * c);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { a += d4[u]; b += d4[u] * ((z4[u] - mu) * rs); }
+            }
+            for (; r < r1; r += RL) {
+                const f32x4 d = ldq4(dy, px + (long)r * c);
+                a += d; b += d * ((ldq4(z, px + (long)r * c) - mu) * rs);
+            }
+            acc[0] = a; acc[1] = b;
+        },
+        [&](int ch, const f32x4* acc) {
+            if (part) {
+                float* pp = part + (long)blockIdx.y * 2 * slab + img_c + ch;
+                stq4(pp, 0, acc[0]); stq4(pp, slab, acc[1]);
+            } else {
+                se_lin_sums_finish(acc[0], acc[1], img_c + ch, ch, gamma, beta, gate, s1, s2, dgate);
+            }
+        });
+}
+__global__ __launch_bounds__(256) void se_lin_bwd_sums_merge_kernel(const float* __restrict__ part, int splits, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, const float* __restrict__ gate,
+                                                                    float* __restrict__ s1, float* __restrict__ s2, float* __restrict__ dgate,
+                                                                    int n, int c) {
+    const int cq = c >> 2;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)n * cq) return;
+    const long o = i * 4, slab = (long)n * c;
+    f32x4 t1 = ldq4(part, o), t2 = ldq4(part, slab + o);
+    for (int k = 1; k < splits; ++k) { t1 += ldq4(part, 2 * k * slab + o); t2 += ldq4(part, (2 * k + 1) * slab + o); }
+    se_lin_sums_finish(t1, t2, o, (int)(i % cq) * 4, gamma, beta, gate, s1, s2, dgate);
+}
+
+// out = u * gate[n, c] + shortcut, u = fma(z, scale, shift); product and sum rounded on their own, so gate = 1 gives the bytes of
+// fte_bn_apply(res = shortcut, relu = 0).  grid = (blocks over one image's hw * c / 4 quads, image), the stride a multiple of c / 4
+// (se_lin_apply_grid): a thread keeps its channel quad -- the walk of se_apply_kernel (layers.hip)
+__global__ __launch_bounds__(256) void se_lin_apply_kernel(const float* __restrict__ z, const float* __restrict__ scale,
+                                                           const float* __restrict__ shift, const float* __restrict__ gate,
+                                                           const float* __restrict__ res, float* __restrict__ out, int hwq, int cq) {
+    const int step = (int)gridDim.x * 256;
+    const long base = (long)blockIdx.y * hwq;
+    int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= hwq) return;
+    const int cqi = i % cq;
+    const f32x4 g = ldq4(gate, ((long)blockIdx.y * cq + cqi) * 4);
+    const f32x4 sc = ldq4(scale, cqi * 4), sf = ldq4(shift, cqi * 4);
+    auto f = [&](const f32x4 zz, const f32x4 rr) {
+#pragma clang fp contract(off)
+        const f32x4 u = affine4(zz, sc, sf);
+        const f32x4 p = u * g;
+        return p + rr;
+    };
+    for (; i + 3 * step < hwq; i += 4 * step) {
+        f32x4 zv[4], rv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { zv[u] = ldq4(z, (base + i + u * step) * 4); rv[u] = ldq4(res, (base + i + u * step) * 4); }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) stq4(out, (base + i + u * step) * 4, f(zv[u], rv[u]));
+    }
+    for (; i < hwq; i += step) stq4(out, (base + i) * 4, f(ldq4(z, (base + i) * 4), ldq4(res, (base + i) * 4)));
+}
+
 // grid_for_c of layers.hip for fp32 tensors: the grid stride (blocks * 256 threads) is a multiple of C / 4, about two resident blocks
 // per CU once every thread has four pieces to walk (FTE_BN_APPLY_BLOCKS: the same tuning hook)
 inline int apply_grid(long n4, int C) {
@@ -251,6 +432,40 @@ inline void prelu_split(long rows, int C, int* splits, long* rps) {
     if (rs < 1) rs = 1;
     *rps = (rows + rs - 1) / rs;
     *splits = (int)((rows + *rps - 1) / *rps);
+}
+
+
+// chscale_grid of layers.hip: blocks.x a multiple of (c / 4) / gcd(c / 4, 256), four pieces per thread, about 1024 blocks in all
+inline dim3 se_lin_apply_grid(int n, int hw, int c) {
+    const long hwq = (long)hw * (c / 4), cq = c / 4;
+    long a = cq, b = 256;
+    while (b) { const long t = a % b; a = b; b = t; }
+    const long m = cq / a;
+    long gx = (hwq + 1023) / 1024;
+    const long want = (1024 + n - 1) / n;
+    if (gx > want) gx = want;
+    if (gx < 1) gx = 1;
+    gx = (gx + m - 1) / m * m;
+    return dim3((unsigned)gx, (unsigned)n);
+}
+
+inline int se_lin_quads(int c) { return c < 32 ? 8 : 16; }
+
+// Pixel splits of an image.  None when the unsplit grid (channel blocks x images) has a block for every CU (a quarter of the target
+// FTE_SE_LIN_BLOCKS, default 4 blocks per CU; 0: never split -- the A/B hook) or the image has fewer than 64 pixels; else enough
+// for the target, every pixel lane of a split with a pixel, at most SE_LIN_MAX_SPLITS.  -> S and the pixels per split; the last
+// split may be short.
+inline void se_lin_split(int n, int hw, int c, int* splits, int* pps) {
+    const int Q = se_lin_quads(c);
+    const long base = (long)((c / 4 + Q - 1) / Q) * n;
+    static const long env = getenv("FTE_SE_LIN_BLOCKS") ? atol(getenv("FTE_SE_LIN_BLOCKS")) : -1;
+    const long target = env >= 0 ? env : 4L * igemm_num_cus();
+    long s = (4 * base >= target || hw < 64) ? 1 : (target + base - 1) / base;
+    if (s > hw / (256 / Q)) s = hw / (256 / Q);
+    if (s > SE_LIN_MAX_SPLITS) s = SE_LIN_MAX_SPLITS;
+    if (s < 1) s = 1;
+    *pps = (int)((hw + s - 1) / s);
+    *splits = (hw + *pps - 1) / *pps;
 }
 
 }  // namespace
@@ -290,5 +505,59 @@ hipError_t l_bn_prelu_bwd(const float* dy, const float* z, const float* gamma, c
     if (e != hipSuccess) return e;
     const long n4 = rows * C / 4;
     hipLaunchKernelGGL(bn_prelu_bwd_apply_kernel, dim3(apply_grid(n4, C)), dim3(256), 0, st, dy, z, coef, scale, shift, alpha, dz, n4, C);
+    return hipGetLastError();
+}
+
+// ---- BN + SE + shortcut, no activation -------------------------------------------------------------
+size_t l_se_lin_ws_floats(int n, int hw, int c) {
+    int splits, pps;
+    se_lin_split(n, hw, c, &splits, &pps);
+    return (size_t)2 * splits * n * c;                     // (the squeeze uses half; S == 1 uses none of it)
+}
+
+static bool se_lin_shape_ok(int n, int hw, int c) {
+    return n >= 1 && hw >= 1 && c >= 4 && c % 4 == 0 && n <= 65535 && (long)hw * c / 4 < (1L << 30);
+}
+
+hipError_t l_se_lin_squeeze(const float* z, const float* scale, const float* shift, const float* mean, const float* rstd, float* sq,
+                            float* xm, int n, int hw, int c, float* ws, hipStream_t st) {
+    if (!se_lin_shape_ok(n, hw, c)) return hipErrorInvalidValue;
+    int splits, pps;
+    se_lin_split(n, hw, c, &splits, &pps);
+    float* part = splits > 1 ? ws : nullptr;
+    const int Q = se_lin_quads(c);
+    const dim3 grid((c / 4 + Q - 1) / Q, splits, n);
+    if (Q == 16) hipLaunchKernelGGL(se_lin_squeeze_kernel<16>, grid, dim3(256), 0, st, z, scale, shift, mean, rstd, sq, xm, part, hw, c, pps);
+    else hipLaunchKernelGGL(se_lin_squeeze_kernel<8>, grid, dim3(256), 0, st, z, scale, shift, mean, rstd, sq, xm, part, hw, c, pps);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || splits == 1) return e;
+    const long nq = (long)n * (c / 4);
+    hipLaunchKernelGGL(se_lin_squeeze_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, part, splits, scale, shift, mean, rstd,
+                       sq, xm, n, hw, c);
+    return hipGetLastError();
+}
+
+hipError_t l_se_lin_apply(const float* z, const float* scale, const float* shift, const float* gate, const float* shortcut, float* out,
+                          int n, int hw, int c, hipStream_t st) {
+    if (!se_lin_shape_ok(n, hw, c)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(se_lin_apply_kernel, se_lin_apply_grid(n, hw, c), dim3(256), 0, st, z, scale, shift, gate, shortcut, out, hw * (c / 4), c / 4);
+    return hipGetLastError();
+}
+
+hipError_t l_se_lin_bwd_sums(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                             const float* gate, float* s1, float* s2, float* dgate, int n, int hw, int c, float* ws, hipStream_t st) {
+    if (!se_lin_shape_ok(n, hw, c)) return hipErrorInvalidValue;
+    int splits, pps;
+    se_lin_split(n, hw, c, &splits, &pps);
+    float* part = splits > 1 ? ws : nullptr;
+    const int Q = se_lin_quads(c);
+    const dim3 grid((c / 4 + Q - 1) / Q, splits, n);
+    if (Q == 16) hipLaunchKernelGGL(se_lin_bwd_sums_kernel<16>, grid, dim3(256), 0, st, dy, z, gamma, beta, mean, rstd, gate, s1, s2, dgate, part, hw, c, pps);
+    else hipLaunchKernelGGL(se_lin_bwd_sums_kernel<8>, grid, dim3(256), 0, st, dy, z, gamma, beta, mean, rstd, gate, s1, s2, dgate, part, hw, c, pps);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || splits == 1) return e;
+    const long nq = (long)n * (c / 4);
+    hipLaunchKernelGGL(se_lin_bwd_sums_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, part, splits, gamma, beta, gate,
+                       s1, s2, dgate, n, c);
     return hipGetLastError();
 }

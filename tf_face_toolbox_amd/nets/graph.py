@@ -85,6 +85,7 @@ class GraphNet(Network):
     head = 'softmax'
     channel_pad = 1
     bn_eps, bn_decay = BN_EPS, BN_DECAY      # per net: IResNet sets 1e-5 / 0.9; they reach every BN call of the walk
+    se_hidden_pad = None                     # multiple the SE gates' dense layers are stored at (None: channel_pad); SE-IResNet: 64
 
     def _pc(self, c):
         p = self.channel_pad
@@ -150,7 +151,7 @@ class GraphNet(Network):
         self.spec = OrderedDict((n, (s, k)) for n, s, k in spec)
         # shapes, typed plan ops and fusion tables (nets/plan.py); the gather tables become device tensors here
         compiled = plan.compile_net(self.graph, self.spec, self.in_hwc, self.channel_pad, self.feature_name, self.opt,
-                                    self.num_classes, self.sub_centers * self.cpad, self.name)
+                                    self.num_classes, self.sub_centers * self.cpad, self.name, self.se_hidden_pad)
         for field, value in compiled._asdict().items():
             setattr(self, field, value)
         self.plan = [self._device_tables(op) if op[0] == 'gather' else op for op in compiled.plan]
@@ -196,6 +197,8 @@ class GraphNet(Network):
     def _internal_shape(self, shape, kind, name=None):
         """arena layout of a variable whose reference shape is `shape`"""
         pc = (lambda c: (c + 31) // 32 * 32) if name in self.narrow else self._pc
+        if self.se_hidden_pad and kind in ('fc_w', 'bias'):      # an SE gate's dense layers: zero rows / columns up to the GEMMs' granularity
+            pc = lambda c: (c + self.se_hidden_pad - 1) // self.se_hidden_pad * self.se_hidden_pad
         if kind == 'cls_w':
             assert pc(shape[0]) == shape[0]
             return (shape[0], self.sub_centers * self.cpad)
@@ -1113,6 +1116,52 @@ class GraphNet(Network):
         dz = torch.empty_like(T[zin])
         call('fte_se_bn_bwd_apply', g, T[zin], b['coef'], gate, dsq, dz, n, hw, c, fl, st)
         self._put(op.shortcut, g)
+        self._put(zin, dz)
+
+    def _alloc_selin(self, w, op):
+        assert not w.s16, 'selin: fp32 tensors only (the nets that plan it refuse bf16 storage)'
+        self._alloc_out(w, op, False)
+        self._alloc_bn(w, op, stored=False)
+        ih, iw, c = self.shapes[op.out]
+        for nm in ('xm', 's1', 's2'):                  # per-image sums of the backward pass, the squeeze in xhat units
+            self.t[op.out + '/' + nm] = self._f32(w.n, c)
+        self._alloc_se_gate(w, op.out, op.se, c)
+        w.need = max(w.need, _lib.query('fte_se_lin_ws_bytes', w.n, ih * iw, c))
+
+    def _fwd_selin(self, w, j, op):
+        """BN -> SE gate -> + shortcut, no activation: statistics, squeeze, the gate's dense layers, out = u * gate + shortcut"""
+        call, T, n, st = w.call, self.t, w.n, w.st
+        out, zin, scn, se = op.out, op.inp, op.shortcut, op.se
+        ih, iw, c = self.shapes[out]
+        hw = ih * iw
+        b = self.bn[out]
+        if j not in w.stats_done:                      # (else the producing conv's epilogue left the batch statistics)
+            self._bn_stats(w, op, T[zin], False)
+        sq, _, gate = self._se_buffers(out)
+        call('fte_se_lin_squeeze', T[zin], b['scale'], b['shift'], b['mean'], b['rstd'], sq, T[out + '/xm'] if w.is_training else None,
+             n, hw, c, w.ws, self.ws_bytes, st)
+        self._se_gate_fwd(w, out, se, c, 'small' if self._se_small(c, se.hidden) else 'act')
+        self._wait_shortcut(w, scn)
+        call('fte_se_lin_apply_fwd', T[zin], b['scale'], b['shift'], gate, T[scn], T[out], n, hw, c, st)
+
+    def _bwd_selin(self, w, op, dy):
+        """dy is the gated tensor's gradient AND the shortcut's (passed on uncopied, as the activation-free bn op does)"""
+        call, T, n, st = w.call, self.t, w.n, w.st
+        out, zin, pre, se = op.out, op.inp, op.pre, op.se
+        ih, iw, c = self.shapes[out]
+        hw = ih * iw
+        b = self.bn[out]
+        gate = T[out + '/gate']
+        s1, s2, xm = T[out + '/s1'], T[out + '/s2'], T[out + '/xm']
+        gam, bet = self.view(pre + '/gamma'), self.view(pre + '/beta')
+        call('fte_se_lin_bwd_sums', dy, T[zin], gam, bet, b['mean'], b['rstd'], gate, s1, s2, self.ident[('se', out, 'dgate')], n, hw, c,
+             self.ws, self.ws_bytes, st)
+        dsq = self._se_gate_bwd(w, out, se, c, self._se_small(c, se.hidden))
+        call('fte_se_bn_bwd_coef', s1, s2, gate, dsq, xm, gam, b['mean'], b['rstd'], self.view(pre + '/gamma', self.grads),
+             self.view(pre + '/beta', self.grads), b['coef'], n, hw, c, st)
+        dz = torch.empty_like(T[zin])
+        call('fte_se_bn_bwd_apply', dy, T[zin], b['coef'], gate, dsq, dz, n, hw, c, 0, st)
+        self._add(op.shortcut, dy)
         self._put(zin, dz)
 
     def _alloc_se(self, w, op):

@@ -9,13 +9,20 @@ the net the margin-head papers (ArcFace, sub-center ArcFace, Partial FC, AdaFace
 
 Variable names follow the ResNet scheme: `IResNet-50/stage2/block_0/conv1_3x3/weights`, `.../BatchNorm/{gamma,beta,moving_mean,
 moving_variance}`, `.../prelu/alpha`, `classifier/fc_classifier/weights`.  BN + PReLU pairs run fused (csrc/iresnet.hip); batch norm uses
-epsilon 1e-5 and momentum 0.9, the published code's values.  Differences from that code are listed in DESIGN.md section 8."""
+epsilon 1e-5 and momentum 0.9, the published code's values.  Differences from that code are listed in DESIGN.md section 8.
+
+se=True gives SE-IResNet ("IR-SE"): the block's last BN is followed by a squeeze-and-excitation gate before the shortcut is added,
+  gate = sigmoid(fc2(relu(fc1(mean_hw(BN output))))), fc1 [c, c / 16] + bias, fc2 [c / 16, c] + bias, variables `.../se/fc1/weights`,
+  `.../se/fc1/biases`, `.../se/fc2/...` as nets/resnet.py names them.  BN -> gate -> + shortcut runs as one plan op ('selin', fte.h
+  "BN + SE + shortcut, no activation").  The gate's dense layers are stored 64 hidden units wide (zero columns / rows, which stay
+  zero): the granularity of the GEMM entry points."""
 from .. import _lib
 from .graph import GraphNet
 
 BLOCKS = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 14, 3], 100: [3, 13, 30, 3]}
 WIDTHS = [64, 128, 256, 512]
 EMBED = 512
+SE_REDUCTION = 16
 
 
 def _refuse_bf16s(name):
@@ -28,13 +35,16 @@ class IResNet(GraphNet):
     bn_eps, bn_decay = 1e-5, 0.9
 
     def __init__(self, num_layers, weight_decay=0.0005, data_format='NCHW', name='IResNet', seed=0, head='softmax',
-                 scale=None, margin=None, margin_cos=None, blocks=None):
+                 scale=None, margin=None, margin_cos=None, blocks=None, se=False):
         if num_layers not in BLOCKS:
             raise ValueError('Unsupported num_layers.')
         self.num_layers = num_layers
         self.num_block = list(BLOCKS[num_layers] if blocks is None else blocks)          # blocks=: test-only override of the block counts
         assert len(self.num_block) == 4 and all(b >= 1 for b in self.num_block), self.num_block
-        super(IResNet, self).__init__(weight_decay, data_format, name + '-' + str(num_layers), seed)
+        self.se = bool(se)
+        if self.se:
+            self.se_hidden_pad = 64
+        super(IResNet, self).__init__(weight_decay, data_format, ('SE-' if self.se else '') + name + '-' + str(num_layers), seed)
         _refuse_bf16s(self.name)
         self.feature_name = 'features'
         self._set_head(head, scale, margin, margin_cos)
@@ -95,7 +105,14 @@ class IResNet(GraphNet):
         self._prelu(g, spec, scope + '/conv1_3x3', t + '/c1', t + '/c1/bn', cout)
         self._conv(g, spec, scope + '/conv2_3x3', t + '/c2/z', t + '/c1', 3, cout, cout, stride)
         self._bn(g, spec, scope + '/conv2_3x3', t + '/c2/bn', t + '/c2/z', cout)
-        g.append(('add', t, t + '/c2/bn', shortcut))
+        last = t + '/c2/bn'
+        if self.se:
+            pre, hid = scope + '/se', cout // SE_REDUCTION
+            spec.extend([(pre + '/fc1/weights', (cout, hid), 'fc_w'), (pre + '/fc1/biases', (hid,), 'bias'),
+                         (pre + '/fc2/weights', (hid, cout), 'fc_w'), (pre + '/fc2/biases', (cout,), 'bias')])
+            g.append(('se', t + '/se', last, pre))
+            last = t + '/se'
+        g.append(('add', t, last, shortcut))
         return t
 
     def build_graph(self, in_ch, num_classes):

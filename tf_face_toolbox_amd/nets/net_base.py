@@ -53,6 +53,7 @@ def adaface_state(device):
 
 
 IRESNET_NAMES = tuple('IResNet-%d%s' % (d, h) for d in (18, 34, 50, 100) for h in ('', '-arcface', '-cosface', '-adaface'))
+SE_IRESNET_NAMES = tuple('SE-' + n for n in IRESNET_NAMES)      # "IR-SE": an SE gate behind every block's last BN
 SUB_CENTER_NETS = ('SphereNet-ArcFace', 'SphereNet-CosFace', 'ResNet-50-arcface', 'ResNet-50-cosface')
 
 
@@ -92,11 +93,12 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4, sub_centers=1):
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay, head=name.split('-')[2])
         network.set_sub_centers(sub_centers)
-    elif name in IRESNET_NAMES:                  # the ArcFace papers' backbone (nets/iresnet.py): IResNet-<depth>[-<margin head>]
+    elif name in IRESNET_NAMES + SE_IRESNET_NAMES:      # the ArcFace papers' backbone (nets/iresnet.py): [SE-]IResNet-<depth>[-<margin head>]
         from .iresnet import IResNet
-        parts = name.split('-')
+        se = name.startswith('SE-')
+        parts = name[3 if se else 0:].split('-')
         network = IResNet(num_layers=int(parts[1]), data_format=data_format, weight_decay=weight_decay,
-                          head=parts[2] if len(parts) > 2 else 'softmax')
+                          head=parts[2] if len(parts) > 2 else 'softmax', se=se)
     elif name == 'ResNet-26':                    # not a reference factory name; the class accepts 26 (nets/resnet.py:39-40)
         from .resnet import ResNet
         network = ResNet(num_layers=26, data_format=data_format, weight_decay=weight_decay)

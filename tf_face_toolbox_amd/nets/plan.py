@@ -17,7 +17,7 @@ Options = namedtuple('Options', [
     'bn_fuse_gbwd',     # FTE_BN_FUSE_GBWD (0, opt-in): a grouped conv's data gradient does
     'bn_fold',          # FTE_BN_FOLD (1): the normalise pass of a BN + ReLU moves into its consumer's operand loader
     'bn_gather',        # FTE_BN_GATHER (1): a BN whose only consumer is a channel gather is applied inside the gather
-    'se_fuse',          # FTE_SE_FUSE (1): BN -> SE gate -> add -> ReLU as one plan op ('seblock')
+    'se_fuse',          # FTE_SE_FUSE (1): BN -> SE gate -> add -> ReLU as one plan op ('seblock'); 'selin' (no ReLU) has no other form
     'se_act_fuse',      # FTE_SE_ACT_FUSE (1): the unfused SE gate's dense layers carry their activation
     'se_dense',         # FTE_SE_DENSE (1): the fused SE block's dense layers through fte_dense_small where it applies
     'direct_stem',      # FTE_DIRECT_STEM (1): a 3x3 stem of <= 32 filters is stored 32 wide and runs on the direct kernel
@@ -58,7 +58,10 @@ BnPrelu = namedtuple('BnPrelu', 'kind out inp pre alpha')
 # w1 .. hidden: weight / bias names of the gate's two dense layers and the (padded) hidden width
 Se = namedtuple('Se', 'kind out inp pre scope1 scope2 w1 b1 w2 b2 hidden')
 SeBlock = namedtuple('SeBlock', 'kind out inp pre shortcut se y s')    # se: the Se it absorbed; y, s: the BN output / gated tensor that no longer exist
+# BN -> SE gate -> add shortcut with NO activation (the SE-IResNet block tail): the fields of SeBlock, kernels of their own
+SeLin = namedtuple('SeLin', SeBlock._fields)
 AddRelu = namedtuple('AddRelu', 'kind out a b')
+Add = namedtuple('Add', 'kind out a b')                                # a bare add behind an SE gate: exists only until _fuse_se_lin has run
 # ins: (a, b | None); outs / bwd: [(tensor, table)], table = int32 words (src << 16 | channel, -1: none); gouts: (out0, out1 | None)
 Gather = namedtuple('Gather', 'kind out ins outs gouts bwd')
 MaxPool = namedtuple('MaxPool', 'kind out inp')
@@ -67,7 +70,7 @@ Dropout = namedtuple('Dropout', 'kind out inp keep')
 Fc = namedtuple('Fc', 'kind out inp wname bias embed')                # embed: a dense layer of the body (on a flattened map), not the classifier
 
 RECORDS = {'conv': Conv, 'gconv': GConv, 'dwconv': DwConv, 'bn': Bn, 'bnstats': Bn, 'bnprelu': BnPrelu, 'seblock': SeBlock, 'se': Se,
-           'addrelu': AddRelu, 'gather': Gather, 'maxpool': MaxPool, 'gap': Gap, 'dropout': Dropout, 'fc': Fc}
+           'selin': SeLin, 'addrelu': AddRelu, 'gather': Gather, 'maxpool': MaxPool, 'gap': Gap, 'dropout': Dropout, 'fc': Fc}
 
 Plan = namedtuple('Plan', 'plan shapes real_c narrow embed_in folded se_fused fuse_fwd fuse_bwd fold_apply shortcut_fwd shortcut_shared '
                           'has_classifier')
@@ -269,9 +272,9 @@ def plan_inputs(op):
         return [x for x in op.ins if x is not None]
     if kind == 'bn':
         return [op.inp] + ([op.res] if op.res is not None else [])
-    if kind == 'addrelu':
+    if kind in ('addrelu', 'add'):
         return [op.a, op.b]
-    if kind == 'seblock':
+    if kind in ('seblock', 'selin'):
         return [op.inp, op.shortcut]
     return [op.inp] if kind in RECORDS else graph_inputs(op)
 
@@ -281,8 +284,8 @@ def op_weight_names(op):
     kind = op[0]
     if kind in ('conv', 'gconv', 'dwconv') or (kind == 'fc' and op.embed):
         return [op.wname]
-    if kind in ('se', 'seblock'):
-        se = op.se if kind == 'seblock' else op
+    if kind in ('se', 'seblock', 'selin'):
+        se = op.se if kind != 'se' else op
         return [se.w1, se.w2]
     return []
 
@@ -306,7 +309,7 @@ def _defined_before(graph, name, idx):
 
 
 def _se_record(op, spec, channel_pad):
-    """('se', out, inp, prefix[, scope1, scope2]) -> Se with the names of the two FCs and the hidden width resolved"""
+    """('se', out, inp, prefix[, scope1, scope2]) -> Se with the names of the two FCs and the (stored) hidden width resolved"""
     _, out, inp, pre = op[:4]
     s1, s2 = (op[4], op[5]) if len(op) > 4 else ('fc1', 'fc2')
     w1 = pre + '/%s/weights' % s1
@@ -314,7 +317,7 @@ def _se_record(op, spec, channel_pad):
               _pad(spec[w1][0][-1], channel_pad))
 
 
-def _fuse_graph(graph, spec, shapes, real_c, channel_pad, name):
+def _fuse_graph(graph, spec, shapes, real_c, channel_pad, name, hidden_pad=None):
     """Graph ops -> plan ops: bn -> relu, bn -> add -> relu and bn -> prelu become one BN op each, add -> relu one 'addrelu', the
     channel splits / shuffles one 'gather' with its tables; everything else is typed as it stands."""
     g = graph
@@ -355,13 +358,16 @@ def _fuse_graph(graph, spec, shapes, real_c, channel_pad, name):
         elif kind == 'add':
             _, out, a, b = op
             u = users.get(out, [])
+            if not any(g[k][0] == 'relu' for k in u) and any(o[0] == 'se' and o[1] in (a, b) for o in g[:i]):
+                plan.append(Add('add', out, a, b))           # SE gate -> add, no activation: _fuse_se_lin takes it (or compile_net raises)
+                continue
             assert len(u) == 1 and g[u[0]][0] == 'relu', 'a bare add is always followed by a ReLU in these nets'
             skip.add(u[0])
             plan.append(AddRelu('addrelu', g[u[0]][1], a, b))
         elif kind in ('split', 'shufsplit', 'shufcat'):
             plan.append(gather_tables(op, shapes, real_c))
         elif kind == 'se':
-            plan.append(_se_record(op, spec, channel_pad))
+            plan.append(_se_record(op, spec, channel_pad if hidden_pad is None else hidden_pad))
         elif kind == 'fc':
             plan.append(Fc(*op, embed=spec[op[3]][1] == 'embed_w'))
         elif kind in RECORDS:
@@ -371,9 +377,10 @@ def _fuse_graph(graph, spec, shapes, real_c, channel_pad, name):
     return plan
 
 
-def _fuse_se_blocks(plan, shapes, feature_name, se_fused):
+def _fuse_se_blocks(plan, shapes, feature_name, se_fused, tail='addrelu', record=SeBlock):
     """('bn', y, z, pre, None, 0) -> ('se', s, y, ...) -> ('addrelu', out, s, shortcut), each the only user of its input, becomes
-    ('seblock', out, z, pre, shortcut, se op, y, s) at the add's place (nets/resnet.py:63-92 with use_se)."""
+    ('seblock', out, z, pre, shortcut, se op, y, s) at the add's place (nets/resnet.py:63-92 with use_se).  With tail = 'add' and
+    record = SeLin: the same sequence ending in an add without activation -> 'selin' (the SE-IResNet block, nets/iresnet.py)."""
     users = _users(plan, plan_inputs)
     drop, repl = set(), {}
     for j, op in enumerate(plan):
@@ -384,13 +391,13 @@ def _fuse_se_blocks(plan, shapes, feature_name, se_fused):
             continue
         se = plan[u[0]]
         u2 = users.get(se.out, [])
-        if len(u2) != 1 or plan[u2[0]][0] != 'addrelu' or se.out == feature_name:
+        if len(u2) != 1 or plan[u2[0]][0] != tail or se.out == feature_name:
             continue
         ar = plan[u2[0]]
         sc = ar.b if ar.a == se.out else ar.a
         if sc == se.out or shapes[sc] != shapes[op.out] or shapes[op.out][-1] % 4:
             continue
-        repl[u2[0]] = SeBlock('seblock', ar.out, op.inp, op.pre, sc, se, op.out, se.out)
+        repl[u2[0]] = record(record.__name__.lower(), ar.out, op.inp, op.pre, sc, se, op.out, se.out)
         drop.update([j, u[0]])
         se_fused[op.out] = ('y', ar.out, op.inp)
         se_fused[se.out] = ('s', ar.out, op.inp)
@@ -428,7 +435,7 @@ def _bn_fusion(plan, pusers, feature_name):
     producer = {op[1]: j for j, op in enumerate(plan) if op[0] in ('conv', 'gconv')}
     prelu_net = any(op[0] == 'bnprelu' for op in plan)
     for j, op in enumerate(plan):
-        if op[0] not in ('bn', 'bnstats', 'seblock', 'bnprelu'):
+        if op[0] not in ('bn', 'bnstats', 'seblock', 'selin', 'bnprelu'):
             continue
         i = producer.get(op.inp)
         if i is not None and pusers.get(op.inp, []) == [j]:
@@ -472,7 +479,7 @@ def _shortcut_branches(plan, pusers, feature_name):
             continue
         cons = plan[us[0]]
         as_res = (cons[0] == 'bn' and cons.res == op.out and cons.inp != op.out) or (cons[0] == 'addrelu' and op.out in (cons.a, cons.b)) or \
-            (cons[0] == 'seblock' and cons.shortcut == op.out and cons.inp != op.out)
+            (cons[0] in ('seblock', 'selin') and cons.shortcut == op.out and cons.inp != op.out)
         i = producer.get(op.inp)
         if as_res and i is not None and pusers.get(op.inp, []) == [j] and i == j - 1:
             shortcut_fwd[i] = True
@@ -480,18 +487,26 @@ def _shortcut_branches(plan, pusers, feature_name):
     return shortcut_fwd
 
 
-def compile_net(graph, spec, in_hwc, channel_pad, feature_name, options, num_classes, logits_width, name=''):
+def compile_net(graph, spec, in_hwc, channel_pad, feature_name, options, num_classes, logits_width, name='', se_hidden_pad=None):
     """The whole static analysis of a net -> Plan.  `spec`: variable name -> (reference shape, kind); `logits_width`: stored
-    columns of the classifier output."""
+    columns of the classifier output; `se_hidden_pad`: multiple the SE gates' hidden width is stored at (None: channel_pad)."""
     narrow = narrow_variables(graph, spec, channel_pad, options)
     shapes, real_c, embed_in = infer_shapes(graph, spec, in_hwc, channel_pad, narrow, num_classes, logits_width)
-    plan = _fuse_graph(graph, spec, shapes, real_c, channel_pad, name)
+    plan = _fuse_graph(graph, spec, shapes, real_c, channel_pad, name, se_hidden_pad)
     # SE residual block: BN (no activation) -> SE gate -> add shortcut -> ReLU becomes ONE plan op whose kernels read the BN's input z
     # and write the block's output; the BN output and the gated tensor never exist (csrc/layers.hip "SE residual block",
     # fte_se_*).  FTE_SE_FUSE=0: the separate ops (A/B hook).
     se_fused = {}
     if options.se_fuse:
         plan = _fuse_se_blocks(plan, shapes, feature_name, se_fused)
+        # ... and without the ReLU (the SE-IResNet block tail): 'selin', fte_se_lin_* (csrc/iresnet.hip)
+        plan = _fuse_se_blocks(plan, shapes, feature_name, se_fused, 'add', SeLin)
+    bare = [op.out for op in plan if op[0] == 'add']
+    if bare:
+        raise ValueError('%s: BN -> SE gate -> add without an activation (%s%s) runs only as the fused plan op %r; %s' % (
+            name, bare[0], ', ...' if len(bare) > 1 else '', 'selin',
+            'there is no unfused path for it: unset FTE_SE_FUSE=0' if not options.se_fuse else
+            'the BN, the gate and the add must each be the only reader of their input, and the shortcut must have the shape of the BN output'))
     pusers = _users(plan, plan_inputs)
     folded = _fold_into_gathers(plan, pusers, feature_name) if options.bn_gather else {}
     fuse_fwd, fuse_bwd = _bn_fusion(plan, pusers, feature_name) if options.bn_fuse else ({}, {})
@@ -499,7 +514,8 @@ def compile_net(graph, spec, in_hwc, channel_pad, feature_name, options, num_cla
     shortcut_fwd = _shortcut_branches(plan, pusers, feature_name) if options.shortcut_side else {}
     # tensors read by a BN AND by the activation-free shortcut of a later BN (the input of an IResNet identity block): the only
     # place where two gradient contributions are summed outside a conv's `addin` (_add); everywhere else a second one is a plan bug (_put)
-    shortcut_shared = {op.res for op in plan if op[0] == 'bn' and op.res is not None and not op.relu}
+    shortcut_shared = {op.res for op in plan if op[0] == 'bn' and op.res is not None and not op.relu} | \
+        {op.shortcut for op in plan if op[0] == 'selin'}
     last = plan[-1]
     return Plan(plan, shapes, real_c, narrow, embed_in, folded, se_fused, fuse_fwd, fuse_bwd, fold_apply, shortcut_fwd, shortcut_shared,
                 last[0] == 'fc' and spec[last.wname][1] == 'cls_w')
