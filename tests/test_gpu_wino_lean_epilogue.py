@@ -4,7 +4,7 @@ uses them (fte_conv3x3_fwd_keep_act, nets/sphere.py).
 A residual block's first conv writes z only and the second conv's tile transform applies the PReLU to that z; the data gradient of a
 block's second conv has neither ADD nor RAW.  Both must give what the generic path gives -- `==` on every tensor, which lets only the
 sign of a zero differ (the generic epilogue adds the absent tensor's 0.0) -- and both paths are held to the float64 oracle at the 2e-5
-of tests/test_gpu_wino.py.  FTE_WINO_LEAN=0 (read by the library at every call, and by the net at every forward) is the old path."""
+of tests/test_gpu_wino.py.  FTE_WINO_LEAN=0 (read by the library at every call, and by the net when it is constructed) is the old path."""
 import os
 
 import numpy as np

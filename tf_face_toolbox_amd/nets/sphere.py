@@ -16,18 +16,49 @@ MI355X-first layout decisions (engine-internal; the boundary keeps the reference
   * every conv keeps z (pre-activation) and y = PReLU(z) (+shortcut): backward needs sign(z)
     and min(z,0) exactly, for any alpha.
 """
-import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
 from .. import _lib, heads
 from ..loss import sample_size
 from .net_base import NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
+from .sphere_plan import StageRing, split_point, wino_plan
 
 NUM_BLOCKS = (1, 2, 4, 1)     # nets/sphere.py:58,62,66,70
 EMBED = 512                   # nets/sphere.py:73
+
+Options = namedtuple('Options', [
+    'bf16_copies',      # FTE_BF16_COPIES (1): in the bf16 MFMA mode the convs read bf16 copies of their operands (net.bf16_copies starts here)
+    'wino_keep',        # FTE_WINO_KEEP (1): a Winograd layer's forward leaves the V pack of its input for its filter gradient
+    'wino_lean',        # FTE_WINO_LEAN (1): the first conv of a block whose two convs keep a pack writes no y (the library reads it too)
+    'side_stream',      # FTE_SIDE_STREAM (unset: 'size'): filter gradients on a second stream: 0 'off', 1 'forced', else where it pays
+    'fwd_halves',       # FTE_FWD_HALVES (unset: 'auto'): forward walk as two part shards: 0 'off', 1 'forced', else from fwd_halves_min
+    'fwd_split',        # FTE_FWD_SPLIT (unset: None): images in the first part shard instead of the planned split point
+    'fwd_halves_min',   # FTE_FWD_HALVES_MIN (128): smallest shard the 'auto' part-shard walk takes
+    'dz_buffers',       # FTE_DZ_BUFFERS (3, at least 2): dz buffers per stage: with 3, wgrad(l) may still read its dz while dgrad(l - 1) writes
+])
+
+# what one pass may use, resolved by the forward walk for the backward walk of the same pass: the activations were kept (training);
+# bf16 storage; the convs read bf16 copies (storage included); the Winograd layers kept their V packs; ... and the lean blocks wrote no y
+Mode = namedtuple('Mode', 'keep s16 copies vpack lean')
+
+LayerViews = namedtuple('LayerViews', 'w b a')       # a conv's filter, bias (or None) and alpha in one of the arenas, made once in build()
+
+PLAIN, KEEP, LEAN_FIRST, LEAN_SECOND = range(4)      # a layer's forward launch in the fp32 training walk (_wino_tables)
+
+
+def read_options(env=None):
+    """SphereNet's switches as one immutable record.  SphereNet.__init__ calls this, so a switch acts on the nets constructed after
+    it is set (the precision mode and fte_set_conv_algo are not among them: they are asked of _lib at every step)."""
+    env = os.environ if env is None else env
+    three = lambda k, other: {'0': 'off', '1': 'forced'}.get(env.get(k), other)
+    return Options(
+        bf16_copies=env.get('FTE_BF16_COPIES', '1') != '0', wino_keep=env.get('FTE_WINO_KEEP', '1') != '0',
+        wino_lean=env.get('FTE_WINO_LEAN', '1') != '0', side_stream=three('FTE_SIDE_STREAM', 'size'),
+        fwd_halves=three('FTE_FWD_HALVES', 'auto'), fwd_split=int(env['FTE_FWD_SPLIT']) if 'FTE_FWD_SPLIT' in env else None,
+        fwd_halves_min=int(env.get('FTE_FWD_HALVES_MIN', '128')), dz_buffers=max(2, int(env.get('FTE_DZ_BUFFERS', '3'))))
 
 
 def same_pads(in_size, k, stride):
@@ -38,6 +69,11 @@ def same_pads(in_size, k, stride):
 
 class _Conv(object):
     __slots__ = ('name', 'stage', 'stride', 'has_bias', 'second', 'cin', 'cout', 'hin', 'win', 'hout', 'wout')
+
+    @property
+    def tiles(self):
+        """2x2-output Winograd tiles per image of the layer's input"""
+        return ((self.hin + 1) // 2) * ((self.win + 1) // 2)
 
 
 class Variable(object):
@@ -64,11 +100,17 @@ class SphereNet(Network):
         self.built = False
         # in the bf16 MFMA mode the convs read bf16 COPIES of their operands (written by the producing epilogue / packed
         # once per step) through fte_conv2d_*16: bit-identical to the operand mode, half the bytes through the load path
-        self.bf16_copies = os.environ.get('FTE_BF16_COPIES', '1') != '0'
+        self.options = read_options()
+        self.bf16_copies = self.options.bf16_copies
         self.tower_scale = 1.0        # 1/num_gpus, set by the parallel wrapper (data_parallel.py:37)
         self.global_step = 0          # A-softmax lambda annealing reads it
         self.sub_centers = 1          # K centres per class (SphereNetAdditiveMargin only; fte.h "Sub-center ArcFace")
-        self._act_n = None
+        self.one_stream = False       # True: one chain, forward and backward (bench.py's launch-record steps: a launch's duration is its own)
+        self._trace_dz = None         # a dict: the backward walk leaves a copy of every layer's dz in it (scripts/trace_dz.py)
+        self._act_n = self._act_key = None
+        self._split_key, self._split = None, 0
+        self._mode = Mode(False, False, False, False, False)
+        self.packs = self.side = self._images = None
 
     # ------------------------------------------------------------------ construction
     def _conv_specs(self, h, w, cin):
@@ -96,6 +138,7 @@ class SphereNet(Network):
         self.num_classes = int(num_classes)
         self.cpad = (self.num_classes + 127) // 128 * 128
         self.convs = self._conv_specs(height, width, channels)
+        self.cls_w, self.fc_w = 'classifier/fc_classifier/weights', self.name + '/fully_connected/weights'
         last = self.convs[-1]
         self.feat_hwc = (last.hout, last.wout, last.cout)
         self.fin = last.hout * last.wout * last.cout
@@ -107,18 +150,18 @@ class SphereNet(Network):
             small.append((c.name + '/alpha', 'alpha', (c.cout,), c.cout))
             big.append((c.name + '/weights', 'conv_w', (3, 3, c.cin, c.cout), 9 * c.cin * c.cout))
         small.append((self.name + '/fully_connected/biases', 'fc_b', (EMBED,), EMBED))
-        big.append((self.name + '/fully_connected/weights', 'fc_w', (self.fin, EMBED), self.fin * EMBED))
+        big.append((self.fc_w, 'fc_w', (self.fin, EMBED), self.fin * EMBED))
         # K centres per class: K planes of cpad columns, centre k of class j at column k * cpad + j; the reference layout packs them
         K = self.sub_centers
-        big.append(('classifier/fc_classifier/weights', 'cls_w', (EMBED, K * self.num_classes), EMBED * K * self.cpad))
+        big.append((self.cls_w, 'cls_w', (EMBED, K * self.num_classes), EMBED * K * self.cpad))
         self.variables = OrderedDict()
         off = 0
         for nm, kind, shape, size in small + big:
             self.variables[nm] = Variable(nm, kind, shape, off, size)
             off += (size + 3) // 4 * 4
         self.small_end = self.variables[big[0][0]].offset
-        self.cls_start = self.variables['classifier/fc_classifier/weights'].offset
-        self.fc_start = self.variables[self.name + '/fully_connected/weights'].offset
+        self.cls_start = self.variables[self.cls_w].offset
+        self.fc_start = self.variables[self.fc_w].offset
         self._stage_first = [min(self.variables[c.name + '/weights'].offset for c in self.convs if c.stage == st_)
                              for st_ in sorted(set(c.stage for c in self.convs))]
         self.arena_size = off
@@ -126,6 +169,9 @@ class SphereNet(Network):
         self.params = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grads = torch.zeros(off + 4, dtype=torch.float32, device=dev)      # +4: [ce, reg, -, -] loss slots
         self.loss_slots = self.grads[off:off + 4]
+        views = lambda arena: [LayerViews(self.view(c.name + '/weights', arena), self.view(c.name + '/biases', arena) if c.has_bias else None,
+                                          self.view(c.name + '/alpha', arena)) for c in self.convs]
+        self._pv, self._gv = views(self.params), views(self.grads)      # per layer: parameters, gradients
         self.state = self._make_state()                   # non-trainable variables: outside the arena, never all-reduced
         self._init_params()
         self.built = True
@@ -154,11 +200,11 @@ class SphereNet(Network):
             self.view(c.name + '/alpha').fill_(0.25)
         lim = (6.0 / (self.fin + EMBED)) ** 0.5
         w = (torch.rand(self.fin, EMBED, generator=g) * 2 - 1) * lim
-        self.view(self.name + '/fully_connected/weights').copy_(w.reshape(-1))
+        self.view(self.fc_w).copy_(w.reshape(-1))
         K = self.sub_centers                              # every plane drawn on its own: identical planes would tie on every sample
         wc = torch.zeros(EMBED, K, self.cpad)
         wc[:, :, :self.num_classes] = (torch.randn(EMBED, K * self.num_classes, generator=g) * 0.001).reshape(EMBED, K, self.num_classes)
-        self.view('classifier/fc_classifier/weights').copy_(wc.reshape(-1))
+        self.view(self.cls_w).copy_(wc.reshape(-1))
 
     # ---- reference-layout import / export ----------------------------------------------
     def _fc_perm(self, t, to_internal):
@@ -211,81 +257,85 @@ class SphereNet(Network):
     def _alloc_acts(self, n):
         s16 = self._storage16()
         key = (s16, _lib.get_mfma_dtype(), _lib.query('fte_get_conv_algo'))      # what the workspace / V-pack sizes depend on
-        if self._act_n == n and getattr(self, '_act_key', None) == key:
+        if self._act_n == n and self._act_key == key:
             return
-        self._act_key = key
-        dev = self.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        i16 = dict(dtype=torch.int16, device=dev)
-        self._act_s16 = s16
-        self.y16 = None
-        self.z, self.y = [], []
+        self._act_key, self._act_s16 = key, s16
+        self._alloc_forward(n, s16)
+        self._alloc_backward(n, s16)
+        self._wino_tables(n, s16)
+        self._alloc_workspace(n)
+        self._alloc_head(n)
+        self._act_n = n
+
+    def _alloc_forward(self, n, s16):
+        """z / y of every layer (bf16 storage: as bf16, and in fp32 for the last layer only) and the head's buffers"""
+        f32 = dict(dtype=torch.float32, device=self.device)
         last = len(self.convs) - 1
-        for l, c in enumerate(self.convs):
-            keep32 = not s16 or l == last
-            self.z.append(torch.empty(n, c.hout, c.wout, c.cout, **f32) if keep32 else None)
-            self.y.append(torch.empty(n, c.hout, c.wout, c.cout, **f32) if keep32 else None)
-        self.lean = [False] * len(self.convs)             # filled below, with the V packs
-        if s16:
-            self.z16 = [torch.empty(n, c.hout, c.wout, c.cout, **i16) for c in self.convs]
+        act = lambda c, dtype: torch.empty(n, c.hout, c.wout, c.cout, dtype=dtype, device=self.device)
+        self.z = [act(c, torch.float32) if not s16 or l == last else None for l, c in enumerate(self.convs)]
+        self.y = [act(c, torch.float32) if not s16 or l == last else None for l, c in enumerate(self.convs)]
+        self.z16 = [act(c, torch.int16) for c in self.convs] if s16 else None
+        self.y16 = None                                   # allocated on first use (_alloc_copies)
         self.emb = torch.empty(n, EMBED, **f32)
         hw = self._head_width()                           # cpad; the sampled-class head: its Spad columns
-        self.s_raw = torch.empty(n, hw, **f32)
-        self.G = torch.empty(n, hw, **f32)
+        self.s_raw, self.G = torch.empty(n, hw, **f32), torch.empty(n, hw, **f32)
         self.logits_buf = torch.empty(n, hw // self.sub_centers, **f32) if self.head == 'asoftmax' or self.head in NORMALISED_HEADS else self.s_raw
-        self.loss_rows = torch.empty(n, **f32)
-        self.xn = torch.empty(n, **f32)
-        self.wn = torch.empty(hw, **f32)
-        self.rowcoef = torch.empty(n, **f32)
-        self.colcoef = torch.empty(hw, **f32)
+        self.loss_rows, self.xn, self.rowcoef = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
+        self.wn, self.colcoef = torch.empty(hw, **f32), torch.empty(hw, **f32)
         self.demb = torch.empty(n, EMBED, **f32)
-        self.bwd = {}
-        for si in range(4):
+
+    def _alloc_backward(self, n, s16):
+        """one StageRing per stage; bf16 storage: bf16 only, the last stage keeps one fp32 dz / raw for the dense layer's backward epilogue"""
+        self.bwd = []
+        for si in range(len(NUM_BLOCKS)):
             c = [q for q in self.convs if q.stage == si][0]
-            shp = (n, c.hout, c.wout, c.cout)
-            if s16:      # bf16 only (dz16 / raw16); the last stage keeps one fp32 dz / raw for the dense layer's backward epilogue
-                one = [torch.empty(shp, **f32)] if si == 3 else []
-                self.bwd[si] = dict(dz=one, raw=list(one and [torch.empty(shp, **f32)]), dzi=0, rawi=0,
-                                    dz16=[torch.empty(shp, **i16) for _ in range(self._dz_buffers())],
-                                    raw16=[torch.empty(shp, **i16), torch.empty(shp, **i16)])
+            new = lambda k, dtype: [torch.empty(n, c.hout, c.wout, c.cout, dtype=dtype, device=self.device) for _ in range(k)]
+            if s16:
+                dz16 = new(self.options.dz_buffers, torch.int16)
+                self.bwd.append(StageRing(dz16, new(2, torch.int16), dz16, new(2, torch.float32) if si == len(NUM_BLOCKS) - 1 else None))
             else:
-                self.bwd[si] = dict(dz=[torch.empty(shp, **f32) for _ in range(self._dz_buffers())],
-                                    raw=[torch.empty(shp, **f32), torch.empty(shp, **f32)], dzi=0, rawi=0)
-        need = 4096
+                self.bwd.append(StageRing(new(self.options.dz_buffers, torch.float32), new(2, torch.float32)))
+
+    def _algo(self, *shape_op):
+        return _lib.query('fte_conv3x3_algo', *shape_op)
+
+    def _wino_tables(self, n, s16):
+        """Winograd layers (fte.h FTE_CONV_*; the reference's train.py:260): the forward pass leaves V = B^T d B of its input for the
+        layer's filter gradient (fte_conv3x3_fwd_keep / fte_conv3x3_wgrad_kept) -- one tile transform instead of two.
+        Residual blocks whose two convs both keep a V pack (lean[l], l = the block's second conv): the training forward does not
+        write the first conv's y = prelu(z).  Its readers are the second conv's tile transform, which takes z and alpha instead
+        (fte_conv3x3_fwd_keep_act), and that conv's filter gradient, which reads the kept pack; the data gradient reads z.  Those
+        y buffers (1.3 GB of writes per step at 512 images) are allocated only when another walk asks for them (_y_buf).
+        FTE_WINO_LEAN=0: the walk that writes every y (A/B hook; the library reads the same variable for its epilogues).
+        -> vpack, lean, and form[l]: the forward launch of layer l in the fp32 training walk."""
+        keep, self.lean = wino_plan(self.convs, n, self._algo, self.options, s16)
+        self.vpack = [torch.empty(_lib.query('fte_wino_pack_bytes', n, c.hin, c.win, c.cin) // 4, dtype=torch.float32, device=self.device)
+                      if k else None for c, k in zip(self.convs, keep)]
+        lean = [f and self.options.wino_lean for f in self.lean] + [False]
+        self.form = [LEAN_SECOND if lean[l] else LEAN_FIRST if lean[l + 1] else KEEP if keep[l] else PLAIN for l in range(len(keep))]
+        for l, f in enumerate(self.lean):
+            if f:
+                self.y[l - 1] = None
+
+    def _alloc_workspace(self, n):
         q = _lib.query
-        # Winograd layers (fte.h FTE_CONV_*; the reference's train.py:260): the forward pass leaves V = B^T d B of its input for the
-        # layer's filter gradient (fte_conv3x3_fwd_keep / fte_conv3x3_wgrad_kept) -- one tile transform instead of two
-        self.vpack = [None] * len(self.convs)
-        if not s16 and os.environ.get('FTE_WINO_KEEP', '1') != '0':
-            for l, c in enumerate(self.convs):
-                if l > 0 and c.stride == 1 and q('fte_conv3x3_algo', n, c.hin, c.win, c.cin, c.cout, 1, 0) == 1 \
-                        and q('fte_conv3x3_algo', n, c.hin, c.win, c.cin, c.cout, 1, 2) == 1:
-                    self.vpack[l] = torch.empty(q('fte_wino_pack_bytes', n, c.hin, c.win, c.cin) // 4, **f32)
-            # Residual blocks whose two convs both keep a V pack (lean[l], l = the block's second conv): the training forward does not
-            # write the first conv's y = prelu(z).  Its readers are the second conv's tile transform, which takes z and alpha instead
-            # (fte_conv3x3_fwd_keep_act), and that conv's filter gradient, which reads the kept pack; the data gradient reads z.  Those
-            # y buffers (1.3 GB of writes per step at 512 images) are allocated only when another walk asks for them (_y_buf).
-            # FTE_WINO_LEAN=0: the walk that writes every y (A/B hook; the library reads the same variable for its epilogues).
-            for l, c in enumerate(self.convs):
-                if c.second == 1 and self.vpack[l] is not None and self.vpack[l - 1] is not None:
-                    self.lean[l] = True
-                    self.y[l - 1] = None
+        need = 4096
         for c in self.convs[1:]:
             need = max(need, q('fte_conv3x3_fwd_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride),
                        q('fte_conv3x3_wgrad_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride),
                        q('fte_conv3x3_dgrad_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride))
         c0 = self.convs[0]
         need = max(need, q('fte_conv3x3_first_wgrad_ws_bytes', n, c0.hin, c0.win, c0.cin, c0.cout, c0.stride),
-                   q('fte_gemm_ws_bytes', n, EMBED, self.fin), q('fte_gemm_ws_bytes', n, hw, EMBED))
-        self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
+                   q('fte_gemm_ws_bytes', n, EMBED, self.fin), q('fte_gemm_ws_bytes', n, self._head_width(), EMBED))
+        self.ws = torch.empty((need + 3) // 4 + 1024, dtype=torch.float32, device=self.device)
         self.ws_bytes = self.ws.numel() * 4
+        self._alloc_side()
+
+    def _alloc_side(self):
         # filter gradients run on a second stream beside the data gradient of the same layer (_body_walk); their split-K slabs
         # need a workspace of their own
-        self.side = side_stream(self.device) if os.environ.get('FTE_SIDE_STREAM', '1') != '0' else None
+        self.side = side_stream(self.device) if self.options.side_stream != 'off' else None
         self.ws_side = torch.empty_like(self.ws) if self.side is not None else self.ws
-        self._alloc_head(n)
-        self._act_n = n
-        self.y16 = None                                   # allocated on first use (_alloc_copies)
 
     def _y_buf(self, l):
         """y of layer l; the first conv of a lean block (_alloc_acts) gets its buffer on the first walk that writes it"""
@@ -310,13 +360,11 @@ class SphereNet(Network):
         if self.y16 is not None and self.y16[0].shape[0] == self._act_n:
             return
         i16 = dict(dtype=torch.int16, device=self.device)
-        n = self._act_n
-        self.y16 = [torch.empty(n, c.hout, c.wout, c.cout, **i16) for c in self.convs]
-        for si in range(4):
-            b = self.bwd[si]
-            if 'dz16' not in b:
-                b['dz16'] = [torch.empty(b['dz'][0].shape, **i16) for _ in b['dz']]
-        if getattr(self, 'packs', None) is None:
+        self.y16 = [torch.empty(self._act_n, c.hout, c.wout, c.cout, **i16) for c in self.convs]
+        for ring in self.bwd:
+            if ring.dz16 is None:
+                ring.dz16 = [torch.empty(d.shape, **i16) for d in ring.dz]
+        if self.packs is None:
             from ._packs import FilterPacks
             self.packs = FilterPacks([(c.name, self.variables[c.name + '/weights'].offset, 3, c.cin, c.cout) for c in self.convs[1:]], self.device)
             self.w16, self.w16t = self.packs.w16, self.packs.w16t
@@ -337,39 +385,71 @@ class SphereNet(Network):
 
     def _fwd_split(self, n, copies):
         """Forward walk as two part shards on two streams: the size of the first part, or 0 (one chain).  fp32 Winograd plan only (the
-        direct kernels fill the chip by themselves and have no HBM-bound companion).  The first part must end on a whole 64-tile row
-        block of every kept V pack (the second part's pack is the rest of the shard's): the split point is the multiple of that
-        granule nearest below the middle (112 x 112: 64 images), and both parts must plan the same algorithm per layer as the whole
-        shard.  FTE_FWD_HALVES=0 / 1 forces it off / on where it is possible; FTE_FWD_SPLIT=<images> moves the split point (exploration)."""
-        env = os.environ.get('FTE_FWD_HALVES', 'auto')
-        if env == '0' or copies or self.side is None or n < 2 or getattr(self, 'one_stream', False):      # (one_stream: bench.py's launch-record steps)
+        direct kernels fill the chip by themselves and have no HBM-bound companion); sphere_plan.split_point has the rule."""
+        if copies or self.side is None or self.one_stream:      # (one_stream: bench.py's launch-record steps)
             return 0
-        key = (n, getattr(self, '_act_key', None))
-        if getattr(self, '_split_key', None) != key:
-            q = _lib.query
-            gran = 1
-            for l, c in enumerate(self.convs):
-                if self.vpack[l] is not None:
-                    tpi = ((c.hin + 1) // 2) * ((c.win + 1) // 2)
-                    gran = max(gran, 64 // math.gcd(64, tpi))      # (powers of two: the largest is their common multiple)
-            a = int(os.environ.get('FTE_FWD_SPLIT', (n // 2) // gran * gran))
-            ok, any_w = 0 < a < n, False
-            for l, c in enumerate(self.convs):
-                if l == 0 or c.stride != 1 or not ok:
-                    continue
-                algo = [q('fte_conv3x3_algo', m, c.hin, c.win, c.cin, c.cout, 1, 0) for m in (n, a, n - a)]
-                any_w = any_w or algo[0] == 1
-                if algo[1] != algo[0] or algo[2] != algo[0]:
-                    ok = False
-                if self.vpack[l] is not None and (a * ((c.hin + 1) // 2) * ((c.win + 1) // 2)) % 64:
-                    ok = False
-            self._split_key, self._split = key, (a if ok and any_w else 0)
-        if not self._split:
-            return 0
-        return self._split if env == '1' or n >= int(os.environ.get('FTE_FWD_HALVES_MIN', '128')) else 0
+        key = (n, self._act_key)
+        if self._split_key != key:
+            self._split_key, self._split = key, split_point(self.convs, [v is not None for v in self.vpack], n, self._algo, self.options)
+        return self._split
 
     def _fwd_halves(self, n, copies):
         return self._fwd_split(n, copies) > 0
+
+    def _part_pack(self, l, lo, hi):
+        """the V pack of layer l for images [lo, hi): a part shard's is its part of the shard's (whole row blocks: split_point)"""
+        vp, n = self.vpack[l], self._act_n
+        if hi - lo != n:
+            per = self.convs[l].tiles * self.convs[l].cin * 16      # floats per image
+            vp = vp[lo * per:hi * per] if hi < n else vp[lo * per:]      # (the last part keeps the shard's padding rows)
+        return vp
+
+    def _layer_views(self, l, lo, hi):
+        """(conv spec, filter, bias, alpha, fp32 z to keep) of layer l; bf16 storage keeps fp32 z / y for the last layer only"""
+        return (self.convs[l],) + self._pv[l] + (self.z[l][lo:hi] if self._mode.keep and self.z[l] is not None else None,)
+
+    # layer l over images [lo, hi) on stream st (every forward kernel is per image: no statistics, nets/sphere.py:38-45): the stem,
+    # then one launch body per mode
+    def _fwd_stem(self, l, lo, hi, ws, st):
+        c, wv, bv, av, zz = self._layer_views(0, lo, hi)
+        x, m, call = self._images[lo:hi], self._mode, _lib.call
+        if m.s16:
+            call('fte_conv3x3_first_fwd_s16', x, wv, bv, av, self.z16[0][lo:hi] if m.keep else None, self.y16[0][lo:hi],
+                 hi - lo, c.hin, c.win, c.cin, c.cout, c.stride, st)
+            return
+        call('fte_conv3x3_first_fwd', x, wv, bv, av, zz, self.y[0][lo:hi], hi - lo, c.hin, c.win, c.cin, c.cout, c.stride, st)
+        if m.copies:
+            call('fte_to_bf16', self.y[0][lo:hi], self.y16[0][lo:hi], self.y[0][lo:hi].numel(), st)
+
+    def _fwd_s16(self, l, lo, hi, ws, st):
+        """bf16 storage: every layer writes bf16 z / y only (+ the unrounded fp32 pair for the last layer: the dense layer reads it)"""
+        c, _, bv, av, zz = self._layer_views(l, lo, hi)
+        _lib.call('fte_conv2d_fwd_s16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, self.y16[l - 2][lo:hi] if c.second == 1 else None,
+                  self.z16[l][lo:hi] if self._mode.keep else None, self.y16[l][lo:hi], zz, self.y[l][lo:hi] if self.y[l] is not None else None,
+                  hi - lo, c.hin, c.win, c.cin, c.cout, 3, c.stride, ws, self.ws_bytes, st)
+
+    def _fwd_copies(self, l, lo, hi, ws, st):
+        """bf16 operands read as copies: the epilogue writes fp32 y and its bf16 copy"""
+        c, _, bv, av, zz = self._layer_views(l, lo, hi)
+        _lib.call('fte_conv2d_fwd16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, self.y[l - 2][lo:hi] if c.second == 1 else None, zz,
+                  self.y[l][lo:hi], self.y16[l][lo:hi], hi - lo, c.hin, c.win, c.cin, c.cout, 3, c.stride, ws, self.ws_bytes, st)
+
+    def _fwd_f32(self, l, lo, hi, ws, st):
+        """fp32 storage, operands as the library's mode has them: the layer's Winograd form of _wino_tables while the packs are kept"""
+        c, wv, bv, av, zz = self._layer_views(l, lo, hi)
+        form, call = self.form[l] if self._mode.vpack else PLAIN, _lib.call
+        shape = (hi - lo, c.hin, c.win, c.cin, c.cout, c.stride)
+        if form == LEAN_SECOND:      # the input is prelu(z) of the block's first conv, formed in the tile transform
+            call('fte_conv3x3_fwd_keep_act', self.z[l - 1][lo:hi], self._pv[l - 1].a, wv, bv, av, self.y[l - 2][lo:hi], zz,
+                 self.y[l][lo:hi], *shape, self._part_pack(l, lo, hi), ws, self.ws_bytes, st)
+        elif form == LEAN_FIRST:     # z only
+            call('fte_conv3x3_fwd_keep_act', self.y[l - 1][lo:hi], None, wv, bv, av, None, zz, None, *shape, self._part_pack(l, lo, hi), ws, self.ws_bytes, st)
+        else:
+            res = self.y[l - 2][lo:hi] if c.second == 1 else None
+            if form == KEEP:
+                call('fte_conv3x3_fwd_keep', self.y[l - 1][lo:hi], wv, bv, av, res, zz, self.y[l][lo:hi], *shape, self._part_pack(l, lo, hi), ws, self.ws_bytes, st)
+            else:
+                call('fte_conv3x3_fwd', self.y[l - 1][lo:hi], wv, bv, av, res, zz, self.y[l][lo:hi], *shape, ws, self.ws_bytes, st)
 
     def backbone(self, inputs, is_training=False, reuse=None):
         """nets/sphere.py:47-76: [N,H,W,C] NHWC -> embedding [N,512] (a view of an internal buffer)."""
@@ -380,69 +460,19 @@ class SphereNet(Network):
         assert (h, w, ch) == self.in_hwc, ((h, w, ch), self.in_hwc)
         self._alloc_acts(n)
         st = _stream()
-        call = _lib.call
-        keep = is_training
         self._images = x
         s16 = self._storage16()
         copies = self._use_copies() or s16
-        self._copies_live = copies and keep              # backward of THIS forward may use the bf16 copies
-        self._s16_live = s16 and keep
-        self._vpack_live = keep and not copies           # ... or the V packs the Winograd layers keep
-        lean_live = self._vpack_live and os.environ.get('FTE_WINO_LEAN', '1') != '0'
-        self._lean_live = lean_live                      # ... with no y of the first conv of a lean block
+        vpack = is_training and not copies
+        m = self._mode = Mode(is_training, s16, copies, vpack, vpack and self.options.wino_lean)
         nl = len(self.convs)
-        if not lean_live:                                # (before any stream forks: the part shards write them from two streams)
+        if not m.lean:                                   # (before any stream forks: the part shards write them from two streams)
             for l in range(nl):
                 self._y_buf(l)
         if copies:
             self._alloc_copies()
             self._pack_weights(st)
-        def part_pack(l, c, lo, hi, m):
-            vp = self.vpack[l]
-            if m != n:                               # a part shard's V pack is its part of the shard's (whole row blocks: _fwd_split)
-                per = ((c.hin + 1) // 2) * ((c.win + 1) // 2) * c.cin * 16      # floats per image
-                vp = vp[lo * per:hi * per] if hi < n else vp[lo * per:]        # (the last part keeps the shard's padding rows)
-            return vp
-
-        def layer(l, c, lo, hi, ws, st):
-            """layer l over images [lo, hi) on stream st (every forward kernel is per image: no statistics, nets/sphere.py:38-45)"""
-            m = hi - lo
-            wv = self.view(c.name + '/weights')
-            bv = self.view(c.name + '/biases') if c.has_bias else None
-            av = self.view(c.name + '/alpha')
-            zz = self.z[l][lo:hi] if keep and self.z[l] is not None else None      # (bf16 storage keeps fp32 z / y for the last layer only)
-            if s16:
-                # bf16 storage: every layer writes bf16 z / y only (+ the unrounded fp32 pair for the last layer: the dense layer reads it)
-                z16 = self.z16[l][lo:hi] if keep else None
-                if l == 0:
-                    call('fte_conv3x3_first_fwd_s16', x[lo:hi], wv, bv, av, z16, self.y16[0][lo:hi], m, c.hin, c.win, c.cin, c.cout, c.stride, st)
-                else:
-                    call('fte_conv2d_fwd_s16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, self.y16[l - 2][lo:hi] if c.second == 1 else None,
-                         z16, self.y16[l][lo:hi], zz, self.y[l][lo:hi] if self.y[l] is not None else None, m, c.hin, c.win, c.cin, c.cout, 3, c.stride,
-                         ws, self.ws_bytes, st)
-            elif lean_live and self.lean[l]:             # second conv of a lean block: the input is prelu(z) of the first, formed in the tile transform
-                p = self.convs[l - 1]
-                call('fte_conv3x3_fwd_keep_act', self.z[l - 1][lo:hi], self.view(p.name + '/alpha'), wv, bv, av, self.y[l - 2][lo:hi], zz,
-                     self.y[l][lo:hi], m, c.hin, c.win, c.cin, c.cout, c.stride, part_pack(l, c, lo, hi, m), ws, self.ws_bytes, st)
-            elif lean_live and l + 1 < nl and self.lean[l + 1]:      # first conv of a lean block: z only
-                call('fte_conv3x3_fwd_keep_act', self.y[l - 1][lo:hi], None, wv, bv, av, None, zz, None,
-                     m, c.hin, c.win, c.cin, c.cout, c.stride, part_pack(l, c, lo, hi, m), ws, self.ws_bytes, st)
-            elif l == 0:
-                call('fte_conv3x3_first_fwd', x[lo:hi], wv, bv, av, zz, self.y[0][lo:hi], m, c.hin, c.win, c.cin, c.cout, c.stride, st)
-                if copies:
-                    call('fte_to_bf16', self.y[0][lo:hi], self.y16[0][lo:hi], self.y[0][lo:hi].numel(), st)
-            else:
-                res = self.y[l - 2][lo:hi] if c.second == 1 else None
-                if copies:
-                    call('fte_conv2d_fwd16', self.y16[l - 1][lo:hi], self.w16t[c.name], bv, av, res, zz, self._y_buf(l)[lo:hi], self.y16[l][lo:hi],
-                         m, c.hin, c.win, c.cin, c.cout, 3, c.stride, ws, self.ws_bytes, st)
-                elif keep and self.vpack[l] is not None:
-                    call('fte_conv3x3_fwd_keep', self._y_buf(l - 1)[lo:hi], wv, bv, av, res, zz, self._y_buf(l)[lo:hi],
-                         m, c.hin, c.win, c.cin, c.cout, c.stride, part_pack(l, c, lo, hi, m), ws, self.ws_bytes, st)
-                else:
-                    call('fte_conv3x3_fwd', self._y_buf(l - 1)[lo:hi], wv, bv, av, res, zz, self._y_buf(l)[lo:hi],
-                         m, c.hin, c.win, c.cin, c.cout, c.stride, ws, self.ws_bytes, st)
-
+        launch = [self._fwd_stem] + [self._fwd_s16 if s16 else self._fwd_copies if copies else self._fwd_f32] * (nl - 1)
         split = self._fwd_split(n, copies)
         if split:
             # Two part shards (halves), one per stream: layer l of one part runs beside the tile transform of the other (an HBM-bound
@@ -452,21 +482,20 @@ class SphereNet(Network):
             # the stride-2 layers may split their K sums differently: ~1e-7 relative; tests/test_gpu_stress.py).
             main, side = torch.cuda.current_stream(), self.side
             side.wait_stream(main)
-            for l, c in enumerate(self.convs):
-                layer(l, c, 0, split, self.ws, st)
-                layer(l, c, split, n, self.ws_side, side.cuda_stream)
+            for l in range(nl):
+                launch[l](l, 0, split, self.ws, st)
+                launch[l](l, split, n, self.ws_side, side.cuda_stream)
             main.wait_stream(side)
         else:
-            for l, c in enumerate(self.convs):
-                layer(l, c, 0, n, self.ws, st)
-        call('fte_gemm_nn', self.y[-1], self.view(self.name + '/fully_connected/weights'),
-             self.view(self.name + '/fully_connected/biases'), self.emb, n, EMBED, self.fin, self.ws, self.ws_bytes, st)
+            for l in range(nl):
+                launch[l](l, 0, n, self.ws, st)
+        _lib.call('fte_gemm_nn', self.y[-1], self.view(self.fc_w), self.view(self.name + '/fully_connected/biases'), self.emb,
+                  n, EMBED, self.fin, self.ws, self.ws_bytes, st)
         return self.emb
 
     def _head_cols(self):
         """(W, dW, live columns, leading dimension) of the classifier columns the head runs on: here all of them, in the arenas"""
-        cls = 'classifier/fc_classifier/weights'
-        return self.view(cls), self.view(cls, self.grads), self.num_classes, self.cpad
+        return self.view(self.cls_w), self.view(self.cls_w, self.grads), self.num_classes, self.cpad
 
     def _classifier_raw(self, n):
         W, _, _, ld = self._head_cols()
@@ -550,9 +579,8 @@ class SphereNet(Network):
         call = _lib.call
         g = self.grads
         self._head_backward(n, st)
-        fcw = self.name + '/fully_connected/weights'
         call('fte_reduce_rows', self.demb, self.view(self.name + '/fully_connected/biases', g), None, 1, n, EMBED, 1, 1.0, st)
-        call('fte_gemm_tn', self.y[-1], self.demb, self.view(fcw, g), n, EMBED, self.fin, self.ws, self.ws_bytes, st)
+        call('fte_gemm_tn', self.y[-1], self.demb, self.view(self.fc_w, g), n, EMBED, self.fin, self.ws, self.ws_bytes, st)
 
     def backward(self):
         for stage in self.backward_stages():
@@ -566,19 +594,14 @@ class SphereNet(Network):
         it = self._body_walk()
         return [self.backward_head] + [lambda it=it: next(it) for _ in range(len(self._stage_first))]
 
-    @staticmethod
-    def _dz_buffers():
-        # three dz buffers per stage: wgrad(l) may still be reading its dz while dgrad(l - 1) writes the next one (_body_walk)
-        return max(2, int(os.environ.get('FTE_DZ_BUFFERS', '3')))
-
     def _side_stream(self, n):
         """The stream of the filter gradients, or None for the one-stream walk.  Measured on MI355X (fp32, images/s, one stream ->
         two): 64 per GPU 7.95 k -> 8.30 k, 128: 9.08 k -> 9.44 k, 256: 9.79 k -> 9.96 k, 512: 10.44 k -> 10.30 k -- at 512 every
         kernel is many rounds of blocks, nothing is left to cover and two MFMA-bound kernels sharing the chip cost 1.3 %; in the
         bf16 mode (launches 3x shorter) 512 gains too: 16.63 -> 16.13 ms.  FTE_SIDE_STREAM=0 / 1 forces one / two streams."""
-        if self.side is None or getattr(self, 'one_stream', False):      # one_stream: bench.py's launch-record steps (a launch's duration is its own)
+        if self.side is None or self.one_stream:         # one_stream: bench.py's launch-record steps (a launch's duration is its own)
             return None
-        if os.environ.get('FTE_SIDE_STREAM') == '1':
+        if self.options.side_stream == 'forced':
             return self.side
         # ... and with the Winograd layers (round 6) at every size: the data gradient's tile transform (HBM-bound, 68 registers) shares the
         # CUs with the resident filter-gradient kernel of the other stream (MFMA-bound): 34.5 -> 33.4 ms per step at 512 images
@@ -588,136 +611,110 @@ class SphereNet(Network):
         for _ in self._body_walk():
             pass
 
-    def _body_walk(self):
-        """Generator over the conv stack's backward pass; yields each time every filter gradient of one stage is final."""
-        n = self._act_n
-        st = _stream()
-        call = _lib.call
-        g = self.grads
-        fcw = self.name + '/fully_connected/weights'
-        L = self.convs
-        last = len(L) - 1
-        b4 = self.bwd[L[last].stage]
-        d_out, dz_cur = b4['raw'][0], b4['dz'][0]
-        b4['rawi'], b4['dzi'] = 0, 0
-        call('fte_gemm_nt', self.demb, self.view(fcw), self.z[last], self.view(L[last].name + '/alpha'), L[last].cout,
-             d_out, dz_cur, self.view(L[last].name + '/alpha', g), n, EMBED, self.fin, self.ws, self.ws_bytes, st)
-        s16 = getattr(self, '_s16_live', False) and self._storage16()
-        copies = s16 or (getattr(self, '_copies_live', False) and self._use_copies())
-        dz16_cur = None
-        d16_out = None                                  # bf16 storage: the skip-path gradient (what `d_out` is in fp32)
+    def _dense_backward(self, ring, s16, copies, st):
+        """the dense layer's data gradient with the last conv's PReLU backward in its epilogue -> (dz, skip gradient, bf16 dz) of the last
+        layer in the mode's precision; bf16 storage: written in fp32 (ring.f32) and rounded, the skip gradient too"""
+        c, call = self.convs[-1], _lib.call
+        dz, raw = ring.reset()
+        dz32, raw32 = ring.f32 if s16 else (dz, raw)
+        call('fte_gemm_nt', self.demb, self.view(self.fc_w), self.z[-1], self._pv[-1].a, c.cout, raw32, dz32,
+             self._gv[-1].a, self._act_n, EMBED, self.fin, self.ws, self.ws_bytes, st)
         if copies:
-            dz16_cur = b4['dz16'][0]
-            call('fte_to_bf16', dz_cur, dz16_cur, dz_cur.numel(), st)
+            call('fte_to_bf16', dz32, ring.dz16[0], dz32.numel(), st)
         if s16:
-            d16_out = b4['raw16'][0]
-            call('fte_to_bf16', d_out, d16_out, d_out.numel(), st)
-        trace = getattr(self, '_trace_dz', None)
-        # Second stream: wgrad(l) and dgrad(l) both consume dz(l) and are independent of each other (and of every other layer's
-        # wgrad), so the filter gradients are queued on `side` and share the chip with the dgrad chain -- at small per-GPU shards a
-        # launch is one round of blocks whose prologue, epilogue and stragglers (~25 us of 130) are covered by the other stream's
-        # MFMAs.  dz rotates through the stage's three buffers: before dgrad(l) overwrites one, the main stream waits for the
-        # wgrad that read it (two layers earlier).
-        # Same kernels, same operands, same order of every reduction: bit-identical to the one-stream walk.
-        main, side = torch.cuda.current_stream(), self._side_stream(n)
+            call('fte_to_bf16', raw32, raw, raw32.numel(), st)
+        return dz, raw, ring.dz16[0] if copies else None
+
+    # filter gradient of layer l from its dz (dz16: the bf16 one where the mode has it), one launch body per mode ...
+    def _wgrad_stem(self, dz, s16, st):
+        c = self.convs[0]
+        _lib.call('fte_conv3x3_first_wgrad_s16' if s16 else 'fte_conv3x3_first_wgrad', self._images, dz, self._gv[0].w,
+                  self._act_n, c.hin, c.win, c.cin, c.cout, c.stride, self.ws, self.ws_bytes, st)
+
+    def _wgrad16(self, l, dz, dz16, ws, st):
+        c = self.convs[l]
+        _lib.call('fte_conv2d_wgrad16', self.y16[l - 1], dz16, self._gv[l].w, self._act_n, c.hin, c.win, c.cin, c.cout,
+                  3, c.stride, ws, self.ws_bytes, st)
+
+    def _wgrad_f32(self, l, dz, dz16, ws, st):
+        c, m = self.convs[l], self._mode
+        gw, shape = self._gv[l].w, (self._act_n, c.hin, c.win, c.cin, c.cout, c.stride)
+        if m.vpack and self.vpack[l] is not None:
+            # (x is never read beside a kept pack -- fte.h -- and in a lean block y[l - 1] was not written)
+            _lib.call('fte_conv3x3_wgrad_kept', None if m.lean and self.lean[l] else self.y[l - 1], dz, gw, *shape, self.vpack[l], ws, self.ws_bytes, st)
+        else:
+            _lib.call('fte_conv3x3_wgrad', self.y[l - 1], dz, gw, *shape, ws, self.ws_bytes, st)
+
+    # ... and its data gradient: dz (+ addin) -> dz_prev (+ its bf16 copy), raw: the skip gradient it leaves for the block's shortcut
+    def _dgrad_tail(self, l):
+        """the arguments every data gradient ends on: dalpha and dbias of the layer below, the shard and the layer's shape"""
+        c, g = self.convs[l], self._gv[l - 1]
+        return g.a, g.b, self._act_n, c.hin, c.win, c.cin, c.cout
+
+    def _dgrad_s16(self, l, dz, dz16, addin, raw, dz_prev, dz16_prev, st):
+        c = self.convs[l]
+        _lib.call('fte_conv2d_dgrad_s16', dz, self.w16[c.name], addin, self.z16[l - 1], self._pv[l - 1].a, raw, dz_prev,
+                  *self._dgrad_tail(l), 3, c.stride, self.ws, self.ws_bytes, st)
+
+    def _dgrad_copies(self, l, dz, dz16, addin, raw, dz_prev, dz16_prev, st):
+        c = self.convs[l]
+        _lib.call('fte_conv2d_dgrad16', dz16, self.w16[c.name], addin, self.z[l - 1], self._pv[l - 1].a, raw, dz_prev, dz16_prev,
+                  *self._dgrad_tail(l), 3, c.stride, self.ws, self.ws_bytes, st)
+
+    def _dgrad_f32(self, l, dz, dz16, addin, raw, dz_prev, dz16_prev, st):
+        c = self.convs[l]
+        _lib.call('fte_conv3x3_dgrad', dz, self._pv[l].w, addin, self.z[l - 1], self._pv[l - 1].a, raw, dz_prev,
+                  *self._dgrad_tail(l), c.stride, self.ws, self.ws_bytes, st)
+
+    def _body_walk(self):
+        """Generator over the conv stack's backward pass; yields each time every filter gradient of one stage is final.
+        Second stream: wgrad(l) and dgrad(l) both consume dz(l) and are independent of each other (and of every other layer's
+        wgrad), so the filter gradients are queued on `side` and share the chip with the dgrad chain -- at small per-GPU shards a
+        launch is one round of blocks whose prologue, epilogue and stragglers (~25 us of 130) are covered by the other stream's
+        MFMAs.  dz rotates through the stage's three buffers (StageRing): before dgrad(l) overwrites one, the main stream waits for
+        the wgrad that read it (two layers earlier).
+        Same kernels, same operands, same order of every reduction: bit-identical to the one-stream walk."""
+        m, L, st = self._mode, self.convs, _stream()
+        s16, copies = m.keep and m.s16, m.keep and m.copies
+        wgrad = self._wgrad16 if copies else self._wgrad_f32
+        dgrad = self._dgrad_s16 if s16 else self._dgrad_copies if copies else self._dgrad_f32
+        dz, d_out, dz16 = self._dense_backward(self.bwd[L[-1].stage], s16, copies, st)
+        main, side = torch.cuda.current_stream(), self._side_stream(self._act_n)
         wst, wws = (side.cuda_stream, self.ws_side) if side is not None else (st, self.ws)
         readers = {}                                    # dz buffer -> event: the filter gradient that reads it has finished
         last_w = None
-        for l in range(last, -1, -1):
-            c = L[l]
-            if trace is not None:
-                trace[c.name] = (dz16_cur if s16 else dz_cur).clone()
-            gw = self.view(c.name + '/weights', g)
-            if l == 0:
-                if last_w is not None:
-                    main.wait_event(last_w)
-                if s16:
-                    call('fte_conv3x3_first_wgrad_s16', self._images, dz16_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
-                         self.ws, self.ws_bytes, st)
-                else:
-                    call('fte_conv3x3_first_wgrad', self._images, dz_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
-                         self.ws, self.ws_bytes, st)
-                break
+        for l in range(len(L) - 1, 0, -1):
+            c, p = L[l], L[l - 1]
+            if self._trace_dz is not None:
+                self._trace_dz[c.name] = dz.clone()
             if side is not None:
                 side.wait_event(main.record_event())    # dz(l) is complete
-            if copies:
-                call('fte_conv2d_wgrad16', self.y16[l - 1], dz16_cur, gw, n, c.hin, c.win, c.cin, c.cout, 3, c.stride,
-                     wws, self.ws_bytes, wst)
-            elif getattr(self, '_vpack_live', False) and self.vpack[l] is not None:
-                # (x is never read beside a kept pack -- fte.h -- and in a lean block y[l - 1] was not written)
-                call('fte_conv3x3_wgrad_kept', None if getattr(self, '_lean_live', False) and self.lean[l] else self.y[l - 1], dz_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
-                     self.vpack[l], wws, self.ws_bytes, wst)
-            else:
-                call('fte_conv3x3_wgrad', self.y[l - 1], dz_cur, gw, n, c.hin, c.win, c.cin, c.cout, c.stride,
-                     wws, self.ws_bytes, wst)
+            wgrad(l, dz, dz16, wws, wst)
             if side is not None:
-                last_w = readers[(dz16_cur if s16 else dz_cur).data_ptr()] = side.record_event()
-            p = L[l - 1]
-            bp = self.bwd[p.stage]
-            if s16:
-                # bf16 storage: dz and the skip-path gradient exist as bf16 only (same buffer rotation as below)
-                if p.stage != c.stage:
-                    bp['dzi'], bp['rawi'] = 0, 0
-                    raw16_t = bp['raw16'][0]
-                else:
-                    bp['dzi'] = (bp['dzi'] + 1) % len(bp['dz16'])
-                    raw16_t = bp['raw16'][bp['rawi'] ^ 1]
-                dz16_prev = bp['dz16'][bp['dzi']]
-                raw16 = raw16_t if p.second == 1 else None
-                ev = readers.pop(dz16_prev.data_ptr(), None)
-                if ev is not None:
-                    main.wait_event(ev)
-                call('fte_conv2d_dgrad_s16', dz16_cur, self.w16[c.name], d16_out if c.second == 0 else None, self.z16[l - 1],
-                     self.view(p.name + '/alpha'), raw16, dz16_prev, self.view(p.name + '/alpha', g),
-                     self.view(p.name + '/biases', g) if p.has_bias else None,
-                     n, c.hin, c.win, c.cin, c.cout, 3, c.stride, self.ws, self.ws_bytes, st)
-                if raw16 is not None:
-                    d16_out = raw16
-                    if p.stage == c.stage:
-                        bp['rawi'] ^= 1
-                dz16_cur = dz16_prev
-                if p.stage != c.stage:
-                    if last_w is not None:
-                        main.wait_event(last_w)
-                        last_w = None
-                        readers.clear()
-                    yield
-                continue
-            addin = d_out if c.second == 0 else None
-            if p.stage != c.stage:
-                bp['dzi'], bp['rawi'] = 0, 0
-                dz_prev, raw_t = bp['dz'][0], bp['raw'][0]
-            else:
-                bp['dzi'] = (bp['dzi'] + 1) % len(bp['dz'])
-                dz_prev = bp['dz'][bp['dzi']]
-                raw_t = bp['raw'][bp['rawi'] ^ 1]
-            raw = raw_t if p.second == 1 else None
+                last_w = readers[dz.data_ptr()] = side.record_event()
+            ring, boundary = self.bwd[p.stage], p.stage != c.stage
+            dz_prev, raw = ring.reset() if boundary else ring.advance()
+            raw = raw if p.second == 1 else None
             ev = readers.pop(dz_prev.data_ptr(), None)
             if ev is not None:
                 main.wait_event(ev)                     # an earlier layer's wgrad still reads the buffer dgrad(l) is about to overwrite
-            if copies:
-                dz16_prev = bp['dz16'][bp['dzi']]
-                call('fte_conv2d_dgrad16', dz16_cur, self.w16[c.name], addin, self.z[l - 1],
-                     self.view(p.name + '/alpha'), raw, dz_prev, dz16_prev, self.view(p.name + '/alpha', g),
-                     self.view(p.name + '/biases', g) if p.has_bias else None,
-                     n, c.hin, c.win, c.cin, c.cout, 3, c.stride, self.ws, self.ws_bytes, st)
-                dz16_cur = dz16_prev
-            else:
-                call('fte_conv3x3_dgrad', dz_cur, self.view(c.name + '/weights'), addin, self.z[l - 1],
-                     self.view(p.name + '/alpha'), raw, dz_prev, self.view(p.name + '/alpha', g),
-                     self.view(p.name + '/biases', g) if p.has_bias else None,
-                     n, c.hin, c.win, c.cin, c.cout, c.stride, self.ws, self.ws_bytes, st)
+            dz16_prev = ring.copy16() if copies else None
+            dgrad(l, dz, dz16, d_out if c.second == 0 else None, raw, dz_prev, dz16_prev, st)
             if raw is not None:
                 d_out = raw
-                if p.stage == c.stage:
-                    bp['rawi'] ^= 1
-            dz_cur = dz_prev
-            if p.stage != c.stage:
+                ring.take_raw()
+            dz, dz16 = dz_prev, dz16_prev
+            if boundary:
                 if last_w is not None:
                     main.wait_event(last_w)             # the stage's filter gradients are final for whoever follows on this stream
                     last_w = None
                     readers.clear()
                 yield                                   # stage c.stage is done: its filter gradients are final
+        if self._trace_dz is not None:
+            self._trace_dz[L[0].name] = dz.clone()
+        if last_w is not None:
+            main.wait_event(last_w)
+        self._wgrad_stem(dz, s16, st)
         yield
 
     # ------------------------------------------------------------------ bookkeeping the wrappers use
@@ -725,7 +722,7 @@ class SphereNet(Network):
         """nets/sphere.py:120-126: [backbone vars, classifier vars] (lists of Variable)."""
         bb = [v for k, v in self.variables.items() if k.startswith(self.name + '/')]
         if is_training:
-            return [bb, [self.variables['classifier/fc_classifier/weights']]]
+            return [bb, [self.variables[self.cls_w]]]
         return [bb]
 
     def pretrained_param(self, scope=None):
@@ -879,7 +876,7 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         if self.sample_rate is None:
             return labels, {}
         S = self.sample_size
-        heads.sample_classes(self, labels, self.view('classifier/fc_classifier/weights'), n, EMBED, self.num_classes, self.cpad, S,
+        heads.sample_classes(self, labels, self.view(self.cls_w), n, EMBED, self.num_classes, self.cpad, S,
                              self._head_width(), self.sample_seed, self.global_step, self.pfc_ws, self.pfc_ws.numel() * 4, st,
                              self.sample_comm)
         return self.sampled_labels, {'class_index': self.class_index[:S]}
@@ -894,7 +891,7 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         # under compact_head_update the classifier range of `grads` is NOT written (it holds whatever an earlier step or mode left there);
         # the gradient is compact_grad(), and apply_compact_update takes it into the classifier
         if self.sample_rate is not None and not self.compact_head_update:
-            _lib.call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, self.view('classifier/fc_classifier/weights', self.grads), EMBED,
+            _lib.call('fte_pfc_scatter_cols', self.dWs, self.class_inverse, self.view(self.cls_w, self.grads), EMBED,
                       self.num_classes, self.cpad, self.sample_size, self._head_width(), st)
 
     # ---- the compact classifier update (fte.h fte_pfc_momentum_update_cols / fte_pfc_adam_update_cols) -------------------------------
