@@ -1,6 +1,6 @@
 """-m gpu: oracle parity for EVERY tile instantiation the headline run (SphereFaceNet-20, 512 x 112 x 112 x 3) launches.
 
-Round-2 review: the planner (csrc/api.hip plan_rows / wgrad_plan) picks the 192x64 filter-gradient tile only for K ranges of
+Round-2 review: the planner (csrc/conv_plan.h plan_rows / wgrad_plan) picks the 192x64 filter-gradient tile only for K ranges of
 >= 1024 pixels per split (>= ~84 images of 56x56), the tall 128x64 forward / dgrad tile only at >= 4096 such tiles, and split counts
 of 153-256 only at the full batch -- none of which the small cases of test_gpu_kernels.py reach, so those instantiations were only
 ever compared with themselves (additivity 512 = 256 + 256).  Here each one runs at a size that triggers it NATURALLY (no hook) and
@@ -191,7 +191,7 @@ def test_pointwise_resident_filter_gradient():
 
 
 def test_stream_k_natural_at_the_small_shards():
-    """Round 5: launches of < 4 tiles (128x64) per CU run on igemm_sk_kernel (csrc/igemm.hip "stream-K"; planner: api.hip plan_sk) --
+    """Round 5: launches of < 4 tiles (128x64) per CU run on igemm_sk_kernel (csrc/igemm.hip "stream-K"; planner: conv_plan.h plan_sk) --
     forward on 64x64 tiles, data gradient on 128x64.  The 8-GPU shard of the headline (64 images) NATURALLY: 14x14x256 (1.53 tiles per
     CU, every tile split over 2-3 workers), 7x7x512 (0.78 per CU: was split-K + fix-up), 28x28x128 (3.06), the stride-2 entry of
     stage 3 (forward); the 128-image shard's 14x14 layer; and 56x56x64 must stay on the one-block-per-tile kernel (6 tiles per CU).
@@ -227,7 +227,7 @@ def test_stream_k_flag_words_in_the_workspace():
 
 def test_winograd_symbols_run_naturally_at_the_headline_shapes():
     """FTE_CONV_ALGO=auto (the default): the stride-1 3x3 layers of >= 128 channels take the Winograd kernels for all three products,
-    the 64-channel stage for forward and filter gradient (csrc/api.hip wino_sized); each symbol at a shard of the headline shape that
+    the 64-channel stage for forward and filter gradient (csrc/conv_plan.h wino_sized); each symbol at a shard of the headline shape that
     gives every resident block several tiles and a ragged last row block, block by block against the float64 oracle."""
     cs = _run([['fwd', 72, 14, 14, 256, 256, 1], ['dgrad', 72, 14, 14, 256, 256, 1], ['wgrad', 72, 14, 14, 256, 256, 1],
                ['fwd', 24, 28, 28, 128, 128, 1], ['dgrad', 24, 28, 28, 128, 128, 1], ['wgrad', 24, 28, 28, 128, 128, 1],

@@ -1,6 +1,6 @@
 """Child process of tests/test_gpu_tiles.py: runs fte_conv3x3_{fwd,dgrad,wgrad} through the C ABI on one case list and compares
 every result with the float64 oracle (oracle/ops.py), image block by image block so that the production sizes of the headline run
-(hundreds of 56x56 / 28x28 images) fit the host.  The tile / split-K hooks of csrc/api.hip are read ONCE per process
+(hundreds of 56x56 / 28x28 images) fit the host.  The tile / split-K hooks of csrc/conv_plan.h are read ONCE per process
 (FTE_WGRAD_TILE, FTE_WGRAD_SPLIT_MAJOR, ...), hence a process per environment.
 
     python tests/tile_worker.py '[["wgrad", n, h, w, cin, cout, stride], ["fwd", ...], ["dgrad", ...]]'

@@ -2,11 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "conv_plan.h"      // EPI_*, TILE_*, FIXUP_CHUNKS, igemm_tile_dims, igemm_sk_ws_bytes: shared with the host-only planner
+
 enum { AL_MK = 0, AL_KM = 1 };           // A operand: k-contiguous rows (im2col) | m-contiguous (k = pixel)
 enum { BL_KN = 0, BL_NK = 1 };           // B operand: [k][n] n-contiguous | [n][k] k-contiguous (per tap)
-enum { EPI_FWD = 0, EPI_DGRAD = 1 };
-enum { TILE_128x128 = 0, TILE_256x64 = 1, TILE_128x64 = 2, TILE_64x64 = 3, TILE_192x64 = 4,      // 192x64: M = 576 = 9 taps x 64 channels in three whole tiles
-       TILE_64x64_W1 = 5, TILE_64x64_W2 = 6 };  // 64x64 tile computed by ONE wave (64 threads, no barrier) / by two waves (128 threads)
 
 struct IgemmParams {
     int M, N, K;          // K = NT*KC (tap modes) or number of pixels (AL_KM)
@@ -80,17 +79,11 @@ struct IgemmParams {
 };
 
 hipError_t igemm_launch(const IgemmParams& p, int al, int bl, int epi, int tile, int splits, hipStream_t st);
-// the fix-up splits every tile into this many row chunks (one block each); a dgrad fix-up therefore writes
-// FIXUP_CHUNKS partial rows (PA/PB) per tile row, numbered prow0 + mt*FIXUP_CHUNKS + chunk
-constexpr int FIXUP_CHUNKS = 4;
 // sums `splits` partial tiles written through PW and applies the EPI_FWD / EPI_DGRAD epilogue of the same params
 hipError_t igemm_fixup(const IgemmParams& p, int epi, int tile, int splits, hipStream_t st);
-void igemm_tile_dims(int tile, int* bm, int* bn);
-// stream-K: resident blocks per CU the planner assumes for a tile shape (0: no stream-K instantiation of that shape), and the
-// workspace (slabs + flag words) a launch of `workers` blocks needs
+// stream-K: resident blocks per CU the planner assumes for a tile shape (0: no stream-K instantiation of that shape)
 int igemm_sk_blocks_per_cu(int tile, int epi);      // min(compiled figure, the runtime's occupancy of that symbol on this device)
 int igemm_num_cus();                                   // compute units of the current device (256 without one)
-size_t igemm_sk_ws_bytes(int tile, int workers);
 
 // igemm16.hip: the bf16 LDS-DMA kernel (k-contiguous bf16 A and B: conv forward / dgrad on the bf16 operand copies).  igemm_launch
 // routes a launch there when igemm16_handles() says so; everything else runs on igemm.hip's kernels.

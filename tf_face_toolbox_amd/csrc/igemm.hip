@@ -1540,18 +1540,3 @@ int igemm_sk_blocks_per_cu(int tile, int epi) {
     if (rt >= 0 && rt < v) v = rt;
     return env > 0 && env < v ? env : v;
 }
-size_t igemm_sk_ws_bytes(int tile, int workers) {
-    int bm, bn;
-    igemm_tile_dims(tile, &bm, &bn);
-    return (size_t)workers * bm * bn * sizeof(float) + (((size_t)workers * 4 + 255) & ~(size_t)255);
-}
-
-void igemm_tile_dims(int tile, int* bm, int* bn) {
-    switch (tile) {
-        case TILE_128x128: *bm = 128; *bn = 128; break;
-        case TILE_256x64:  *bm = 256; *bn = 64; break;
-        case TILE_128x64:  *bm = 128; *bn = 64; break;
-        case TILE_192x64:  *bm = 192; *bn = 64; break;
-        default:           *bm = 64;  *bn = 64; break;
-    }
-}

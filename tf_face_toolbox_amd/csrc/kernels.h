@@ -3,13 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_plan.h"      // REDUCE_SCRATCH_FLOATS: shared with the host-only planner
+
 hipError_t k_pack_weights_table(const float* params, unsigned short* w16t, const int* table, int nconv, long total, int transposed, hipStream_t st);
 hipError_t k_conv_first_fwd(const float* x, const float* w, const float* bias, const float* alpha, float* z, float* y,
                             unsigned short* z16, unsigned short* y16, int n, int h, int wd, int cin, int cout, int ho, int wo, int stride, int pt, int pl, hipStream_t st);
 int k_conv_first_wgrad_blocks(long npix);
 hipError_t k_conv_first_wgrad(const float* x, const float* dz, const unsigned short* dz16, float* part, int n, int h, int wd, int cin, int cout, int ho, int wo,
                               int stride, int pt, int pl, int blocks, hipStream_t st);
-constexpr long REDUCE_SCRATCH_FLOATS = 1 << 18;      // 1 MiB of scratch for the tall-and-narrow case of k_reduce_rows
 hipError_t k_reduce_rows(const float* in, float* out, const float* bias, int bmod, long rows, long cols, int fold, float scale,
                          float* scratch, hipStream_t st, int act = 0);
 // the same for two matrices of one shape in one launch (out2 may not alias out)

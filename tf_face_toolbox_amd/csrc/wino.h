@@ -5,20 +5,13 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
-// Geometry of one stride-1 SAME 3x3 layer over [n, h, w, c]: 2x2 output tiles, TH x TW of them per image (odd sizes: the last
-// tile row / column is half outside the image), M tiles in all, MB = row blocks of 64 tiles.
-struct WinoGeom {
-    int n, h, w, th, tw;
-    long M;
-    int MB;
-};
-WinoGeom wino_geom(int n, int h, int w);
+#include "conv_plan.h"      // WinoGeom / wino_geom, wino_pack_floats, wino_wgrad_splits: shared with the host-only planner
 
 // "pack" layout of every transformed operand, C channels (C % 8 == 0), R rows (tiles, or output channels for a filter):
 //   float index = ((((R / 64) * (C / 8) + c / 8) * 16 + t) * 64 + R % 64) * 8 + (((c % 8) / 4) ^ ((R % 64 / 16) & 1)) * 4 + c % 4
 // i.e. per (row block, 8-channel step) one contiguous 32 KiB slab [16 t][64 rows][8 channels] -- exactly the LDS image of one
 // K-step of wino_mm_kernel (the 16-byte halves of a row swapped for rows 16-31 and 48-63: conflict-free ds_read_b128 fragments).
-inline size_t wino_pack_floats(long rows, int c) { return (size_t)((rows + 63) / 64) * 64 * (size_t)c * 16; }
+// (wino_pack_floats(rows, c) counts its floats)
 
 // mode 0: V = B^T d B of the 4x4 input patch of every tile (forward: d = x; data gradient: d = dz)
 // mode 1: U' = G' d G'^T of the 2x2 tile itself (filter gradient: d = dz), G' = [[1,0],[.5,.5],[.5,-.5],[0,1]]
@@ -50,7 +43,6 @@ bool wino_lean_enabled();
 // filter gradient: slabs[s][t][cin][cout] = sum over the tiles of split s of V_t[tile][cin] * U'_t[tile][cout] with U' = G' e G'^T of
 // the 2x2 tiles of dz computed inside the kernel (dz: [n, h, w, cout] NHWC); then
 // dw[3][3][cin][cout] = A'^T (sum_s slabs) A' with A'^T = [[1,1,1,0],[0,1,-1,0],[0,1,1,-1]]
-int wino_wgrad_splits(int cin, int cout);      // 0: shape not supported
 hipError_t wino_wgrad(const float* V, const float* dz, float* slabs, float* dw, const WinoGeom& g, int cin, int cout, hipStream_t st);
 
 // conv algorithm switch (api.hip): 0 = direct implicit GEMM, 1 = Winograd wherever it applies, 2 = auto (the planner's rule)

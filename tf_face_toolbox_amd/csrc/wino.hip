@@ -737,14 +737,6 @@ int g_algo = -1;
 
 }  // namespace
 
-WinoGeom wino_geom(int n, int h, int w) {
-    WinoGeom g;
-    g.n = n; g.h = h; g.w = w; g.th = (h + 1) / 2; g.tw = (w + 1) / 2;
-    g.M = (long)n * g.th * g.tw;
-    g.MB = (int)((g.M + 63) / 64);
-    return g;
-}
-
 hipError_t wino_transform_tiles(const float* x, float* pack, int n, int h, int w, int c, int mode, hipStream_t st, bool small, const float* alpha) {
     if (c % 32 || (alpha && mode != 0)) return hipErrorInvalidValue;
     const WinoGeom g = wino_geom(n, h, w);
@@ -849,13 +841,6 @@ hipError_t wino_mm(const WinoMMParams& p, int epi, hipStream_t st) {
     }
     if (tail_base < nvirt) e = wino_mm_pick<1>(p, epi, lean, NBX, GRP, tail_base, nvirt, 2 * L, L, st);
     return e;
-}
-
-int wino_wgrad_splits(int cin, int cout) {
-    if (cin % 64 || cout % 64) return 0;
-    const int P = (cin / 64) * (cout / 64);
-    if (P > 256 || 256 % P) return 0;
-    return 256 / P;
 }
 
 hipError_t wino_wgrad(const float* V, const float* dz, float* slabs, float* dw, const WinoGeom& g, int cin, int cout, hipStream_t st) {
