@@ -9,6 +9,12 @@ The case kinds 'bnfwd1' / 'bnfold1' run fte_conv2d_bn_fwd of a 1x1 conv under bf
 FTE_PW16_* hooks of csrc/pw16.hip are read once per process too); their checks are the functions tests/test_gpu_pw16_edges.py calls
 in-process for the default environment.
 
+The bf16-storage kinds ('s16fwd', 's16dgrad', 's16fwd1', 's16dgrad1', 's16wgrad', 's16wgrad1') poison what they hand to the library: every bf16
+output holds CANARY16 and carries GUARD rows behind row M, dalpha / dbias / dw hold NaN, the workspace is NaN with 4 KB behind the granted
+bytes -- a guard row that changed, a canary left inside or a changed workspace tail fails the case.  's16fwdx' / 's16dgradx' are the
+EXACT-PLACEMENT kinds of a 3x3 conv (tests/win16_map.py: position-coded input, one power of two per output channel): the stored tensor must
+equal the tap-shifted input bit for bit.
+
 Prints one JSON line: {"cases": [{"case": [...], "symbols": [...kernel symbols the launch records name...], "splits": [...],
 "errors": {...}}], "ok": true|false}.  Tolerances are tests/util_gpu.py's (2e-5 max-abs / rel-L2 against float64)."""
 import json
@@ -22,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
+import win16_map                                           # noqa: E402
 from oracle import ops                                     # noqa: E402
 from tf_face_toolbox_amd import _lib                       # noqa: E402
 from util_gpu import call, query, stream, ws, TOL_MAXABS, TOL_RELL2      # noqa: E402
@@ -139,6 +146,46 @@ def _stored_ok(got16, ref64, scale):
     return float((err / lim).max()), bool((err <= lim).all())
 
 
+CANARY16 = 0x7fc1       # a bf16 NaN no kernel stores: an element still holding it was never written
+GUARD = 8               # rows behind row M of a bf16 output that must keep the canary
+
+
+def _out16(n, h, w, c):
+    """a poisoned bf16 output: (the [n, h, w, c] view the library writes, the whole buffer with GUARD rows behind row M)"""
+    M = n * h * w
+    buf = torch.full((M + GUARD, c), CANARY16, dtype=torch.int16, device='cuda')
+    return buf[:M].view(n, h, w, c), buf
+
+
+def _nan32(*shape):
+    return torch.full(shape, float('nan'), device='cuda')
+
+
+def _ws_nan(nbytes):
+    """a NaN workspace of exactly the granted bytes (what the library is told) with 4 KB of NaN behind them"""
+    nbytes = int(nbytes)
+    return torch.full(((nbytes + 3) // 4 + 1024,), float('nan'), device='cuda'), nbytes
+
+
+def _canary_fails(outs, wsb=None, nbytes=0, finite=()):
+    """outs: {name: whole buffer of _out16}; finite: {name: fp32 tensor that must be written everywhere} -> failure messages"""
+    fails = []
+    for name, buf in outs.items():
+        M = buf.shape[0] - GUARD
+        if not bool((buf[M:] == CANARY16).all()):
+            fails.append('%s: a guard row behind row M = %d was written' % (name, M))
+        left = int((buf[:M] == CANARY16).sum())
+        if left:
+            fails.append('%s: %d elements never written' % (name, left))
+    if wsb is not None and not bool(torch.isnan(wsb[(nbytes + 3) // 4:]).all()):
+        fails.append('workspace: written behind the granted %d bytes' % nbytes)
+    for name, t in dict(finite).items():
+        bad = int((~torch.isfinite(t)).sum())
+        if bad:
+            fails.append('%s: %d elements not finite (never written?)' % (name, bad))
+    return fails
+
+
 def run_s16fwd(n, h, w, cin, cout, stride, r, k=3):
     """fte_conv2d_fwd_s16 (bf16 x / shortcut in, bf16 z / y out): the persistent bf16 kernels at the sizes that select them"""
     assert stride == 1
@@ -151,13 +198,14 @@ def run_s16fwd(n, h, w, cin, cout, stride, r, k=3):
     b = r.standard_normal(cout, dtype=np.float32)
     al = (0.25 + 0.1 * r.standard_normal(cout, dtype=np.float32)).astype(np.float32)
     res, res16 = _bf(r.standard_normal((n, h, w, cout), dtype=np.float32))
-    z16 = torch.empty(n, h, w, cout, dtype=torch.int16, device='cuda'); y16 = torch.empty_like(z16)
-    wsb, nb = ws(query('fte_conv2d_fwd_ws_bytes', n, h, w, cin, cout, k, 1))
+    (z16, zbuf), (y16, ybuf) = _out16(n, h, w, cout), _out16(n, h, w, cout)
+    wsb, nb = _ws_nan(query('fte_conv2d_fwd_ws_bytes', n, h, w, cin, cout, k, 1))
     _lib.query('fte_prof_enable', 1)
     call('fte_conv2d_fwd_s16', x16, w16t, torch.from_numpy(b).cuda(), torch.from_numpy(al).cuda(), res16, z16, y16, None, None,
          n, h, w, cin, cout, k, 1, wsb, nb, stream())
     _lib.query('fte_prof_enable', 0)
     syms, splits = _records()
+    fails = _canary_fails({'z16': zbuf, 'y16': ybuf}, wsb, nb)
     b64, al64 = b.astype(np.float64), al.astype(np.float64)
     wz = wy = 0.0
     ok = True
@@ -166,7 +214,7 @@ def run_s16fwd(n, h, w, cin, cout, stride, r, k=3):
         yr = ops.prelu_fwd(zr, al64) + res[i:i + BLOCK]
         e, o = _stored_ok(z16[i:i + BLOCK], zr, np.abs(zr).max()); wz = max(wz, e); ok = ok and o
         e, o = _stored_ok(y16[i:i + BLOCK], yr, np.abs(yr).max()); wy = max(wy, e); ok = ok and o
-    return syms, splits, {'z_worst_over_limit': wz, 'y_worst_over_limit': wy}, ok
+    return syms, splits, {'z_worst_over_limit': wz, 'y_worst_over_limit': wy, 'fails': fails}, ok and not fails
 
 
 def run_s16dgrad(n, h, w, cin, cout, stride, r, k=3):
@@ -183,13 +231,14 @@ def run_s16dgrad(n, h, w, cin, cout, stride, r, k=3):
     zp[0, 0, 0, :4] = 0.0
     zprev, zp16 = _bf(zp)
     alp = (0.25 + 0.1 * r.standard_normal(cin, dtype=np.float32)).astype(np.float32)
-    raw16 = torch.empty(n, h, w, cin, dtype=torch.int16, device='cuda'); dzp16 = torch.empty_like(raw16)
-    da = torch.empty(cin, device='cuda'); db = torch.empty(cin, device='cuda')
-    wsb, nb = ws(query('fte_conv2d_dgrad_ws_bytes', n, h, w, cin, cout, k, 1))
+    (raw16, rawbuf), (dzp16, dzpbuf) = _out16(n, h, w, cin), _out16(n, h, w, cin)
+    da = _nan32(cin); db = _nan32(cin)
+    wsb, nb = _ws_nan(query('fte_conv2d_dgrad_ws_bytes', n, h, w, cin, cout, k, 1))
     _lib.query('fte_prof_enable', 1)
     call('fte_conv2d_dgrad_s16', dz16, w16, add16, zp16, torch.from_numpy(alp).cuda(), raw16, dzp16, da, db, n, h, w, cin, cout, k, 1, wsb, nb, stream())
     _lib.query('fte_prof_enable', 0)
     syms, splits = _records()
+    fails = _canary_fails({'raw16': rawbuf, 'dz16': dzpbuf}, wsb, nb, {'dalpha': da, 'dbias': db})
     al64 = alp.astype(np.float64)
     da_ref = np.zeros(cin); db_ref = np.zeros(cin)
     xshape = np.zeros((1, h, w, cin))
@@ -208,23 +257,90 @@ def run_s16dgrad(n, h, w, cin, cout, stride, r, k=3):
         return float(np.sqrt(((got - ref) ** 2).sum() / (ref ** 2).sum()))
     errs = {'raw_worst_over_limit': wr, 'dz_worst_over_limit': wd_,
             'dalpha_rell2': rl2(da.cpu().numpy().astype(np.float64), da_ref), 'dbias_rell2': rl2(db.cpu().numpy().astype(np.float64), db_ref)}
-    ok = ok and errs['dalpha_rell2'] <= TOL_RELL2 and errs['dbias_rell2'] <= TOL_RELL2
+    errs['fails'] = fails
+    ok = ok and errs['dalpha_rell2'] <= TOL_RELL2 and errs['dbias_rell2'] <= TOL_RELL2 and not fails
     return syms, splits, errs, ok
+
+
+def _bits(t16):
+    return t16.cpu().numpy()
+
+
+def _placement_errs(name, got16, want, errs, fails, bitwise=True):
+    """got16: int16 [n, h, w, N] device tensor; want: float64 (bf16-exact) -- bit for bit, or by value (+0 == -0)"""
+    if bitwise:
+        cnt, first = win16_map.placement_check(_bits(got16), _bits(_dev16(want)))
+    else:
+        cnt, first = win16_map.placement_check(_host16(got16), want)
+    errs[name + '_wrong_elements'] = cnt
+    if cnt:
+        fails.append('exact: %s differs from the tap-shifted input, first at (image, y, x, channel) = %s, %d in all' % (name, first, cnt))
+
+
+def run_s16fwdx(n, h, w, cin, cout, stride, r):
+    """EXACT placement, forward 3x3: position-coded x, one power of two per output channel at tap n mod 9 (tests/win16_map.py), zero bias,
+    no shortcut, alpha = 1/4 -- every product and sum is exact, so the stored z must equal the tap-shifted input element times its power of
+    two BIT FOR BIT, exact zero where the tap leaves the image; y = z or z / 4 by value"""
+    assert stride == 1
+    M = n * h * w
+    x = coded_input(M, cin).reshape(n, h, w, cin)
+    wd = torch.tensor(win16_map.hwio_filter('fwd', cin, cout), dtype=torch.float32, device='cuda')
+    w16 = torch.empty(3, 3, cin, cout, dtype=torch.int16, device='cuda'); w16t = torch.empty(3, 3, cout, cin, dtype=torch.int16, device='cuda')
+    call('fte_pack_weights_bf16', wd, w16, w16t, 3, cin, cout, stream())
+    (z16, zbuf), (y16, ybuf) = _out16(n, h, w, cout), _out16(n, h, w, cout)
+    wsb, nb = _ws_nan(query('fte_conv2d_fwd_ws_bytes', n, h, w, cin, cout, 3, 1))
+    _lib.query('fte_prof_enable', 1)
+    call('fte_conv2d_fwd_s16', _dev16(x), w16t, torch.zeros(cout, device='cuda'), torch.full((cout,), 0.25, device='cuda'), None, z16, y16, None, None,
+         n, h, w, cin, cout, 3, 1, wsb, nb, stream())
+    _lib.query('fte_prof_enable', 0)
+    syms, splits = _records()
+    fails = _canary_fails({'z16': zbuf, 'y16': ybuf}, wsb, nb)
+    want = win16_map.placement_expected('fwd', x, cout)
+    errs = {}
+    _placement_errs('z16', z16, want, errs, fails)
+    _placement_errs('y16', y16, np.where(want > 0, want, 0.25 * want), errs, fails, bitwise=False)
+    errs['fails'] = fails
+    return syms, splits, errs, not fails
+
+
+def run_s16dgradx(n, h, w, cin, cout, stride, r):
+    """EXACT placement, data gradient 3x3 in its plain form (no skip gradient, no previous z, no alpha, no dalpha / dbias): position-coded
+    dz, one power of two per INPUT channel -- the stored dx (and the raw copy) must equal the tap-shifted dz element times its power of two"""
+    assert stride == 1
+    M = n * h * w
+    dz = coded_input(M, cout).reshape(n, h, w, cout)
+    wd = torch.tensor(win16_map.hwio_filter('dgrad', cin, cout), dtype=torch.float32, device='cuda')
+    w16 = torch.empty(3, 3, cin, cout, dtype=torch.int16, device='cuda'); w16t = torch.empty(3, 3, cout, cin, dtype=torch.int16, device='cuda')
+    call('fte_pack_weights_bf16', wd, w16, w16t, 3, cin, cout, stream())
+    (raw16, rawbuf), (dx16, dxbuf) = _out16(n, h, w, cin), _out16(n, h, w, cin)
+    wsb, nb = _ws_nan(query('fte_conv2d_dgrad_ws_bytes', n, h, w, cin, cout, 3, 1))
+    _lib.query('fte_prof_enable', 1)
+    call('fte_conv2d_dgrad_s16', _dev16(dz), w16, None, None, None, raw16, dx16, None, None, n, h, w, cin, cout, 3, 1, wsb, nb, stream())
+    _lib.query('fte_prof_enable', 0)
+    syms, splits = _records()
+    fails = _canary_fails({'raw16': rawbuf, 'dx16': dxbuf}, wsb, nb)
+    want = win16_map.placement_expected('dgrad', dz, cin)
+    errs = {}
+    _placement_errs('dx16', dx16, want, errs, fails)
+    _placement_errs('raw16', raw16, want, errs, fails, bitwise=False)
+    errs['fails'] = fails
+    return syms, splits, errs, not fails
 
 
 def run_s16wgrad1(n, h, w, cin, cout, stride, r):
     """fte_conv2d_wgrad16 of a 1x1 conv: the pointwise resident kernel (wgrad16p_kernel) against the float64 product of the same bf16 inputs"""
     x, x16 = _bf(r.standard_normal((n, h, w, cin), dtype=np.float32))
     dz, dz16 = _bf(r.standard_normal((n, h, w, cout), dtype=np.float32))
-    dw = torch.empty(1, 1, cin, cout, device='cuda')
-    wsb, nb = ws(query('fte_conv2d_wgrad_ws_bytes', n, h, w, cin, cout, 1, stride))
+    dw = _nan32(1, 1, cin, cout)
+    wsb, nb = _ws_nan(query('fte_conv2d_wgrad_ws_bytes', n, h, w, cin, cout, 1, stride))
     _lib.query('fte_prof_enable', 1)
     call('fte_conv2d_wgrad16', x16, dz16, dw, n, h, w, cin, cout, 1, stride, wsb, nb, stream())
     _lib.query('fte_prof_enable', 0)
     syms, splits = _records()
+    fails = _canary_fails({}, wsb, nb, {'dw': dw})
     ref = x.reshape(-1, cin).astype(np.float64).T @ dz.reshape(-1, cout).astype(np.float64)
     e, s = _maxabs(dw.cpu().numpy().astype(np.float64).reshape(cin, cout), ref)
-    return syms, splits, {'dw_maxabs_rel': e / s}, e / s <= TOL_MAXABS
+    return syms, splits, {'dw_maxabs_rel': e / s, 'fails': fails}, e / s <= TOL_MAXABS and not fails
 
 
 def run_s16wgrad(n, h, w, cin, cout, stride, r):
@@ -232,27 +348,27 @@ def run_s16wgrad(n, h, w, cin, cout, stride, r):
     x, x16 = _bf(r.standard_normal((n, h, w, cin), dtype=np.float32))
     ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
     dz, dz16 = _bf(r.standard_normal((n, ho, wo, cout), dtype=np.float32))
-    dw = torch.empty(3, 3, cin, cout, device='cuda')
-    wsb, nb = ws(query('fte_conv2d_wgrad_ws_bytes', n, h, w, cin, cout, 3, stride))
+    dw = _nan32(3, 3, cin, cout)
+    wsb, nb = _ws_nan(query('fte_conv2d_wgrad_ws_bytes', n, h, w, cin, cout, 3, stride))
     _lib.query('fte_prof_enable', 1)
     call('fte_conv2d_wgrad16', x16, dz16, dw, n, h, w, cin, cout, 3, stride, wsb, nb, stream())
     _lib.query('fte_prof_enable', 0)
     syms, splits = _records()
+    fails = _canary_fails({}, wsb, nb, {'dw': dw})
     ref = np.zeros((3, 3, cin, cout))
     wz = np.zeros((3, 3, cin, cout))
     for i in range(0, n, BLOCK):
         _, d = ops.conv2d_bwd(x[i:i + BLOCK].astype(np.float64), wz, dz[i:i + BLOCK].astype(np.float64), stride, need_dx=False)
         ref += d
     e, s = _maxabs(dw.cpu().numpy().astype(np.float64), ref)
-    return syms, splits, {'dw_maxabs_rel': e / s}, e / s <= TOL_MAXABS
+    return syms, splits, {'dw_maxabs_rel': e / s, 'fails': fails}, e / s <= TOL_MAXABS and not fails
 
 
 # ---- fte_conv2d_bn_fwd under bf16 storage (tests/test_gpu_pw16_edges.py, tests/test_gpu_bn_fusion.py): conv, rounded z, the batch
 # statistics of the stored values; folded: the BN in front of the conv in the loader, y side-stored.  Called in-process by those modules
 # for the default environment and through main() ('bnfwd1' / 'bnfold1') where a hook of csrc/pw16.hip is set.
 BN_EPS, BN_DECAY = 1e-3, 0.999
-CANARY16 = 0x7fc1       # a bf16 NaN no kernel stores: an element still holding it was never written
-GUARD = 8               # rows behind row M of z and y_side that must keep the canary
+# (CANARY16 / GUARD above: z and y_side carry GUARD rows behind row M that must keep the canary)
 # the limits of tests/test_gpu_bn_fusion.py on the statistics of the stored z (max-abs over the channels, relative to the largest reference)
 BN_LIMITS = {'mean': 2e-6, 'rstd': 4e-6, 'scale': 4e-6, 'shift': 1e-5, 'moving_mean': 2e-6, 'moving_var': 2e-6}
 
@@ -468,7 +584,7 @@ def main():
         r = np.random.default_rng(100 + ci)
         syms, splits, errs, ok = {'fwd': run_fwd, 'dgrad': run_dgrad, 'wgrad': run_wgrad, 's16fwd': run_s16fwd, 's16dgrad': run_s16dgrad,
                                   's16fwd1': lambda *a: run_s16fwd(*a, k=1), 's16dgrad1': lambda *a: run_s16dgrad(*a, k=1),
-                                  's16wgrad': run_s16wgrad, 's16wgrad1': run_s16wgrad1,
+                                  's16wgrad': run_s16wgrad, 's16wgrad1': run_s16wgrad1, 's16fwdx': run_s16fwdx, 's16dgradx': run_s16dgradx,
                                   'bnfwd1': lambda *a: _run_bn1(*a, fold=False), 'bnfold1': lambda *a: _run_bn1(*a, fold=True)}[op](*dims, r)
         out.append({'case': c, 'symbols': syms, 'splits': splits, 'errors': errs, 'ok': bool(ok)})
         ok_all = ok_all and ok
