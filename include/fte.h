@@ -704,6 +704,39 @@ int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float*
 int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels,
                                float scale, float m, float m3, float* f, float* loss_rows, float* G, float* rowcoef,
                                int n, int c, int ld, float grad_scale, void* stream);
+/* Sharded margin head: fte_margin_softmax_fwd_bwd with the classes split over R ranks (model parallelism).
+ * Global batch of N = R * n_local rows in rank order (the `n` below is N), C = num_classes classes, Cs = ceil(C / R).  Rank r owns
+ * classes [lo_r, hi_r) = [r * Cs, min(C, (r + 1) * Cs)), c_r = hi_r - lo_r >= 1, stored as columns [D, ld_r] with ld_r = c_r rounded
+ * up to 128 and zero padding columns.  c_ij, t, t', eps, the clamp and the presets are those of fte_margin_softmax_fwd_bwd.  Labels
+ * are GLOBAL class ids: row i's target column lives on the one shard with lo <= y_i < hi, at local column y_i - lo.
+ *
+ * fte_margin_shard_stats -- for row i over this shard's live columns j < c, z_ij carrying the margin on the target column iff this
+ * shard owns it; stats is [3][n]:
+ *   stats[0][i] = max_j z_ij,   stats[1][i] = sum_j exp(z_ij - stats[0][i]),   stats[2][i] = z_iy if the shard owns y_i, else 0.0f
+ * A label outside [0, num_classes) gives NaN in all three on EVERY shard, never an out-of-bounds access.
+ *
+ * fte_margin_shard_fwd_bwd -- all_stats is [R][3][n], the shards' stats in rank order.  Per row, every sum over r in rank order (so
+ * every rank computes the same bits from the same all_stats):
+ *   M = max_r m_r,   Z = sum_r e_r * expf(m_r - M),   T = sum_r t_r,   loss_rows[i] = logf(Z) + M - T   (the same on every shard)
+ *   p_ij = exp(z_ij - M) / Z
+ *   G_ij = grad_scale * S * (p_ij - [j owns y]) * (t' or 1) / (max(xn_i, eps) * wn_j) on this shard's columns, 0 in c..ld-1
+ *   rowcoef_part[i] = xn_i > eps ? -sum_{j<c} G_ij s_ij / xn_i^2 : 0     (the shard's share: the shares add up to the dense rowcoef)
+ *   f (optional, may be NULL) = this shard's margin logits, 0 in the pads.
+ * A NaN statistic (or an out-of-range label) gives the NaN row of the dense contract; the other rows are bitwise unaffected.
+ * colcoef is the unchanged fte_asoftmax_colcoef over all N rows of the shard's G: complete on the owning rank.  With X [N, D] the
+ * gathered features, dW_r = X^T G + colcoef (.) W_r is FINAL (no all-reduce), dX = sum_r (G W_r^T + rowcoef_part (.) X).
+ * Both: 16-byte aligned s / wn / G / f and ld % 4 == 0 take the vector path, anything else the scalar one.  All sums are fp32 in a
+ * fixed order, no float atomics: two calls write identical bytes.
+ * FTE_EINVAL (nothing is launched): the cases of fte_margin_softmax_fwd_bwd, a null stats / all_stats, R < 1, class_lo < 0,
+ * class_lo + c > num_classes. */
+int fte_margin_shard_stats(const float* s, const float* xn, const float* wn, const int32_t* labels,
+                           int class_lo, int num_classes, float scale, float m, float m3,
+                           float* stats, int n, int c, int ld, void* stream);
+int fte_margin_shard_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels,
+                             int class_lo, int num_classes, float scale, float m, float m3,
+                             const float* all_stats, int R,
+                             float* f, float* loss_rows, float* G, float* rowcoef_part,
+                             int n, int c, int ld, float grad_scale, void* stream);
 /* Additive-margin softmax with a margin per row (the AdaFace head; Kim et al., CVPR 2022).  The contract is that of
  * fte_margin_softmax_fwd_bwd above -- c_ij, z_ij for j != y, loss_rows, G, rowcoef, the optional f, columns c..ld-1, the NaN row
  * of an out-of-range label -- with the target term of row i taken from a = a_rows[i], b = b_rows[i] (c = c_iy, E = 1e-3):

@@ -168,6 +168,8 @@ _SIGS = {
     'fte_asoftmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
     'fte_asoftmax_colcoef': (c_int, [_P] * 4 + [c_int] * 3 + [_P]),
     'fte_margin_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] * 3 + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
+    'fte_margin_shard_stats': (c_int, [_P] * 4 + [c_int] * 2 + [c_float] * 3 + [_P] + [c_int] * 3 + [_P]),
+    'fte_margin_shard_fwd_bwd': (c_int, [_P] * 4 + [c_int] * 2 + [c_float] * 3 + [_P, c_int] + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
     'fte_margin_softmax_rows_fwd_bwd': (c_int, [_P] * 4 + [c_float] + [_P] * 6 + [c_int] * 3 + [c_float, _P]),
     'fte_subcenter_margin_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_int] + [c_float] * 3 + [_P] * 4 + [c_int] * 3 + [c_float, _P]),
     'fte_subcenter_colcoef': (c_int, [_P] * 4 + [c_int] * 4 + [_P]),

@@ -802,6 +802,23 @@ int fte_margin_softmax_fwd_bwd(const float* s, const float* xn, const float* wn,
         return FTE_EINVAL;
     return rc(k_margin_softmax(s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
 }
+// the shard [class_lo, class_lo + c) must lie inside [0, num_classes) (the sum in 64 bits: class_lo + c may not wrap)
+static bool shard_ok(int class_lo, int num_classes, int c) { return class_lo >= 0 && (long long)class_lo + c <= (long long)num_classes; }
+int fte_margin_shard_stats(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes, float scale,
+                           float m, float m3, float* stats, int n, int c, int ld, void* stream) {
+    if (!s || !xn || !wn || !labels || !stats || n <= 0 || c <= 0 || ld < c || !(scale > 0.f) || !(m >= 0.f) || !shard_ok(class_lo, num_classes, c))
+        return FTE_EINVAL;
+    return rc(k_margin_shard_stats(s, xn, wn, labels, class_lo, num_classes, scale, m, m3, stats, n, c, ld, (hipStream_t)stream));
+}
+int fte_margin_shard_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes, float scale,
+                             float m, float m3, const float* all_stats, int R, float* f, float* loss_rows, float* G, float* rowcoef_part,
+                             int n, int c, int ld, float grad_scale, void* stream) {
+    if (!s || !xn || !wn || !labels || !all_stats || !loss_rows || !G || !rowcoef_part || n <= 0 || c <= 0 || ld < c || !(scale > 0.f) ||
+        !(m >= 0.f) || R < 1 || !shard_ok(class_lo, num_classes, c))
+        return FTE_EINVAL;
+    return rc(k_margin_shard_fwd_bwd(s, xn, wn, labels, class_lo, num_classes, scale, m, m3, all_stats, R, f, loss_rows, G, rowcoef_part,
+                                     n, c, ld, grad_scale, (hipStream_t)stream));
+}
 int fte_margin_softmax_rows_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale,
                                     const float* a_rows, const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef,
                                     int n, int c, int ld, float grad_scale, void* stream) {

@@ -29,6 +29,12 @@ hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, co
 hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, const float* a_rows,
                                  const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
                                  hipStream_t st);
+// the head with the classes split over R ranks (fte.h "Sharded margin head"): columns class_lo .. class_lo + c of num_classes
+hipError_t k_margin_shard_stats(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes,
+                                float scale, float m, float m3, float* stats, int n, int c, int ld, hipStream_t st);
+hipError_t k_margin_shard_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes,
+                                  float scale, float m, float m3, const float* all_stats, int R, float* f, float* loss_rows, float* G,
+                                  float* rowcoef_part, int n, int c, int ld, float gs, hipStream_t st);
 // K centres per class in K planes of ld columns (fte.h "Sub-center ArcFace"); K in 1..8 (hipErrorInvalidValue otherwise)
 hipError_t k_subcenter_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, int K, float scale, float m,
                                       float m3, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,

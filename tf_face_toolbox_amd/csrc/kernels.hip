@@ -705,6 +705,201 @@ __global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------
+// The same head with the classes split over R ranks (fte.h "Sharded margin head"): this rank holds columns class_lo .. class_lo + c
+// of the classifier, the labels are global.  Two kernels, each margin_softmax_kernel's pass with the same block per row, the same
+// chunking and the same target term (a row whose label another shard owns has no target column here: R.y = -1 matches none):
+//   margin_shard_stats_kernel   pass 1 alone -> (max, sum of exp against that max, target logit or 0) per row;
+//   margin_shard_fwd_bwd_kernel merges the R triples IN RANK ORDER (every rank gets the same M, Z, T and so the same loss bits),
+//                               then pass 2 with p = exp(z - M) / Z.
+// Kernels of their own for the reason given at margin_softmax_rows_kernel.
+// ------------------------------------------------------------------------------------
+struct ShardRow {
+    MarginRow R;
+    float tp;
+    bool bad, own;
+    // the row's label against this shard and, where the shard owns it, the target term as margin_softmax_kernel forms it
+    __device__ __forceinline__ void init(const float* sr, const float* wn, int yl, int lo, int c, int num_classes, float xr, float S, float m,
+                                         float m3) {
+        constexpr float EPS = 1e-12f;
+        bad = (unsigned)yl >= (unsigned)num_classes;          // out-of-range label: NaN row on every shard, no out-of-bounds access
+        own = !bad && yl >= lo && yl - lo < c;
+        R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
+        R.S = S;
+        R.y = own ? yl - lo : -1;
+        R.zy = 0.f;
+        tp = 1.f;
+        if (own) {
+            const float cy = clamp1(sr[R.y] * (R.ix * __builtin_amdgcn_rcpf(wn[R.y])));
+            float ty = cy - m3;
+            if (m > 0.f) {
+                const float cm = cosf(m), sm = sinf(m);
+                if (cy > -cm) {                                 // cos(pi - m) = -cos m: theta + m <= pi
+                    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+                    ty = cy * cm - st * sm - m3;
+                    tp = cm + sm * cy / fmaxf(st, 1e-6f);
+                } else {
+                    ty = cy - m * sm - m3;                      // easy_margin = False fallback
+                }
+            }
+            R.zy = S * ty;
+        }
+    }
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_shard_stats_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                 const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                 int lo, int num_classes, float S, float m, float m3,
+                                                                 float* __restrict__ stats, int n, int c, int ld) {
+    constexpr int U = 4;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * ld;
+    ShardRow Q;
+    Q.init(sr, wn, labels[row], lo, c, num_classes, xn[row], S, m, m3);
+    const MarginRow R = Q.R;
+    float mx = -INFINITY, se = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < c; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    float z[4], r;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
+                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
+                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < c; j += 256) {
+            float r;
+            const float z = R.z(sr[j], wn[j], j, r);
+            if (z > mx) { se *= __expf(mx - z); mx = z; }
+            se += __expf(z - mx);
+        }
+    }
+    const float M = block_max(mx, sh);
+    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
+    if (t == 0) {
+        stats[row] = Q.bad ? NAN : M;
+        stats[(long)n + row] = Q.bad ? NAN : se;
+        stats[2 * (long)n + row] = Q.bad ? NAN : R.zy;       // 0 where another shard owns the label
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_shard_fwd_bwd_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                   const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                   int lo, int num_classes, float S, float m, float m3,
+                                                                   const float* __restrict__ all_stats, int ranks, float* __restrict__ f,
+                                                                   float* __restrict__ loss_rows, float* __restrict__ G,
+                                                                   float* __restrict__ rowcoef, int n, int c, int ld, float gscale) {
+    constexpr int U = 4;
+    constexpr float EPS = 1e-12f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * ld;
+    float* gr = G + (long)row * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const float xr = xn[row];
+    ShardRow Q;
+    Q.init(sr, wn, labels[row], lo, c, num_classes, xr, S, m, m3);
+    // the R triples of the row, in rank order (every thread reads the same addresses: one broadcast load each)
+    float M = -INFINITY, Z = 0.f, T = 0.f;
+    bool bad = Q.bad;
+    for (int r = 0; r < ranks; ++r) {
+        const float mr = all_stats[((long)r * 3) * n + row];
+        bad = bad || mr != mr;                                  // fmaxf would drop a NaN
+        M = fmaxf(M, mr);
+    }
+    for (int r = 0; r < ranks; ++r) {
+        const float* a = all_stats + ((long)r * 3) * n + row;
+        const float er = a[n], tr = a[2 * (long)n];
+        bad = bad || er != er || tr != tr;
+        Z += er * expf(a[0] - M);
+        T += tr;
+    }
+    MarginRow R = Q.R;
+    if (bad) R.ix = R.zy = NAN;                                 // the NaN row of the dense contract: z, p and g below c are NaN
+    const int y = R.y;
+    const float inv = 1.f / Z;
+    const float gS = gscale * S, gT = gscale * S * Q.tp;
+
+    float acc = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < ld; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < ld) {
+                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
+                    if (j < c) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (j + k < c) {
+                                float r;
+                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
+                                const float p = __expf(z - M) * inv;
+                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
+                                acc += g * sv[u][k];
+                                gv[k] = g;
+                                fv[k] = z;
+                            }
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(gr + j) = gv;
+                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < ld; j += 256) {
+            float g = 0.f, fv = 0.f;
+            if (j < c) {
+                float r;
+                const float sv = sr[j];
+                const float z = R.z(sv, wn[j], j, r);
+                const float p = __expf(z - M) * inv;
+                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
+                acc += g * sv;
+                fv = z;
+            }
+            gr[j] = g;
+            if (fr) fr[j] = fv;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (t == 0) {
+        loss_rows[row] = bad ? NAN : (M + logf(Z)) - T;
+        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
+    }
+}
+
 // The same head with the margin of each row its own (AdaFace; fte.h fte_margin_softmax_rows_fwd_bwd): theta' = theta + a_i clipped
 // to [E, pi - E], t = cos(theta') - b_i.  Inside the clip cos(theta + a) and sin(theta + a) come from c, sin_t and one
 // sincos(a) -- no error of acos enters the logit; acos only decides whether the clip binds.  The per-row work is two scalar
@@ -1655,6 +1850,21 @@ hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, co
     const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
     if (vec) hipLaunchKernelGGL(margin_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(margin_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_margin_shard_stats(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes,
+                                float scale, float m, float m3, float* stats, int n, int c, int ld, hipStream_t st) {
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn) % 16 == 0;
+    if (vec) hipLaunchKernelGGL(margin_shard_stats_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, stats, n, c, ld);
+    else hipLaunchKernelGGL(margin_shard_stats_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, stats, n, c, ld);
+    return hipGetLastError();
+}
+hipError_t k_margin_shard_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes,
+                                  float scale, float m, float m3, const float* all_stats, int R, float* f, float* loss_rows, float* G,
+                                  float* rowcoef_part, int n, int c, int ld, float gs, hipStream_t st) {
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    if (vec) hipLaunchKernelGGL(margin_shard_fwd_bwd_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, all_stats, R, f, loss_rows, G, rowcoef_part, n, c, ld, gs);
+    else hipLaunchKernelGGL(margin_shard_fwd_bwd_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, all_stats, R, f, loss_rows, G, rowcoef_part, n, c, ld, gs);
     return hipGetLastError();
 }
 hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, const float* a_rows,

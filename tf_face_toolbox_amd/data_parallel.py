@@ -95,8 +95,33 @@ class _HostComm(object):
         self.dist.broadcast(t, src=src, group=self.group)
 
     def all_gather(self, out, t):
-        """out [world * len(t)] <- every rank's t, in rank order (the center loss's opt-in reconciliation)."""
-        self.dist.all_gather_into_tensor(out, t.contiguous(), group=self.group)
+        """out [world * len(t)] <- every rank's t, in rank order (the center loss's opt-in reconciliation).  Tensors of more
+        dimensions go as their flat views (out is contiguous, [world, *t.shape] or the rows of the ranks one after another): gloo
+        takes no stacked output shape."""
+        self.dist.all_gather_into_tensor(out.view(-1), t.contiguous().view(-1), group=self.group)
+
+    def reduce_scatter_sum(self, out, inp):
+        """out [len(inp) / world] <- this rank's rows of the sum of every rank's inp (the sharded head's dx, heads.py).  RCCL has the
+        collective; gloo has none, so there it is an all-reduce of inp IN PLACE followed by a copy of the rank's rows."""
+        if self.dist.get_backend(self.group) == 'nccl':
+            self.dist.reduce_scatter_tensor(out, inp, op=self.dist.ReduceOp.SUM, group=self.group)
+            return
+        self.dist.all_reduce(inp, op=self.dist.ReduceOp.SUM, group=self.group)
+        rows = out.shape[0]
+        out.copy_(inp[self.rank() * rows:(self.rank() + 1) * rows])
+
+
+def check_shard_classes(model, sync_sample=False):
+    """ValueError, with the reason, for every net and head option the sharded classifier does not compose with -- before anything is
+    built or communicated."""
+    from . import heads
+    name = getattr(model, 'name', type(model).__name__)
+    if not hasattr(model, 'shard_comm'):
+        raise ValueError('shard_classes: %s (%s, head %r) has no sharded classifier: only SphereNet-ArcFace / SphereNet-CosFace do (not the '
+                         'A-softmax and AdaFace nets, not the graph nets)' % (name, type(model).__name__, getattr(model, 'head', None)))
+    heads.check_sharding(model.head, model.sample_rate, sync_sample, model.sub_centers, name)
+    if getattr(model, 'built', False) and getattr(model, 'shard', None) is None:
+        raise ValueError('shard_classes: %s was already built with the dense classifier; pass a net that has not been built' % name)
 
 
 class Singular(object):
@@ -215,15 +240,23 @@ class Singular(object):
 class DataParallel(Singular):
     """data_parallel.py:81-166: synchronous data parallelism, one replica per GPU."""
 
-    def __init__(self, model, lr, optimizer, num_gpus=4, weight_decay=5e-4, comm=None, sync_centers=False, sync_sample=False):
+    def __init__(self, model, lr, optimizer, num_gpus=4, weight_decay=5e-4, comm=None, sync_centers=False, sync_sample=False,
+                 shard_classes=False):
         """`sync_centers` (not in the reference; default off = the reference's behaviour): the center loss's `centers` table
         is per-tower state there (loss.py:34-39) and the towers' tables drift apart; True all-gathers every step's scatter rows
         so that all replicas keep ONE table, equal to the single-tower update of the global batch (nets/graph.py _reconcile_centers).
         `sync_sample` (default off): a sampled-class head (sample_rate) under data parallelism.  The ranks all-gather their labels
         and draw ONE class sample from the global batch, the compact [D, Spad] classifier gradient is all-reduced instead of the
         dense one and goes straight into the classifier; without it such a net is refused.  No effect on a dense
-        head."""
+        head.
+        `shard_classes` (default off): the margin classifier split by class over the ranks (model parallelism for the head, DESIGN.md
+        4.20; SphereNet-ArcFace / -CosFace, dense head, one centre per class).  Rank r holds C / R columns, their optimizer slots
+        and their gradient; the features of the global batch are all-gathered, the classifier gradient is final on its rank and is
+        never all-reduced, dx comes back through a reduce-scatter.  The net must not have been built yet."""
         assert num_gpus > 1, 'DataParallel objects are only used for multi-gpu training tasks.'
+        self.shard_classes = bool(shard_classes)
+        if self.shard_classes:
+            check_shard_classes(model, sync_sample)
         if getattr(model, 'sample_rate', None) is not None and not sync_sample:
             # each rank sees other labels, so the ranks' samples would differ and the all-reduce would average gradients of
             # different column sets
@@ -257,8 +290,19 @@ class DataParallel(Singular):
         works = []
         buckets = m.grad_buckets()
         compact = None
+        sharded = self.shard_classes                    # until the head stage has run
         for stage, (a, b) in zip(m.backward_stages(), buckets):
             stage()
+            if sharded:
+                # behind backward_head the classifier gradient of this rank's columns is final (no rank holds another part of it): the
+                # update follows on the kernel stream, behind the products that read W, with no collective to wait for; the head bucket
+                # is the FC range and the loss slots get the 16-byte all-reduce of their own
+                sharded = False
+                if not getattr(self._opt, 'supports_ranges', False):
+                    raise ValueError('shard_classes needs an optimizer that updates a range of the arena')
+                self.learning_rate = self._lr_value()
+                self._opt.apply(self.learning_rate, self.global_step + 1, m.mult_lr_list(), m.cls_start, m.arena_size)
+                compact = (None, self.comm.all_reduce_async(m.loss_slots))
             if self._compact() and compact is None:
                 # the sampled-class head with one shared sample: behind backward_head the classifier gradient is the compact
                 # [D, Spad] buffer, the same columns on every rank, so its sum is the dense sum (the zeros of the other columns add
@@ -268,8 +312,9 @@ class DataParallel(Singular):
             works.append(self.comm.all_reduce_async(m.grads[a:b]))
         self.learning_rate = self._lr_value()
         if compact is not None:
-            compact[0].wait()
-            m.apply_compact_update(self._opt, self.learning_rate, self.global_step + 1, m.mult_lr_list())
+            if compact[0] is not None:
+                compact[0].wait()
+                m.apply_compact_update(self._opt, self.learning_rate, self.global_step + 1, m.mult_lr_list())
             compact[1].wait()
         if getattr(self._opt, 'supports_ranges', False):
             # bucket by bucket, in completion order: the head bucket (73 of the 120 MB) is updated while the later, smaller
@@ -294,6 +339,11 @@ class DataParallel(Singular):
             self.model.sample_comm = self.comm
             self.model.compact_head_update = True
         num_classes = inputs['num_classes']
+        if self.shard_classes:
+            from . import heads
+            check_shard_classes(self.model, self.sync_sample)
+            heads.shard_range(num_classes, self.num_gpus, self.comm.rank())      # a rank without a class: refused before the build
+            self.model.shard_comm = self.comm                 # before the construction pass: build() lays out this rank's columns
         self._global_batch = inputs.get('batch_size')
         scope = 'TOWER_%d' % self.comm.rank()
         # the reference's towers draw independent dropout masks (one layers.dropout op per tower); a shared seed would
@@ -317,9 +367,13 @@ class DataParallel(Singular):
         with self._Construction(self.model):
             losses, losses_name, others = tower()
         # train.py:101-120: every replica starts from replica 0's values
-        self.comm.broadcast(self.model.params, src=0)
+        self.comm.broadcast(self.replicated_params(), src=0)
         self.pretrained_param = self.model.pretrained_param()
         return train_ops, losses, losses_name, others
+
+    def replicated_params(self):
+        """the part of the parameter arena every rank holds a copy of: all of it, or what lies before a sharded classifier"""
+        return self.model.params[:self.model.cls_start] if self.shard_classes else self.model.params
 
 
 class DataParallel_margin(DataParallel):

@@ -98,6 +98,84 @@ def sample_classes(b, labels, W, n, d, c, ld, S, spad, seed, step, ws, wsb, st, 
     call('fte_pfc_gather_cols', W, b.class_index, b.Ws, d, c, ld, S, spad, st)
 
 
+# ---- the classifier split by class over the ranks (fte.h "Sharded margin head") ----------------------------------------
+def shard_range(num_classes, world, rank):
+    """Rank `rank` of `world` owns classes [lo, hi): Cs = ceil(C / R) per rank, the last one short.  ValueError for a split that
+    would leave a rank without a class (R = 8 over C = 9: Cs = 2, ranks 5..7 would be empty)."""
+    C, R, r = int(num_classes), int(world), int(rank)
+    if C < 1 or R < 1 or not 0 <= r < R:
+        raise ValueError('shard_range: num_classes %d, %d ranks, rank %d' % (C, R, r))
+    cs = (C + R - 1) // R
+    if (R - 1) * cs >= C:
+        raise ValueError('%d classes over %d ranks is %d per rank, which leaves rank %d without a class' % (C, R, cs, (C + cs - 1) // cs))
+    return r * cs, min(C, (r + 1) * cs)
+
+
+def shard_ld(num_classes, world):
+    """columns every rank stores: Cs rounded up to 128 (cpad's rule), the same on all ranks"""
+    cs = (int(num_classes) + int(world) - 1) // int(world)
+    return (cs + 127) // 128 * 128
+
+
+def check_sharding(head, sample_rate=None, sync_sample=False, sub_centers=1, what='the head'):
+    """what the sharded classifier composes with: the dense K = 1 ArcFace / CosFace head.  ValueError names the reason."""
+    if head not in ('arcface', 'cosface'):
+        raise ValueError('shard_classes needs an ArcFace / CosFace head: %s has %r' % (what, head))
+    if sample_rate is not None and float(sample_rate) < 1.0:
+        raise ValueError('shard_classes does not compose with the class sampler (sample_rate %g < 1): sampling inside each shard is '
+                         'not built yet' % float(sample_rate))
+    if sync_sample:
+        raise ValueError('shard_classes does not compose with sync_sample: the shared sample is the data-parallel form of the head')
+    if int(sub_centers) > 1:
+        raise ValueError('shard_classes does not compose with sub_centers = %d > 1: not built yet' % int(sub_centers))
+
+
+def shard_buffers(b, n, d, world, device):
+    """The gather buffers of the sharded head for a local batch of n rows, made once per batch size: b.X [N, d] and b.Y [N] (the
+    global batch in rank order), b.shard_stats [3, N], b.all_stats [R, 3, N], b.dX_part [N, d]."""
+    N = world * n
+    if getattr(b, 'X', None) is not None and b.X.shape == (N, d) and b.all_stats.shape[0] == world:
+        return
+    f32 = dict(dtype=torch.float32, device=device)
+    b.X, b.Y = torch.empty(N, d, **f32), torch.empty(N, dtype=torch.int32, device=device)
+    b.shard_stats, b.all_stats = torch.empty(3, N, **f32), torch.empty(world, 3, N, **f32)
+    b.dX_part = torch.empty(N, d, **f32)
+
+
+def sharded_margin_forward(b, x, W, s, labels, logits, head, n, d, class_lo, c, ld, num_classes, comm, grad_scale, ws, wsb, st):
+    """The head of one rank that owns classes class_lo .. class_lo + c as the columns W [d, ld]: x [n, d] and the GLOBAL labels [n]
+    of this rank's rows are all-gathered into b.X / b.Y (shard_buffers), s [N, ld] = X W, the per-shard statistics, ONE all-gather
+    of the [3, N] block, then the gradient kernel and colcoef.  `head` is describe()'s (name, S, m, m3).  Leaves the shard's margin
+    logits in `logits` [N, ld] (None: not wanted), the loss of every row of the global batch in b.loss_rows [N] (the same bits on
+    every rank), G [N, ld] in b.G, b.rowcoef [N] = this shard's share and b.colcoef [ld], complete.  b.xn / b.loss_rows / b.rowcoef
+    are N long, b.wn / b.colcoef ld."""
+    call = _lib.call
+    R = comm.world_size()
+    N = R * n
+    S, m, m3 = head[1:4]
+    comm.all_gather(b.X, x)
+    comm.all_gather(b.Y, labels)
+    call('fte_row_norms', b.X, b.xn, N, d, d, st)
+    call('fte_col_norms', W, b.wn, d, c, ld, st)
+    call('fte_gemm_nn', b.X, W, None, s, N, ld, d, ws, wsb, st)
+    call('fte_margin_shard_stats', s, b.xn, b.wn, b.Y, class_lo, num_classes, S, m, m3, b.shard_stats, N, c, ld, st)
+    comm.all_gather(b.all_stats, b.shard_stats)
+    call('fte_margin_shard_fwd_bwd', s, b.xn, b.wn, b.Y, class_lo, num_classes, S, m, m3, b.all_stats, R, logits, b.loss_rows, b.G,
+         b.rowcoef, N, c, ld, grad_scale, st)
+    call('fte_asoftmax_colcoef', b.G, s, b.wn, b.colcoef, N, c, ld, st)
+
+
+def sharded_classifier_dw(b, W, dW, n, d, ld, ws, wsb, st):
+    """dW_r [d, ld] = X^T G + colcoef (.) W_r over the N = R n gathered rows: final on the owning rank, never all-reduced"""
+    classifier_dw(b, b.X, W, dW, b.X.shape[0], d, ld, ws, wsb, st)
+
+
+def sharded_classifier_dx(b, W, dx, n, d, ld, comm, ws, wsb, st):
+    """dx [n, d] of this rank's rows: dX_part = G W_r^T + rowcoef_part (.) X over all N rows, then a sum reduce-scatter"""
+    classifier_dx(b, b.X, W, b.dX_part, b.X.shape[0], d, ld, ws, wsb, st)
+    comm.reduce_scatter_sum(dx, b.dX_part)
+
+
 def classifier_dw(b, x, W, dW, n, d, ld, ws, wsb, st, norm=True):
     """dW [d, ld] = x^T G (+ colcoef (.) W on the same stream; norm=False: the plain softmax / focal heads, which share the product)"""
     _lib.call('fte_gemm_tn', x, b.G, dW, n, ld, d, ws, wsb, st)

@@ -120,6 +120,37 @@ def additive_margin_loss(features, weights, labels, scale=64.0, margin=0.5, marg
     return _head_run(_head_scratch(features, n, d, ld), features, weights, dw, labels, head, n, d, c, ld) + (dw,)
 
 
+def sharded_margin_loss(features, weights_shard, labels, class_lo, num_classes, comm, scale=64.0, margin=0.5, margin_cos=0.0):
+    """additive_margin_loss with the classifier split by class over the ranks of `comm` (fte.h "Sharded margin head"): this rank
+    holds weights_shard [D, ld], the columns of classes class_lo .. (heads.shard_range gives the range of a rank; columns past the
+    range's length are padding), features [n, D] and labels [n] are this rank's rows of the global batch and the labels are GLOBAL
+    class ids.  Does the all-gathers and the reduce-scatter itself: `comm` has world_size / rank / all_gather / reduce_scatter_sum
+    (data_parallel._HostComm).  Every rank must call it.
+    -> (loss [0-d] = the mean over the GLOBAL batch, the same on every rank, dfeatures [n, D], dweights_shard [D, ld]): the exact
+    gradient of that mean; dweights_shard is final on this rank, it is not to be all-reduced."""
+    features, labels = _check(features, torch.float32, 'features'), _check(labels, torch.int32, 'labels')
+    W = _check(weights_shard, torch.float32, 'weights_shard')
+    n, d = features.shape
+    ld = W.shape[1]
+    R, C = comm.world_size(), int(num_classes)
+    lo, hi = heads.shard_range(C, R, comm.rank())
+    if int(class_lo) != lo:
+        raise ValueError('rank %d of %d owns classes [%d, %d) of %d, not a shard that starts at %d' % (comm.rank(), R, lo, hi, C, class_lo))
+    c = hi - lo
+    if W.shape[0] != d or labels.shape != (n,) or ld < c:
+        raise ValueError('features [n, D], weights_shard [D, ld >= %d] and labels [n] do not fit: %s %s %s'
+                         % (c, tuple(features.shape), tuple(W.shape), tuple(labels.shape)))
+    N = R * n
+    b = _head_scratch(features, N, d, ld)
+    heads.shard_buffers(b, n, d, R, features.device)
+    dW, dx = torch.empty_like(W), torch.empty_like(features)
+    head = ('arcface', float(scale), float(margin), float(margin_cos))
+    heads.sharded_margin_forward(b, features, W, b.s, labels, None, head, n, d, lo, c, ld, C, comm, 1.0 / N, b.ws, b.wsb, b.st)
+    heads.sharded_classifier_dw(b, W, dW, n, d, ld, b.ws, b.wsb, b.st)
+    heads.sharded_classifier_dx(b, W, dx, n, d, ld, comm, b.ws, b.wsb, b.st)
+    return _scaled_sum(b.loss_rows, 1.0 / N), dx, dW
+
+
 def subcenter_margin_loss(features, weights, labels, K, scale=64.0, margin=0.5, margin_cos=0.0, num_classes=None):
     """additive_margin_loss with K centres per class (sub-center ArcFace, Deng et al. 2020): the class cosine is the max over its K
     centres, the lowest k on a tie, and only the winning centre of a (row, class) pair takes its gradient; the contract is fte.h's

@@ -153,7 +153,7 @@ class SphereNet(Network):
         big.append((self.fc_w, 'fc_w', (self.fin, EMBED), self.fin * EMBED))
         # K centres per class: K planes of cpad columns, centre k of class j at column k * cpad + j; the reference layout packs them
         K = self.sub_centers
-        big.append((self.cls_w, 'cls_w', (EMBED, K * self.num_classes), EMBED * K * self.cpad))
+        big.append((self.cls_w, 'cls_w', (EMBED, K * self.num_classes), EMBED * self._head_width_stored()))
         self.variables = OrderedDict()
         off = 0
         for nm, kind, shape, size in small + big:
@@ -204,7 +204,19 @@ class SphereNet(Network):
         K = self.sub_centers                              # every plane drawn on its own: identical planes would tie on every sample
         wc = torch.zeros(EMBED, K, self.cpad)
         wc[:, :, :self.num_classes] = (torch.randn(EMBED, K * self.num_classes, generator=g) * 0.001).reshape(EMBED, K, self.num_classes)
-        self.view(self.cls_w).copy_(wc.reshape(-1))
+        self.view(self.cls_w).copy_(self._stored_columns(wc).reshape(-1))
+
+    def _head_width_stored(self):
+        """columns of the classifier the arena holds: every plane, padded"""
+        return self.sub_centers * self.cpad
+
+    def _stored_columns(self, wc):
+        """what the arena keeps of the dense classifier wc [EMBED, K, cpad]: all of it"""
+        return wc
+
+    def _head_rows(self, n):
+        """rows of the head's buffers for a batch of n images: its own rows"""
+        return n
 
     # ---- reference-layout import / export ----------------------------------------------
     def _fc_perm(self, t, to_internal):
@@ -278,9 +290,10 @@ class SphereNet(Network):
         self.y16 = None                                   # allocated on first use (_alloc_copies)
         self.emb = torch.empty(n, EMBED, **f32)
         hw = self._head_width()                           # cpad; the sampled-class head: its Spad columns
-        self.s_raw, self.G = torch.empty(n, hw, **f32), torch.empty(n, hw, **f32)
-        self.logits_buf = torch.empty(n, hw // self.sub_centers, **f32) if self.head == 'asoftmax' or self.head in NORMALISED_HEADS else self.s_raw
-        self.loss_rows, self.xn, self.rowcoef = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32)
+        hn = self._head_rows(n)                           # n; the sharded head: the global batch
+        self.s_raw, self.G = torch.empty(hn, hw, **f32), torch.empty(hn, hw, **f32)
+        self.logits_buf = torch.empty(hn, hw // self.sub_centers, **f32) if self.head == 'asoftmax' or self.head in NORMALISED_HEADS else self.s_raw
+        self.loss_rows, self.xn, self.rowcoef = torch.empty(hn, **f32), torch.empty(hn, **f32), torch.empty(hn, **f32)
         self.wn, self.colcoef = torch.empty(hw, **f32), torch.empty(hw, **f32)
         self.demb = torch.empty(n, EMBED, **f32)
 
@@ -326,7 +339,7 @@ class SphereNet(Network):
                        q('fte_conv3x3_dgrad_ws_bytes', n, c.hin, c.win, c.cin, c.cout, c.stride))
         c0 = self.convs[0]
         need = max(need, q('fte_conv3x3_first_wgrad_ws_bytes', n, c0.hin, c0.win, c0.cin, c0.cout, c0.stride),
-                   q('fte_gemm_ws_bytes', n, EMBED, self.fin), q('fte_gemm_ws_bytes', n, self._head_width(), EMBED))
+                   q('fte_gemm_ws_bytes', n, EMBED, self.fin), q('fte_gemm_ws_bytes', self._head_rows(n), self._head_width(), EMBED))
         self.ws = torch.empty((need + 3) // 4 + 1024, dtype=torch.float32, device=self.device)
         self.ws_bytes = self.ws.numel() * 4
         self._alloc_side()
@@ -823,10 +836,111 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         # the sampled-class head under data parallelism and its compact classifier update; the dense head ignores both
         self.sample_comm = None           # set by DataParallel(sync_sample=True): the ranks all-gather their labels, one sample for all
         self.compact_head_update = False  # True: no dense classifier gradient; the wrapper ends the step with apply_compact_update
+        # the classifier split by class over the ranks (fte.h "Sharded margin head"): set by
+        # DataParallel(shard_classes=True) BEFORE build(); this rank then holds only its own [D, ld_r] columns
+        self.shard_comm = None
         self.set_sample_rate(sample_rate, sample_seed)
 
     def _head_spec(self):
         return heads.describe(self)
+
+    # ---- the sharded classifier --------------------------------------------------------------------------------------------------
+    def build(self, height, width, channels, num_classes, device='cuda'):
+        self.shard = None                                 # (lo, hi): the classes this rank owns
+        if self.shard_comm is not None:
+            heads.check_sharding(self.head, self.sample_rate, self.sample_comm is not None, self.sub_centers, self.name)
+            R = self.shard_comm.world_size()
+            self.shard = heads.shard_range(num_classes, R, self.shard_comm.rank())
+            self.shard_cols = heads.shard_ld(num_classes, R)      # from Cs: the arena has the same size on every rank
+        return super(SphereNetAdditiveMargin, self).build(height, width, channels, num_classes, device)
+
+    def _sharded(self):
+        if self.shard_comm is not None and getattr(self, 'shard', None) is None:
+            raise ValueError('%s was already built with the dense classifier: shard_comm must be set before build()' % self.name)
+        return self.shard_comm is not None
+
+    def _head_width_stored(self):
+        return self.shard_cols if self.shard is not None else super(SphereNetAdditiveMargin, self)._head_width_stored()
+
+    def _stored_columns(self, wc):
+        # the dense classifier is drawn from the seed on every rank and the rank keeps its own columns: a sharded net starts from the
+        # dense net's values
+        if self.shard is None:
+            return wc
+        lo, hi = self.shard
+        own = torch.zeros(EMBED, self.shard_cols)
+        own[:, :hi - lo] = wc[:, 0, lo:hi]
+        return own
+
+    def _head_rows(self, n):
+        return n * self.shard_comm.world_size() if self.shard is not None else n
+
+    def get_variable(self, name, arena=None):
+        """The classifier (or its gradient / slot) of a sharded net comes back DENSE, [512, C], the shards side by side bit for bit: a
+        COLLECTIVE (one all-gather) that every rank must enter."""
+        if self.shard is None or name != self.cls_w:
+            return super(SphereNetAdditiveMargin, self).get_variable(name, arena)
+        R, ld = self.shard_comm.world_size(), self.shard_cols
+        every = torch.empty(R, EMBED, ld, dtype=torch.float32, device=self.device)
+        self.shard_comm.all_gather(every, self.view(name, arena).reshape(EMBED, ld))
+        ranges = [heads.shard_range(self.num_classes, R, r) for r in range(R)]
+        return torch.cat([every[r, :, :hi - lo] for r, (lo, hi) in enumerate(ranges)], dim=1)
+
+    def set_variable(self, name, value, arena=None):
+        """a dense [512, C] classifier value: the rank keeps its own columns (no collective)"""
+        if self.shard is None or name != self.cls_w:
+            return super(SphereNetAdditiveMargin, self).set_variable(name, value, arena)
+        t = torch.as_tensor(value, dtype=torch.float32).to(self.device)
+        assert tuple(t.shape) == self.variables[name].ref_shape, (name, tuple(t.shape), self.variables[name].ref_shape)
+        lo, hi = self.shard
+        buf = torch.zeros(EMBED, self.shard_cols, device=self.device)
+        buf[:, :hi - lo] = t[:, lo:hi]
+        self.view(name, arena).copy_(buf.reshape(-1))
+
+    def _alloc_head(self, n):
+        if self.shard is not None:
+            heads.shard_buffers(self, n, EMBED, self.shard_comm.world_size(), self.device)
+            return
+        self._alloc_sampler(n)
+
+    def forward(self, images, labels=None, num_classes=None, is_training=True):
+        if not is_training or self.shard_comm is None:
+            return super(SphereNetAdditiveMargin, self).forward(images, labels, num_classes, is_training)
+        assert num_classes is not None, 'num_classes must be given when is_training=True'
+        assert labels is not None, 'margin nets take labels in forward (data_parallel.py:220)'
+        self._ensure_built(images, num_classes)
+        self._sharded()
+        n = images.shape[0]
+        labels = heads.check_labels(labels)
+        self._labels = labels
+        st = _stream()
+        self.backbone(images, is_training=True)
+        W, _, c, ld = self._head_cols()
+        N = self._head_rows(n)
+        # grad_scale = 1 / N: what tower_scale / n summed over the ranks gives the dense head
+        heads.sharded_margin_forward(self, self.emb, W, self.s_raw, labels, self.logits_buf, self._head_spec(), n, EMBED, self.shard[0], c, ld,
+                                     self.num_classes, self.shard_comm, 1.0 / N, self.ws, self.ws_bytes, st)
+        return {'logits': self.logits_buf[:, :c]}           # this rank's [N, c_r] block
+
+    def _finish_losses(self, n):
+        if self.shard is None:
+            return super(SphereNetAdditiveMargin, self)._finish_losses(n)
+        # the slots are summed over the ranks: cross_entropy is the mean over the GLOBAL batch, the same bits on every rank, times
+        # tower_scale = 1 / R; reg_loss counts the backbone once (its share times tower_scale) and this rank's classifier columns whole
+        st, N, call = _stream(), self._head_rows(n), _lib.call
+        call('fte_sum', self.loss_rows, N, self.tower_scale / N, self.loss_slots[0:1], self.ws, self.ws_bytes, st)
+        half = 0.5 * self.weight_decay
+        call('fte_sumsq', self.params[self.small_end:self.cls_start], self.cls_start - self.small_end, half * self.tower_scale,
+             self.loss_slots[1:2], self.ws, self.ws_bytes, st)
+        call('fte_sumsq', self.params[self.cls_start:], self.arena_size - self.cls_start, half, self.loss_slots[2:3], self.ws, self.ws_bytes, st)
+        call('fte_axpby', 1.0, self.loss_slots[1:2], 1.0, self.loss_slots[2:3], self.loss_slots[1:2], 1, st)
+
+    def _head_backward(self, n, st):
+        if self.shard is None:
+            return super(SphereNetAdditiveMargin, self)._head_backward(n, st)
+        W, dW, _, ld = self._head_cols()
+        heads.sharded_classifier_dw(self, W, dW, n, EMBED, ld, self.ws, self.ws_bytes, st)       # final: never all-reduced
+        heads.sharded_classifier_dx(self, W, self.demb, n, EMBED, ld, self.shard_comm, self.ws, self.ws_bytes, st)
 
     # ---- the sampled-class head (Partial FC; fte.h "Partial FC", DESIGN.md 4.13) -----------------------------------------------
     def set_sample_rate(self, rate, seed=0):
@@ -845,9 +959,11 @@ class SphereNetAdditiveMargin(SphereNetMargin):
         return sample_size(self.num_classes, self.sample_rate)
 
     def _head_width(self):
+        if getattr(self, 'shard', None) is not None:
+            return self.shard_cols
         return self.sub_centers * self.cpad if self.sample_rate is None else (self.sample_size + 63) // 64 * 64
 
-    def _alloc_head(self, n):
+    def _alloc_sampler(self, n):
         if self.sample_rate is None:
             return
         S, spad = self.sample_size, self._head_width()
@@ -883,6 +999,8 @@ class SphereNetAdditiveMargin(SphereNetMargin):
 
     def _head_cols(self):
         """the sampled head is the dense head on its S gathered columns and their compact gradient"""
+        if getattr(self, 'shard', None) is not None:        # the rank's own columns, in the arenas
+            return self.view(self.cls_w), self.view(self.cls_w, self.grads), self.shard[1] - self.shard[0], self.shard_cols
         if self.sample_rate is None:
             return super(SphereNetAdditiveMargin, self)._head_cols()
         return self.Ws, self.dWs, self.sample_size, self._head_width()
@@ -911,6 +1029,9 @@ class SphereNetAdditiveMargin(SphereNetMargin):
 
     def grad_buckets(self):
         buckets = super(SphereNetAdditiveMargin, self).grad_buckets()
+        if getattr(self, 'shard', None) is not None:
+            # the classifier gradient is final on its rank: the head bucket is the FC range, the four loss slots travel on their own
+            buckets[0] = (self.fc_start, self.cls_start)
         if self.compact_active():
             # the head bucket shrinks to the FC range: the classifier gradient travels as compact_grad(), the four loss slots behind the
             # arena in an all-reduce of their own (data_parallel.py)

@@ -35,8 +35,12 @@ def _state_names(model):
     return list(getattr(model, 'state', None) or {})
 
 
-def save(model, optimizer_slots, global_step, path_prefix):
-    """path_prefix like models/<net>_<model>/<net>_<model>.ckpt ; writes <prefix>-<step>."""
+def save(model, optimizer_slots, global_step, path_prefix, write=True):
+    """path_prefix like models/<net>_<model>/<net>_<model>.ckpt ; writes <prefix>-<step>.
+    A net whose classifier is split over the ranks (nets/sphere.py shard_comm) is saved DENSE: `classifier/fc_classifier/weights` and
+    every optimizer slot of it as [512, C], the shards side by side bit for bit -- a dense net restores the file and the other way
+    round.  Putting them together is a collective inside model.get_variable, so EVERY rank must call save() at a save step; the ranks
+    that pass write=False take part in it and write nothing."""
     ckpt_dir = os.path.dirname(path_prefix)
     os.makedirs(ckpt_dir, exist_ok=True)
     path = '%s-%d' % (path_prefix, global_step)
@@ -47,6 +51,8 @@ def save(model, optimizer_slots, global_step, path_prefix):
         state['variables'][name] = model.get_variable(name).cpu()
     for slot in optimizer_slots or []:
         state['slots'].append({name: model.get_variable(name, slot).cpu() for name in model.variables})
+    if not write:
+        return path
     torch.save(state, path)
     # index + retention
     kept = [path]

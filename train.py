@@ -86,10 +86,32 @@ def build_parser():
                         help='SphereNet-ArcFace / -CosFace, ResNet-50-arcface / -cosface: K centres per class (sub-center ArcFace), 1..8; the class '
                              'logit is the max cosine over its centres.  1 (default) = one centre, the head as it always was.  Not with '
                              '--sample_rate < 1.  subcenter_clean.py reduces a trained K-centre model to K = 1 and cleans the list.')
+    parser.add_argument('--shard_classes', type=int, default=0,
+                        help='SphereNet-ArcFace / SphereNet-CosFace under --num_gpus > 1: 1 = the classifier is split by class over the ranks '
+                             '(model-parallel head): rank r holds C / num_gpus columns with their optimizer slots, the features of the global '
+                             'batch are all-gathered, the classifier gradient is never all-reduced and the checkpoints stay dense.  Not with '
+                             '--sample_rate < 1, --sync_sample 1 or --sub_centers > 1.  0 (default) = every rank holds the whole classifier.')
     return parser
 
 
 SAMPLED_NETS = ('SphereNet-ArcFace', 'SphereNet-CosFace')
+
+
+def shard_flags_check(FLAGS):
+    """--shard_classes: refuse what the sharded classifier does not do, before anything is built or communicated"""
+    if not getattr(FLAGS, 'shard_classes', 0):
+        return
+    if FLAGS.num_gpus < 2:
+        raise SystemExit('--shard_classes 1 splits the classifier over the ranks: it needs --num_gpus > 1 (got %d)' % FLAGS.num_gpus)
+    if FLAGS.net_name not in SAMPLED_NETS:
+        raise SystemExit('--shard_classes 1: only %s have a sharded classifier, not %s' % (' / '.join(SAMPLED_NETS), FLAGS.net_name))
+    from tf_face_toolbox_amd import heads
+    try:
+        heads.check_sharding('arcface', FLAGS.sample_rate, bool(FLAGS.sync_sample), FLAGS.sub_centers, FLAGS.net_name)
+        if FLAGS.synthetic:                               # (a list's class count is known once it is read: the wrapper refuses there)
+            heads.shard_range(FLAGS.synthetic_classes, FLAGS.num_gpus, 0)
+    except ValueError as e:
+        raise SystemExit('--shard_classes 1: %s' % e)
 
 
 def sample_flags_check(FLAGS):
@@ -227,7 +249,8 @@ def train(FLAGS):
         lr = lr_config(FLAGS, FLAGS.lr_decay_method, batches_per_epoch)                              # train.py:176
         if FLAGS.num_gpus > 1:                                                                        # train.py:178-183
             model = DataParallel_margin(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay, num_gpus=FLAGS.num_gpus,
-                                        sync_centers=bool(FLAGS.sync_centers), sync_sample=bool(FLAGS.sync_sample))
+                                        sync_centers=bool(FLAGS.sync_centers), sync_sample=bool(FLAGS.sync_sample),
+                                        shard_classes=bool(FLAGS.shard_classes))
         else:
             model = Singular(network, lr, optimizer=FLAGS.optimizer, weight_decay=FLAGS.weight_decay)
         compact = FLAGS.sample_rate < 1.0 and bool(FLAGS.compact_head_update or (FLAGS.sync_sample and FLAGS.num_gpus > 1))
@@ -241,6 +264,11 @@ def train(FLAGS):
                 print('Sampled-class head mode: %s, compact classifier update (no dense classifier gradient)'
                       % ('one shared sample over %d ranks' % FLAGS.num_gpus if FLAGS.num_gpus > 1 else 'one GPU'))
 
+        if FLAGS.shard_classes:
+            per_rank = (network.num_classes + world - 1) // world
+            print('classifier: %d shards of %s classes (%s in all; rank %d holds classes %d..%d)'
+                  % (world, format(per_rank, ','), format(network.num_classes, ','), rank, network.shard[0], network.shard[1] - 1))
+
         tag = FLAGS.net_name + '_' + FLAGS.model_name
         ckpt_dir = os.path.join(FLAGS.model_dir, tag)
         latest = saver.latest_checkpoint(ckpt_dir)                                                    # train.py:207-215
@@ -253,7 +281,7 @@ def train(FLAGS):
         else:
             print('Network parameters initialized from scratch.')
         if world > 1:
-            model.comm.broadcast(network.params, src=0)
+            model.comm.broadcast(model.replicated_params(), src=0)      # (a sharded classifier: every rank read its own columns)
 
         print('%s training start...' % tag)
         step, epoch = 0, 1
@@ -284,9 +312,12 @@ def train(FLAGS):
                 time_sim += duration
                 image_sim += batch_size / duration
             last = step == FLAGS.max_epoches * batches_per_epoch or (FLAGS.max_steps > 0 and step + 1 >= FLAGS.max_steps)
-            if ((step > 0 and step % FLAGS.save_interval == 0) or last) and rank == 0:
-                path = saver.save(network, model._opt.slots, model.global_step, os.path.join(ckpt_dir, tag + '.ckpt'))
-                print('[%s]: Model has been saved in Iteration %d (%s)' % (datetime.now(), step, path))
+            # a sharded classifier is saved dense: putting it together is a collective, so EVERY rank enters save() at a save step (the
+            # condition depends on the step alone) and rank 0 writes the file
+            if ((step > 0 and step % FLAGS.save_interval == 0) or last) and (rank == 0 or FLAGS.shard_classes):
+                path = saver.save(network, model._opt.slots, model.global_step, os.path.join(ckpt_dir, tag + '.ckpt'), write=rank == 0)
+                if rank == 0:
+                    print('[%s]: Model has been saved in Iteration %d (%s)' % (datetime.now(), step, path))
             if FLAGS.max_steps > 0 and step + 1 >= FLAGS.max_steps:
                 break
         if rank == 0 and step > 0:
@@ -317,6 +348,7 @@ def train(FLAGS):
 def main(argv=None):
     FLAGS = build_parser().parse_args(argv)
     FLAGS_assertion(FLAGS)
+    shard_flags_check(FLAGS)
     sample_flags_check(FLAGS)
     sub_centers_flags_check(FLAGS)
     os.makedirs(os.path.join(FLAGS.train_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
