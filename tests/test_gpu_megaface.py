@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import megaface_ref as mr
+from search_cases import exact_rows
 import verify_ref as vr
 
 pytestmark = pytest.mark.gpu
@@ -27,10 +28,7 @@ def _stream():
 
 def _exact_rows(rng, n, d=64):
     """16 entries of +-0.25 per row: norm exactly 1, every dot product an exact multiple of 1/16 in fp32 (many ties)"""
-    x = np.zeros((n, d), np.float32)
-    for i in range(n):
-        x[i, rng.choice(d, 16, replace=False)] = rng.choice([-0.25, 0.25], 16)
-    return x
+    return exact_rows(rng, n, d)
 
 
 def _clustered_exact(rng, ids, per, d=64):
