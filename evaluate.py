@@ -57,9 +57,10 @@ def evaluate(FLAGS):
         del state
         model = net_select(FLAGS.net_name, FLAGS.data_format)
         model.build(FLAGS.input_height, FLAGS.input_width, 3 if FLAGS.is_color else 1, ncls, device)
-        # the AdaFace head's running norm statistics belong to the training head: the extractor neither reads nor needs them (a
-        # checkpoint of the same backbone without them restores too)
-        names = [k for k in list(model.variables) + saver._state_names(model) if not k.startswith('classifier/adaface/')]
+        # the AdaFace head's running norm statistics and CurricularFace's t belong to the training head: the extractor neither reads
+        # nor needs them (a checkpoint of the same backbone without them restores too)
+        names = [k for k in list(model.variables) + saver._state_names(model)
+                 if not k.startswith(('classifier/adaface/', 'classifier/curricularface/'))]
         saver.restore(model, latest, only=names)
         step = str(saver.step_of(latest))
         print('Extracting features from model saved in iteration %s...' % step)

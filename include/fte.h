@@ -759,6 +759,30 @@ int fte_margin_softmax_rows_fwd_bwd(const float* s, const float* xn, const float
  * FTE_EINVAL: a null pointer, n < 2, m < 0, h <= 0, t_alpha outside [0, 1] (or any of them NaN). */
 int fte_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats,
                         float* a_rows, float* b_rows, void* stream);
+/* CurricularFace (Huang et al., CVPR 2020): ArcFace's target column, and the NEGATIVE columns whose cosine exceeds the margined
+ * target cosine are re-weighted by a running mean t of the batch's target cosines; DESIGN.md 4.21.  c_ij, eps, the clamp (identity
+ * derivative, NaN stays NaN), loss_rows, rowcoef, the optional f, columns c..ld-1 and the NaN row of an out-of-range label are
+ * those of fte_margin_softmax_fwd_bwd.  With c = c_iy, sin_t = sqrt(max((1 - c)(1 + c), 0)):
+ *   u_i = c cos m - sin_t sin m                               (the mask threshold, on both sides of the fallback below)
+ *   target:  c > -cos m:  z_iy = S u_i,              t' = cos m + sin m * c / max(sin_t, 1e-6)
+ *            otherwise:   z_iy = S (c - m sin m),    t' = 1                        (the target column of fte_margin_softmax_fwd_bwd, m3 = 0)
+ *   j != y:  c_ij > u_i (HARD; strict, a NaN is never hard):  z_ij = S c_ij (t + c_ij),  dz/dc = S (t + 2 c_ij)
+ *            otherwise:                                       z_ij = S c_ij,             dz/dc = S
+ *   G_ij = grad_scale * (p_ij - [j = y]) * (dz/dc)_ij / (max(xn_i, eps) * wn_j);  the mask and t are constants of the gradient.
+ * The logit is DISCONTINUOUS in c_ij at c_ij = u_i: it jumps by S c (t + c - 1).
+ * t = t_used[0] is read on the device, once per block.  colcoef is the unchanged fte_asoftmax_colcoef.  Preset: S = 64, m = 0.5.
+ *
+ * fte_curricular_t -- before the logits:  c_iy as above over the rows with 0 <= labels[i] < c (V of them);
+ *   update != 0 and V > 0:  t_used[0] = t_state[0] = alpha * (sum c_iy / V) + (1 - alpha) * t_state[0]
+ *   otherwise:              t_used[0] = t_state[0], t_state is not written
+ * One block, sums in a fixed order, no float atomics, no host read-back: two calls on the same data write identical bytes.
+ * FTE_EINVAL (nothing is launched or written), both: a null pointer (f excepted), n < 1, c < 1, ld < c, scale <= 0, m outside
+ * [0, pi/2), alpha outside [0, 1] (or any of them NaN). */
+int fte_curricular_t(const float* s, const float* xn, const float* wn, const int32_t* labels, float alpha, int update,
+                     float* t_state, float* t_used, int n, int c, int ld, void* stream);
+int fte_curricular_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
+                                   const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef,
+                                   int n, int c, int ld, float grad_scale, void* stream);
 /* Sub-center ArcFace (Deng et al., ECCV 2020): K centres per class, the class cosine the max over them; DESIGN.md 4.16.
  * LAYOUT -- planar: with ld the padded class count of ONE plane, the classifier W [d, K*ld], the raw product s = x @ W [n, K*ld],
  * G [n, K*ld], wn [K*ld] and colcoef [K*ld] hold centre k of class j at column k*ld + j; columns c..ld-1 of every plane are

@@ -832,6 +832,22 @@ int fte_adaface_margins(const float* xn, int n, float m, float h, float t_alpha,
     if (!xn || !stats || !a_rows || !b_rows || n < 2 || !(m >= 0.f) || !(h > 0.f) || !(t_alpha >= 0.f && t_alpha <= 1.f)) return FTE_EINVAL;
     return rc(k_adaface_margins(xn, n, m, h, t_alpha, update, stats, a_rows, b_rows, (hipStream_t)stream));
 }
+// S > 0, 0 <= m < pi/2, 0 <= alpha <= 1; a NaN fails every compare
+static bool curricular_ok(float scale, float m, float alpha) {
+    return scale > 0.f && m >= 0.f && m < 1.57079632679489661923f && alpha >= 0.f && alpha <= 1.f;
+}
+int fte_curricular_t(const float* s, const float* xn, const float* wn, const int32_t* labels, float alpha, int update, float* t_state,
+                     float* t_used, int n, int c, int ld, void* stream) {
+    if (!s || !xn || !wn || !labels || !t_state || !t_used || n <= 0 || c <= 0 || ld < c || !curricular_ok(1.f, 0.f, alpha)) return FTE_EINVAL;
+    return rc(k_curricular_t(s, xn, wn, labels, alpha, update, t_state, t_used, n, c, ld, (hipStream_t)stream));
+}
+int fte_curricular_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
+                                   const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld,
+                                   float grad_scale, void* stream) {
+    if (!s || !xn || !wn || !labels || !t_used || !loss_rows || !G || !rowcoef || n <= 0 || c <= 0 || ld < c || !curricular_ok(scale, m, 0.f))
+        return FTE_EINVAL;
+    return rc(k_curricular_softmax(s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
+}
 int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int n, int c, int ld, void* stream) {
     if (!G || !s || !wn || !colcoef || n <= 0 || c <= 0 || ld < c) return FTE_EINVAL;
     return rc(k_asoftmax_colcoef(G, s, wn, colcoef, n, c, ld, (hipStream_t)stream));

@@ -44,6 +44,12 @@ hipError_t k_subcenter_assign(const float* x, const float* wt, const int32_t* la
                               hipStream_t st);
 hipError_t k_adaface_margins(const float* xn, int n, float m, float h, float t_alpha, int update, float* stats, float* a_rows, float* b_rows,
                              hipStream_t st);
+// CurricularFace (fte.h): t from the batch's target cosines, then the margin softmax that re-weights the hard negatives by it
+hipError_t k_curricular_t(const float* s, const float* xn, const float* wn, const int32_t* labels, float alpha, int update, float* t_state,
+                          float* t_used, int n, int c, int ld, hipStream_t st);
+hipError_t k_curricular_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
+                                const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
+                                hipStream_t st);
 hipError_t k_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* cc, int n, int c, int ld, hipStream_t st);
 hipError_t k_row_norms(const float* a, float* out, int rows, int cols, int ld, hipStream_t st);
 hipError_t k_col_norms(const float* a, float* out, int rows, int cols, int ld, hipStream_t st);

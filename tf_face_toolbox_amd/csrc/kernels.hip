@@ -1047,6 +1047,199 @@ __global__ __launch_bounds__(256) void margin_softmax_rows_kernel(const float* _
     }
 }
 
+// CurricularFace (fte.h fte_curricular_softmax_fwd_bwd): ArcFace's target column, and a negative column whose cosine exceeds the
+// margined target cosine u_i (a HARD negative) gets the logit S c (t + c) instead of S c, derivative S (t + 2 c); t and the mask
+// are constants of the gradient.  The per-element work over margin_softmax_kernel's is one compare against u and one fma; pass 2
+// carries the derivative factor beside z.  t is one scalar load per block.  The two passes are margin_softmax_kernel's, statement
+// for statement; a kernel of its own for the reason given at margin_softmax_rows_kernel.
+struct CurricularRow {
+    float ix, S, zy, u, t;
+    int y;
+    // the logit of column j and d = (dz/dc) / S of a negative column (1, or t + 2c where the column is hard; NaN is never hard)
+    __device__ __forceinline__ float z(float sv, float wv, int j, float& r, float& d) const {
+        r = ix * __builtin_amdgcn_rcpf(wv);
+        const float cv = clamp1(sv * r);
+        const bool hard = cv > u;
+        d = hard ? t + 2.f * cv : 1.f;
+        return j == y ? zy : S * (hard ? cv * (t + cv) : cv);
+    }
+    __device__ __forceinline__ float z(float sv, float wv, int j) const {
+        float r, d;
+        return z(sv, wv, j, r, d);
+    }
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void curricular_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                 const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                 float S, float m, const float* __restrict__ t_used,
+                                                                 float* __restrict__ f, float* __restrict__ loss_rows,
+                                                                 float* __restrict__ G, float* __restrict__ rowcoef, int c, int ld,
+                                                                 float gscale) {
+    constexpr int U = 4;                                        // chunks in flight per thread and trip
+    constexpr float EPS = 1e-12f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * ld;
+    float* gr = G + (long)row * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const int yl = labels[row];
+    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
+    const int y = bad ? 0 : yl;
+    const float xr = xn[row];
+    CurricularRow R;
+    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
+    R.S = S;
+    R.y = y;
+    R.t = t_used[0];
+    // target term and mask threshold, once per row; u = cos(theta + m) on both sides of the fallback
+    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
+    const float cm = cosf(m), sm = sinf(m);
+    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+    R.u = cy * cm - st * sm;
+    float ty = cy, tp = 1.f;
+    if (m > 0.f) {
+        if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
+            ty = R.u;
+            tp = cm + sm * cy / fmaxf(st, 1e-6f);
+        } else {
+            ty = cy - m * sm;                                   // easy_margin = False fallback
+        }
+    }
+    R.zy = S * ty;
+
+    // pass 1: online max / sum of exp
+    float mx = -INFINITY, se = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < c; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    float z[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k) : -INFINITY;
+                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
+                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < c; j += 256) {
+            const float z = R.z(sr[j], wn[j], j);
+            if (z > mx) { se *= __expf(mx - z); mx = z; }
+            se += __expf(z - mx);
+        }
+    }
+    const float M = block_max(mx, sh);
+    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
+    const float inv = 1.f / se;
+    const float gS = gscale * S, gT = gscale * S * tp;
+
+    // pass 2: G (and f), sum of G * s
+    float acc = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < ld; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < ld) {
+                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
+                    if (j < c) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (j + k < c) {
+                                float r, d;
+                                const float z = R.z(sv[u][k], wv[u][k], j + k, r, d);
+                                const float p = __expf(z - M) * inv;
+                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS * d) * r;
+                                acc += g * sv[u][k];
+                                gv[k] = g;
+                                fv[k] = z;
+                            }
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(gr + j) = gv;
+                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < ld; j += 256) {
+            float g = 0.f, fv = 0.f;
+            if (j < c) {
+                float r, d;
+                const float sv = sr[j];
+                const float z = R.z(sv, wn[j], j, r, d);
+                const float p = __expf(z - M) * inv;
+                g = (j == y ? (p - 1.f) * gT : p * gS * d) * r;
+                acc += g * sv;
+                fv = z;
+            }
+            gr[j] = g;
+            if (fr) fr[j] = fv;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (t == 0) {
+        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
+        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
+    }
+}
+
+// CurricularFace's t (fte.h fte_curricular_t): the running mean of the batch's target cosines, blended before the logits are formed.
+// ONE block, built like adaface_margins_kernel: every thread gathers c_iy of its strided rows -- curricular_softmax_kernel's
+// expression, so both see the same bits -- and sums in index order; sum and count merge through block_sum in a fixed order (two
+// calls are bit-identical; the count is exact in fp32 below 2^24 rows).  Rows with an out-of-range label are left out of the mean.
+__global__ __launch_bounds__(256) void curricular_t_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                           const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                           float alpha, int update, float* __restrict__ t_state,
+                                                           float* __restrict__ t_used, int n, int c, int ld) {
+    constexpr float EPS = 1e-12f;
+    __shared__ float sh[4];
+    const int t = threadIdx.x;
+    float acc = 0.f, cnt = 0.f;
+    if (update) {
+        for (int i = t; i < n; i += 256) {
+            const int y = labels[i];
+            if ((unsigned)y < (unsigned)c) {
+                const float ix = 1.f / fmaxf(xn[i], EPS);
+                acc += clamp1(s[(long)i * ld + y] * (ix * __builtin_amdgcn_rcpf(wn[y])));
+                cnt += 1.f;
+            }
+        }
+    }
+    acc = block_sum(acc, sh);
+    cnt = block_sum(cnt, sh);
+    if (t == 0) {
+        const float t0 = t_state[0];
+        const float tn = update && cnt > 0.f ? alpha * (acc / cnt) + (1.f - alpha) * t0 : t0;
+        t_used[0] = tn;
+        if (update && cnt > 0.f) t_state[0] = tn;
+    }
+}
+
 // Sub-center head (fte.h fte_subcenter_margin_softmax_fwd_bwd): K centres per class in K planes of ld columns, centre k of class j
 // at column k * ld + j; s / G rows are K * ld wide, f rows ld.  The class cosine is the max over the K planes, the LOWEST k winning
 // a tie (strict > from plane 0 up; a NaN in plane 0 stays), and the two passes are margin_softmax_kernel's on the pooled cosine,
@@ -1873,6 +2066,19 @@ hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* w
     const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
     if (vec) hipLaunchKernelGGL(margin_softmax_rows_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(margin_softmax_rows_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_curricular_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
+                                const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
+                                hipStream_t st) {
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    if (vec) hipLaunchKernelGGL(curricular_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, c, ld, gs);
+    else hipLaunchKernelGGL(curricular_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_curricular_t(const float* s, const float* xn, const float* wn, const int32_t* labels, float alpha, int update, float* t_state,
+                          float* t_used, int n, int c, int ld, hipStream_t st) {
+    hipLaunchKernelGGL(curricular_t_kernel, dim3(1), dim3(256), 0, st, s, xn, wn, labels, alpha, update, t_state, t_used, n, c, ld);
     return hipGetLastError();
 }
 template <int K>

@@ -1,9 +1,10 @@
-"""The launch sequence of the heads on the normalised features and classifier columns (A-softmax, ArcFace / CosFace, AdaFace, the
-sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py (loss_function, backward_head) call it.
+"""The launch sequence of the heads on the normalised features and classifier columns (A-softmax, ArcFace / CosFace, AdaFace, CurricularFace,
+the sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py (loss_function, backward_head) call it.
 
 Plain functions over buffers the CALLER owns.  `b` is any object that carries them under the nets' attribute names -- a net itself, or
 the scratch namespace loss.py allocates per call: xn [n], wn [ld], rowcoef [n], colcoef [ld], G [n, ld], loss_rows [n]; for AdaFace
-also adaface_stats [2], a_rows [n], b_rows [n]; for the class sampler class_index [spad], class_inverse [c], sampled_labels [n],
+also adaface_stats [2], a_rows [n], b_rows [n]; for CurricularFace cf_state [1], cf_t [1]; for the class sampler class_index [spad],
+class_inverse [c], sampled_labels [n],
 Ws [d, spad]; with K > 1 centres per class (planar layout, fte.h "Sub-center ArcFace") wn, colcoef and the columns of G are K * ld.
 Nothing here allocates on a step (the sampler's all-gather pair is made once per batch size).  Every launch goes
 through `_lib.call`, looked up when it is made: the launch recorder and tests/step_audit.py swap it.
@@ -23,7 +24,10 @@ def check_labels(labels):
 
 def describe(net):
     """The head description margin_forward takes, from a margin net's attributes: ('adaface', S, m, h, t_alpha, update) -- the running
-    statistics move under the net's update_moving_stats -- or (head, S, m, m3) for 'arcface' / 'cosface'."""
+    statistics move under the net's update_moving_stats --, ('curricularface', S, m, alpha, update) -- t moves the same way -- or
+    (head, S, m, m3) for 'arcface' / 'cosface'."""
+    if net.head == 'curricularface':
+        return ('curricularface', net.margin_scale, net.margin, net.curricular_alpha, int(net.update_moving_stats))
     if net.head == 'adaface':
         return ('adaface', net.margin_scale, net.margin, net.adaface_h, net.adaface_t_alpha, int(net.update_moving_stats))
     K = int(getattr(net, 'sub_centers', 1))
@@ -71,6 +75,10 @@ def margin_forward(b, x, W, s, labels, logits, head, n, d, c, ld, grad_scale, st
         S, m, h, t_alpha, update = head[1:]
         call('fte_adaface_margins', b.xn, n, m, h, t_alpha, update, b.adaface_stats, b.a_rows, b.b_rows, st)
         call('fte_margin_softmax_rows_fwd_bwd', s, b.xn, b.wn, labels, S, b.a_rows, b.b_rows, *out)
+    elif head[0] == 'curricularface':    # t from the batch's target cosines, before the logits; then the softmax that re-weights by it
+        S, m, alpha, update = head[1:]
+        call('fte_curricular_t', s, b.xn, b.wn, labels, alpha, update, b.cf_state, b.cf_t, n, c, ld, st)
+        call('fte_curricular_softmax_fwd_bwd', s, b.xn, b.wn, labels, S, m, b.cf_t, *out)
     else:                                # (S, m, m3): ArcFace / CosFace
         call('fte_margin_softmax_fwd_bwd', s, b.xn, b.wn, labels, *(head[1:] + out))
     call('fte_asoftmax_colcoef', b.G, s, b.wn, b.colcoef, n, c, ld, st)

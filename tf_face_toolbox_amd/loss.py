@@ -192,6 +192,21 @@ def adaface_loss(features, weights, labels, stats, scale=64.0, margin=0.4, h=0.3
     return _head_run(b, features, weights, dw, labels, head, n, d, c, ld) + (dw,)
 
 
+def curricularface_loss(features, weights, labels, t, scale=64.0, margin=0.5, alpha=0.01, update=True, num_classes=None):
+    """CurricularFace (Huang et al., CVPR 2020): ArcFace's target logit, and every negative column whose cosine exceeds the margined
+    target cosine re-weighted by t + cos; the contract is fte.h's fte_curricular_t / fte_curricular_softmax_fwd_bwd.  `t` is the
+    float32 CUDA tensor [1] (the paper's code starts it at 0); with `update` it is moved in place towards the mean target cosine of
+    the batch (weight alpha) BEFORE the logits are formed, otherwise it is used as it stands and left alone.  The other arguments,
+    the shapes and the result (loss, dfeatures, dweights) are additive_margin_loss's; t and the mask enter the gradient as constants."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 1):
+        raise TypeError('t must be a contiguous float32 CUDA tensor of 1 element')
+    features, weights, labels, n, d, ld, c = _head_args(features, weights, labels, num_classes)
+    b = _head_scratch(features, n, d, ld, cf_state=t, cf_t=torch.empty(1, dtype=torch.float32, device=features.device))
+    dw = torch.empty_like(weights)
+    head = ('curricularface', float(scale), float(margin), float(alpha), int(bool(update)))
+    return _head_run(b, features, weights, dw, labels, head, n, d, c, ld) + (dw,)
+
+
 def sample_size(num_classes, sample_rate):
     """S = ceil(sample_rate * num_classes) of the sampled-class head (fte.h "Partial FC"); None or a rate of 1 = every class."""
     c = int(num_classes)

@@ -13,7 +13,8 @@ import torch
 
 from .. import _lib, heads
 from . import plan
-from .net_base import MARGIN_PRESETS, NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
+from .net_base import (MARGIN_PRESETS, NORMALISED_HEADS, Network, adaface_params, adaface_state, curricular_params, curricular_state,
+                       margin_params, side_stream)
 from .plan import shuffle_perm, stem_kpad          # noqa: F401 (shuffle_perm: the tests import it from here)
 from .sphere import Variable
 
@@ -80,7 +81,9 @@ class GraphNet(Network):
     fte_margin_softmax_fwd_bwd; (S, m, m3) in margin_scale / margin / margin_cos) and 'adaface' (the same head with the margin of
     each row set from the norm of the classifier's input against two running scalars, fte.h fte_adaface_margins /
     fte_margin_softmax_rows_fwd_bwd; (S, m) in margin_scale / margin, h / t_alpha in adaface_h / adaface_t_alpha; the scalars are
-    state like the BN moving statistics and move under the same switch, update_moving_stats)."""
+    state like the BN moving statistics and move under the same switch, update_moving_stats) and 'curricularface' (ArcFace's target
+    logit with the hard negatives re-weighted by the running scalar t, fte.h fte_curricular_t / fte_curricular_softmax_fwd_bwd; (S, m)
+    in margin_scale / margin, alpha in curricular_alpha; t is state under the same switch)."""
 
     head = 'softmax'
     channel_pad = 1
@@ -120,6 +123,11 @@ class GraphNet(Network):
             if margin_cos is not None:
                 raise ValueError('the adaface head has no margin_cos')
             self.margin_scale, self.margin, self.adaface_h, self.adaface_t_alpha = adaface_params(scale, margin)
+            self.margin_cos = 0.0
+        elif head == 'curricularface':
+            if margin_cos is not None:
+                raise ValueError('the curricularface head has no margin_cos')
+            self.margin_scale, self.margin, self.curricular_alpha = curricular_params(scale, margin)
             self.margin_cos = 0.0
         elif (scale, margin, margin_cos) != (None, None, None):
             raise ValueError('scale / margin / margin_cos belong to the arcface / cosface heads, not %r' % head)
@@ -189,6 +197,9 @@ class GraphNet(Network):
                 self.state_ref[pre + '/moving_mean'] = self.state_ref[pre + '/moving_variance'] = s[0]
         if self.head == 'adaface':                        # the head's running norm statistics: two more non-trainable variables
             self.adaface_stats, extra = adaface_state(dev)
+            self.state.update(extra)
+        if self.head == 'curricularface':                 # t, the running mean of the target cosines: one more non-trainable variable
+            self.cf_state, extra = curricular_state(dev)
             self.state.update(extra)
         self._init_params()
         self.built = True
@@ -402,6 +413,8 @@ class GraphNet(Network):
             self.wn, self.colcoef = (torch.empty(self.sub_centers * self.cpad, **f32) for _ in range(2))
         if self.head == 'adaface':
             self.a_rows, self.b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
+        if self.head == 'curricularface':
+            self.cf_t = torch.empty(1, **f32)
         need = max(w.need, 4 * n * fdim, 12 * n * n)
         self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
         self.ws_bytes = self.ws.numel() * 4
@@ -1366,7 +1379,7 @@ class GraphNet(Network):
                 call('fte_focal_loss_fwd_bwd', self.t['logits'], labels, self.loss_rows, self.G, n,
                      self.num_classes, self.cpad, self.focal_gamma, self.focal_alpha, self.tower_scale / n, st)
             elif self.head in NORMALISED_HEADS:              # the margin on the raw classifier output; backward_head adds the norm terms
-                op = self.plan[-1]                           # (the running statistics of AdaFace move with BN's: heads.describe)
+                op = self.plan[-1]                           # (the running statistics of AdaFace and CurricularFace's t move with BN's: heads.describe)
                 heads.margin_forward(self, self.t[op.inp], self.view(op.wname), self.t['logits'], labels, None, heads.describe(self), n,
                                      self.shapes[op.inp][0], self.num_classes, self.cpad, self.tower_scale / n, st)
             else:

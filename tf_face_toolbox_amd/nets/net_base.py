@@ -32,7 +32,11 @@ ADAFACE_PRESET = (64.0, 0.4, 0.333, 0.01)
 ADAFACE_STATS_INIT = (20.0, 100.0)
 ADAFACE_STATE = ('classifier/adaface/batch_mean', 'classifier/adaface/batch_std')
 # heads on the normalised embedding and classifier columns: xn / wn / rowcoef / colcoef buffers and the norm-correction backward
-NORMALISED_HEADS = tuple(MARGIN_PRESETS) + ('adaface',)
+NORMALISED_HEADS = tuple(MARGIN_PRESETS) + ('adaface', 'curricularface')
+# CurricularFace (Huang et al. 2020: s = 64, m = 0.5, alpha = 0.01): ArcFace's target logit, and the negative columns above the
+# margined target cosine re-weighted by t, a running mean of the batch's target cosines -- one non-trainable variable, initially 0
+CURRICULAR_PRESET = (64.0, 0.5, 0.01)
+CURRICULAR_STATE = ('classifier/curricularface/t',)
 
 
 def adaface_params(scale=None, margin=None, h=None, t_alpha=None):
@@ -52,7 +56,24 @@ def adaface_state(device):
     return stats, OrderedDict((name, stats[i:i + 1]) for i, name in enumerate(ADAFACE_STATE))
 
 
-IRESNET_NAMES = tuple('IResNet-%d%s' % (d, h) for d in (18, 34, 50, 100) for h in ('', '-arcface', '-cosface', '-adaface'))
+def curricular_params(scale=None, margin=None, alpha=None):
+    """(S, m, alpha) of the CurricularFace head: the given values, the preset where an argument is None."""
+    vals = [float(p if v is None else v) for p, v in zip(CURRICULAR_PRESET, (scale, margin, alpha))]
+    S, m, a = vals
+    if not (S > 0.0 and 0.0 <= m < 1.5707963267948966 and 0.0 <= a <= 1.0):
+        raise ValueError('CurricularFace head needs scale > 0, 0 <= margin < pi/2 and 0 <= alpha <= 1 (got %r, %r, %r)' % tuple(vals))
+    return S, m, a
+
+
+def curricular_state(device):
+    """-> (t, state): the one-element t the kernel updates in place (initially 0) and the same tensor under its variable name"""
+    import torch
+    from collections import OrderedDict
+    t = torch.zeros(1, dtype=torch.float32, device=device)
+    return t, OrderedDict(((CURRICULAR_STATE[0], t),))
+
+
+IRESNET_NAMES = tuple('IResNet-%d%s' % (d, h) for d in (18, 34, 50, 100) for h in ('', '-arcface', '-cosface', '-adaface', '-curricularface'))
 SE_IRESNET_NAMES = tuple('SE-' + n for n in IRESNET_NAMES)      # "IR-SE": an SE gate behind every block's last BN
 SUB_CENTER_NETS = ('SphereNet-ArcFace', 'SphereNet-CosFace', 'ResNet-50-arcface', 'ResNet-50-cosface')
 
@@ -86,10 +107,13 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4, sub_centers=1):
     elif name == 'SphereNet-AdaFace':                             # quality-adaptive margin head (fte.h fte_adaface_margins)
         from .sphere import SphereNetAdaFace
         network = SphereNetAdaFace(data_format=data_format, weight_decay=weight_decay)
+    elif name == 'SphereNet-CurricularFace':                      # hard-negative re-weighting head (fte.h fte_curricular_softmax_fwd_bwd)
+        from .sphere import SphereNetCurricularFace
+        network = SphereNetCurricularFace(data_format=data_format, weight_decay=weight_decay)
     elif name == 'ResNet-50':
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay)
-    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface', 'ResNet-50-adaface'):
+    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface', 'ResNet-50-adaface', 'ResNet-50-curricularface'):
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay, head=name.split('-')[2])
         network.set_sub_centers(sub_centers)
@@ -174,6 +198,12 @@ class Network(abc.ABC):
                 raise ValueError('%s: the AdaFace head has no margin_cos' % self.name)
             self.margin_scale, self.margin, _, _ = adaface_params(self.margin_scale if scale is None else scale,
                                                                   self.margin if margin is None else margin, self.adaface_h, self.adaface_t_alpha)
+            return
+        if head == 'curricularface':                     # S and m; the head has no cosine margin
+            if margin_cos is not None:
+                raise ValueError('%s: the CurricularFace head has no margin_cos' % self.name)
+            self.margin_scale, self.margin, _ = curricular_params(self.margin_scale if scale is None else scale,
+                                                                  self.margin if margin is None else margin, self.curricular_alpha)
             return
         if head not in MARGIN_PRESETS:
             raise ValueError('%s has no additive-margin head' % self.name)

@@ -23,7 +23,8 @@ import torch
 
 from .. import _lib, heads
 from ..loss import sample_size
-from .net_base import NORMALISED_HEADS, Network, adaface_params, adaface_state, margin_params, side_stream
+from .net_base import (NORMALISED_HEADS, Network, adaface_params, adaface_state, curricular_params, curricular_state, margin_params,
+                       side_stream)
 from .sphere_plan import StageRing, split_point, wino_plan
 
 NUM_BLOCKS = (1, 2, 4, 1)     # nets/sphere.py:58,62,66,70
@@ -1083,6 +1084,37 @@ class SphereNetAdaFace(SphereNetMargin):
     def _alloc_head(self, n):
         self.a_rows = torch.empty(n, dtype=torch.float32, device=self.device)
         self.b_rows = torch.empty(n, dtype=torch.float32, device=self.device)
+
+    def _head_spec(self):
+        return heads.describe(self)
+
+    def _others(self):
+        return OrderedDict()
+
+
+class SphereNetCurricularFace(SphereNetMargin):
+    """SphereNet-20 + the CurricularFace head (Huang et al., CVPR 2020): ArcFace's target logit, and every negative column whose
+    cosine exceeds the margined target cosine (a hard negative) re-weighted by t + cos, t a running mean of the batch's target
+    cosines -- the emphasis on hard negatives grows as training converges; fte.h fte_curricular_t / fte_curricular_softmax_fwd_bwd
+    state the contract.  `scale` / `margin` / `alpha` = S / m / alpha, None = the preset (nets/net_base.py CURRICULAR_PRESET).  The
+    call order and the norm-correction backward are SphereNetAdditiveMargin's; t and the mask enter the gradient as constants.
+    State: the scalar `classifier/curricularface/t` (net.state; saved and restored by saver.py, not in the arena, not all-reduced:
+    per-tower state like the BN moving statistics); it moves on every training forward, before the logits are formed, unless
+    `update_moving_stats` is False (the parallel wrappers' construction pass)."""
+    head = 'curricularface'
+
+    def __init__(self, weight_decay=0.0005, data_format='NCHW', name='SphereNet', seed=0, scale=None, margin=None, alpha=None):
+        super(SphereNetCurricularFace, self).__init__(weight_decay, data_format, name, seed)
+        self.margin_scale, self.margin, self.curricular_alpha = curricular_params(scale, margin, alpha)
+        self.margin_cos = 0.0
+        self.update_moving_stats = True
+
+    def _make_state(self):
+        self.cf_state, state = curricular_state(self.device)
+        return state
+
+    def _alloc_head(self, n):
+        self.cf_t = torch.empty(1, dtype=torch.float32, device=self.device)
 
     def _head_spec(self):
         return heads.describe(self)

@@ -64,11 +64,11 @@ def build_parser():
     parser.add_argument('--mfma_dtype', type=str, default='f32',
                         help='f32 (the reference arithmetic), bf16 (bf16 MFMA operands, fp32 accumulate and storage) or bf16s (bf16 operands and bf16 '
                              'storage of activations / inter-layer gradients; fp32 accumulate, sums and master weights: SphereNet).')
-    for flag, what in (('--margin_scale', 'scale S'), ('--margin', 'angular margin m (ArcFace; AdaFace: the margin m its per-image margins scale)'),
-                       ('--margin_cos', 'cosine margin m3 (CosFace; not an AdaFace parameter)')):
+    for flag, what in (('--margin_scale', 'scale S'), ('--margin', 'angular margin m (ArcFace, CurricularFace; AdaFace: the margin m its per-image margins scale)'),
+                       ('--margin_cos', 'cosine margin m3 (CosFace; not an AdaFace or CurricularFace parameter)')):
         parser.add_argument(flag, type=float, default=None,
-                            help='additive-margin nets (SphereNet-ArcFace / -CosFace / -AdaFace, ResNet-50-arcface / -cosface / -adaface) only: the %s; '
-                                 "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35; AdaFace S = 64, m = 0.4)" % what)
+                            help='additive-margin nets (SphereNet-ArcFace / -CosFace / -AdaFace / -CurricularFace, ResNet-50-arcface / -cosface / -adaface / -curricularface) only: the %s; '
+                                 "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35; AdaFace S = 64, m = 0.4; CurricularFace S = 64, m = 0.5)" % what)
     parser.add_argument('--sample_rate', type=float, default=1.0,
                         help='SphereNet-ArcFace / SphereNet-CosFace (one GPU; --num_gpus > 1 with --sync_sample 1): the fraction of the classes the margin head runs over per '
                              "step (Partial FC: the batch's own classes plus a seeded random sample of the others; 0.1 is the usual value). "
