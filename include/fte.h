@@ -783,6 +783,31 @@ int fte_curricular_t(const float* s, const float* xn, const float* wn, const int
 int fte_curricular_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
                                    const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef,
                                    int n, int c, int ld, float grad_scale, void* stream);
+/* MagFace (Meng et al., CVPR 2021): ArcFace's target column with the margin of each row a function of the NORM of its embedding,
+ * and a regulariser g on that norm; the one head whose margin is NOT a constant of the gradient; DESIGN.md 4.22.  c_ij, eps, the
+ * clamp (identity derivative, NaN stays NaN), loss_rows, G, the optional f, columns c..ld-1 and the NaN row of an out-of-range
+ * label (NaN in reg_rows too) are those of fte_margin_softmax_fwd_bwd.  With a_raw = xn_i, a = min(max(a_raw, l_a), u_a),
+ * k_m = (u_m - l_m) / (u_a - l_a), c = c_iy, sin_t = sqrt(max((1 - c)(1 + c), 0)):
+ *   mu_i = l_m + k_m (a - l_a)                                 (the row's margin)
+ *   reg_rows[i] = g_i = a / u_a^2 + 1 / a                      (the regulariser)
+ *   c > -cos mu:  t = c cos mu - sin_t sin mu,  t' = cos mu + sin mu * c / max(sin_t, 1e-6),  dt/dmu = -(sin_t cos mu + c sin mu)
+ *   otherwise:    t = c - mu sin mu,            t' = 1,                                      dt/dmu = -(sin mu + mu cos mu)
+ *   z_iy = S t;  z_ij = S c_ij (j != y);  loss_rows[i] = logsumexp_j z_ij - z_iy
+ *   G_ij = grad_scale * S (p_ij - [j = y]) (j = y ? t' : 1) / (max(xn_i, eps) * wn_j)
+ *   in_i = [l_a <= a_raw <= u_a]                               (the derivative of the clamp, bounds included)
+ *   dL/da_i = in_i * grad_scale * (S (p_iy - 1) * dt/dmu * k_m + lambda_g (1 / u_a^2 - 1 / a^2))
+ *   rowcoef_i = xn_i > eps ? -sum_j G_ij s_ij / xn_i^2 + (dL/da_i) / xn_i : 0
+ * The whole of the gradient through the norm is in rowcoef: dx = G W^T + rowcoef (.) x and dW = x^T G + colcoef (.) W keep their
+ * form, colcoef is the unchanged fte_asoftmax_colcoef.  The total loss the gradient belongs to is
+ * grad_scale * sum_i (loss_rows[i] + lambda_g reg_rows[i]).  The target logit is DISCONTINUOUS in c at c = -cos mu_i.
+ * One launch (mu needs no batch statistic); mu, cos mu, sin mu once per block; sums in fp32 in a fixed order, no float atomics: two
+ * calls write identical bytes.  Preset (the paper's MS1M-V2 values): S = 64, l_a = 10, u_a = 110, l_m = 0.45, u_m = 0.8, lambda_g = 35.
+ * FTE_EINVAL (nothing is launched or written): a null pointer (f excepted), n < 1, c < 1, ld < c, scale <= 0, l_a <= 0, u_a <= l_a,
+ * l_m < 0, u_m < l_m, u_m >= pi/2, lambda_g < 0 (or any of them NaN). */
+int fte_magface_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale,
+                                float l_a, float u_a, float l_m, float u_m, float lambda_g,
+                                float* f, float* loss_rows, float* reg_rows, float* G, float* rowcoef,
+                                int n, int c, int ld, float grad_scale, void* stream);
 /* Sub-center ArcFace (Deng et al., ECCV 2020): K centres per class, the class cosine the max over them; DESIGN.md 4.16.
  * LAYOUT -- planar: with ld the padded class count of ONE plane, the classifier W [d, K*ld], the raw product s = x @ W [n, K*ld],
  * G [n, K*ld], wn [K*ld] and colcoef [K*ld] hold centre k of class j at column k*ld + j; columns c..ld-1 of every plane are

@@ -177,6 +177,7 @@ _SIGS = {
     'fte_adaface_margins': (c_int, [_P, c_int] + [c_float] * 3 + [c_int] + [_P] * 4),
     'fte_curricular_t': (c_int, [_P] * 4 + [c_float, c_int] + [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_curricular_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] * 2 + [_P] * 5 + [c_int] * 3 + [c_float, _P]),
+    'fte_magface_softmax_fwd_bwd': (c_int, [_P] * 4 + [c_float] * 6 + [_P] * 5 + [c_int] * 3 + [c_float, _P]),
     'fte_row_norms': (c_int, [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_col_norms': (c_int, [_P] * 2 + [c_int] * 3 + [_P]),
     'fte_add_scaled_rows_cols': (c_int, [_P] * 4 + [c_int] * 3 + [_P]),

@@ -848,6 +848,15 @@ int fte_curricular_softmax_fwd_bwd(const float* s, const float* xn, const float*
         return FTE_EINVAL;
     return rc(k_curricular_softmax(s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, n, c, ld, grad_scale, (hipStream_t)stream));
 }
+int fte_magface_softmax_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float l_a, float u_a,
+                                float l_m, float u_m, float lambda_g, float* f, float* loss_rows, float* reg_rows, float* G, float* rowcoef,
+                                int n, int c, int ld, float grad_scale, void* stream) {
+    // S > 0, 0 < l_a < u_a, 0 <= l_m <= u_m < pi/2, lambda_g >= 0; a NaN fails every compare
+    const bool ok = scale > 0.f && l_a > 0.f && u_a > l_a && l_m >= 0.f && u_m >= l_m && u_m < 1.57079632679489661923f && lambda_g >= 0.f;
+    if (!s || !xn || !wn || !labels || !loss_rows || !reg_rows || !G || !rowcoef || n <= 0 || c <= 0 || ld < c || !ok) return FTE_EINVAL;
+    return rc(k_magface_softmax(s, xn, wn, labels, scale, l_a, u_a, l_m, u_m, lambda_g, f, loss_rows, reg_rows, G, rowcoef, n, c, ld, grad_scale,
+                                (hipStream_t)stream));
+}
 int fte_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* colcoef, int n, int c, int ld, void* stream) {
     if (!G || !s || !wn || !colcoef || n <= 0 || c <= 0 || ld < c) return FTE_EINVAL;
     return rc(k_asoftmax_colcoef(G, s, wn, colcoef, n, c, ld, (hipStream_t)stream));

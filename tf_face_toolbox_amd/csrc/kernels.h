@@ -50,6 +50,10 @@ hipError_t k_curricular_t(const float* s, const float* xn, const float* wn, cons
 hipError_t k_curricular_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
                                 const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
                                 hipStream_t st);
+// MagFace (fte.h): the margin softmax with the margin a function of the row's norm, its norm gradient in rowcoef, one launch
+hipError_t k_magface_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float l_a, float u_a,
+                             float l_m, float u_m, float lambda_g, float* f, float* loss_rows, float* reg_rows, float* G, float* rowcoef,
+                             int n, int c, int ld, float gs, hipStream_t st);
 hipError_t k_asoftmax_colcoef(const float* G, const float* s, const float* wn, float* cc, int n, int c, int ld, hipStream_t st);
 hipError_t k_row_norms(const float* a, float* out, int rows, int cols, int ld, hipStream_t st);
 hipError_t k_col_norms(const float* a, float* out, int rows, int cols, int ld, hipStream_t st);

@@ -1240,6 +1240,160 @@ __global__ __launch_bounds__(256) void curricular_t_kernel(const float* __restri
     }
 }
 
+// MagFace (fte.h fte_magface_softmax_fwd_bwd): ArcFace's target column with the margin of each row a linear function of its
+// clamped norm, mu = l_m + k_m (a - l_a), and the regulariser g = a / u_a^2 + 1 / a per row.  Unlike AdaFace's, the margin is NOT
+// a constant of the gradient: d loss / d a -- the target logit through mu, plus lambda_g g'(a) -- goes into rowcoef as one more
+// term, dLda / xn, where the clamp does not bind; G keeps ArcFace's form.  mu needs no batch statistic, so this is ONE launch.
+// The per-row work is one sincosf and p_iy once more at the end; the two passes are margin_softmax_kernel's, statement for
+// statement; a kernel of its own for the reason given at margin_softmax_rows_kernel.
+template <bool VEC>
+__global__ __launch_bounds__(256) void magface_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                              const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                              float S, float l_a, float u_a, float l_m, float k_m, float lambda_g,
+                                                              float* __restrict__ f, float* __restrict__ loss_rows,
+                                                              float* __restrict__ reg_rows, float* __restrict__ G,
+                                                              float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    constexpr int U = 4;                                        // chunks in flight per thread and trip
+    constexpr float EPS = 1e-12f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const float* sr = s + (long)row * ld;
+    float* gr = G + (long)row * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const int yl = labels[row];
+    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
+    const int y = bad ? 0 : yl;
+    const float xr = xn[row];
+    MarginRow R;
+    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
+    R.S = S;
+    R.y = y;
+    // the row's margin from its clamped norm, then the target term and its derivative in mu, once per row
+    const float a = fminf(fmaxf(xr, l_a), u_a);
+    const float mu = l_m + k_m * (a - l_a);
+    float sm, cm;
+    sincosf(mu, &sm, &cm);
+    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
+    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+    float ty, tp, tmu;
+    if (cy > -cm) {                                             // cos(pi - mu) = -cos mu: theta + mu <= pi
+        ty = cy * cm - st * sm;
+        tp = cm + sm * cy / fmaxf(st, 1e-6f);
+        tmu = -(st * cm + cy * sm);
+    } else {
+        ty = cy - mu * sm;                                      // easy_margin = False fallback
+        tp = 1.f;
+        tmu = -(sm + mu * cm);
+    }
+    R.zy = S * ty;
+
+    // pass 1: online max / sum of exp
+    float mx = -INFINITY, se = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < c; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    float z[4], r;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
+                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
+                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < c; j += 256) {
+            float r;
+            const float z = R.z(sr[j], wn[j], j, r);
+            if (z > mx) { se *= __expf(mx - z); mx = z; }
+            se += __expf(z - mx);
+        }
+    }
+    const float M = block_max(mx, sh);
+    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
+    const float inv = 1.f / se;
+    const float gS = gscale * S, gT = gscale * S * tp;
+
+    // pass 2: G (and f), sum of G * s
+    float acc = 0.f;
+    if (VEC) {
+        for (int b = 4 * t; b < ld; b += 1024 * U) {
+            f32x4 sv[U], wv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < c) {
+                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
+                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
+                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = b + 1024 * u;
+                if (j < ld) {
+                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
+                    if (j < c) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (j + k < c) {
+                                float r;
+                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
+                                const float p = __expf(z - M) * inv;
+                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
+                                acc += g * sv[u][k];
+                                gv[k] = g;
+                                fv[k] = z;
+                            }
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(gr + j) = gv;
+                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
+                }
+            }
+        }
+    } else {
+        for (int j = t; j < ld; j += 256) {
+            float g = 0.f, fv = 0.f;
+            if (j < c) {
+                float r;
+                const float sv = sr[j];
+                const float z = R.z(sv, wn[j], j, r);
+                const float p = __expf(z - M) * inv;
+                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
+                acc += g * sv;
+                fv = z;
+            }
+            gr[j] = g;
+            if (fr) fr[j] = fv;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (t == 0) {
+        // d loss / d a: the target logit through mu, and the regulariser; zero where the clamp binds (torch's clamp: bounds included)
+        const float py = __expf(R.zy - M) * inv;
+        const float ia = 1.f / a;
+        const bool in = xr >= l_a && xr <= u_a;
+        const float da = in ? gscale * (S * (py - 1.f) * tmu * k_m + lambda_g * (1.f / (u_a * u_a) - ia * ia)) : 0.f;
+        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
+        reg_rows[row] = bad ? NAN : a / (u_a * u_a) + ia;
+        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix + da * R.ix : 0.f);
+    }
+}
+
 // Sub-center head (fte.h fte_subcenter_margin_softmax_fwd_bwd): K centres per class in K planes of ld columns, centre k of class j
 // at column k * ld + j; s / G rows are K * ld wide, f rows ld.  The class cosine is the max over the K planes, the LOWEST k winning
 // a tie (strict > from plane 0 up; a NaN in plane 0 stays), and the two passes are margin_softmax_kernel's on the pooled cosine,
@@ -2074,6 +2228,15 @@ hipError_t k_curricular_softmax(const float* s, const float* xn, const float* wn
     const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
     if (vec) hipLaunchKernelGGL(curricular_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(curricular_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, c, ld, gs);
+    return hipGetLastError();
+}
+hipError_t k_magface_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float l_a, float u_a,
+                             float l_m, float u_m, float lambda_g, float* f, float* loss_rows, float* reg_rows, float* G, float* rowcoef,
+                             int n, int c, int ld, float gs, hipStream_t st) {
+    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const float k_m = (u_m - l_m) / (u_a - l_a);
+    if (vec) hipLaunchKernelGGL(magface_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, l_a, u_a, l_m, k_m, lambda_g, f, loss_rows, reg_rows, G, rowcoef, c, ld, gs);
+    else hipLaunchKernelGGL(magface_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, l_a, u_a, l_m, k_m, lambda_g, f, loss_rows, reg_rows, G, rowcoef, c, ld, gs);
     return hipGetLastError();
 }
 hipError_t k_curricular_t(const float* s, const float* xn, const float* wn, const int32_t* labels, float alpha, int update, float* t_state,

@@ -1,9 +1,9 @@
 """The launch sequence of the heads on the normalised features and classifier columns (A-softmax, ArcFace / CosFace, AdaFace, CurricularFace,
-the sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py (loss_function, backward_head) call it.
+MagFace, the sampled-class form and the K-centre form), written once: loss.py, nets/sphere.py and nets/graph.py (loss_function, backward_head) call it.
 
 Plain functions over buffers the CALLER owns.  `b` is any object that carries them under the nets' attribute names -- a net itself, or
 the scratch namespace loss.py allocates per call: xn [n], wn [ld], rowcoef [n], colcoef [ld], G [n, ld], loss_rows [n]; for AdaFace
-also adaface_stats [2], a_rows [n], b_rows [n]; for CurricularFace cf_state [1], cf_t [1]; for the class sampler class_index [spad],
+also adaface_stats [2], a_rows [n], b_rows [n]; for CurricularFace cf_state [1], cf_t [1]; for MagFace reg_rows [n]; for the class sampler class_index [spad],
 class_inverse [c], sampled_labels [n],
 Ws [d, spad]; with K > 1 centres per class (planar layout, fte.h "Sub-center ArcFace") wn, colcoef and the columns of G are K * ld.
 Nothing here allocates on a step (the sampler's all-gather pair is made once per batch size).  Every launch goes
@@ -24,8 +24,10 @@ def check_labels(labels):
 
 def describe(net):
     """The head description margin_forward takes, from a margin net's attributes: ('adaface', S, m, h, t_alpha, update) -- the running
-    statistics move under the net's update_moving_stats --, ('curricularface', S, m, alpha, update) -- t moves the same way -- or
-    (head, S, m, m3) for 'arcface' / 'cosface'."""
+    statistics move under the net's update_moving_stats --, ('curricularface', S, m, alpha, update) -- t moves the same way --,
+    ('magface', S, l_a, u_a, l_m, u_m, lambda_g) -- no state -- or (head, S, m, m3) for 'arcface' / 'cosface'."""
+    if net.head == 'magface':
+        return ('magface', net.margin_scale) + tuple(net.magface)
     if net.head == 'curricularface':
         return ('curricularface', net.margin_scale, net.margin, net.curricular_alpha, int(net.update_moving_stats))
     if net.head == 'adaface':
@@ -79,6 +81,10 @@ def margin_forward(b, x, W, s, labels, logits, head, n, d, c, ld, grad_scale, st
         S, m, alpha, update = head[1:]
         call('fte_curricular_t', s, b.xn, b.wn, labels, alpha, update, b.cf_state, b.cf_t, n, c, ld, st)
         call('fte_curricular_softmax_fwd_bwd', s, b.xn, b.wn, labels, S, m, b.cf_t, *out)
+    elif head[0] == 'magface':           # the margin from the row's norm inside the kernel: one launch; the regulariser per row beside the loss
+        S, l_a, u_a, l_m, u_m, lambda_g = head[1:]
+        call('fte_magface_softmax_fwd_bwd', s, b.xn, b.wn, labels, S, l_a, u_a, l_m, u_m, lambda_g, logits, b.loss_rows, b.reg_rows,
+             *out[2:])
     else:                                # (S, m, m3): ArcFace / CosFace
         call('fte_margin_softmax_fwd_bwd', s, b.xn, b.wn, labels, *(head[1:] + out))
     call('fte_asoftmax_colcoef', b.G, s, b.wn, b.colcoef, n, c, ld, st)

@@ -1,5 +1,5 @@
 """Host-side mirror of the reference's loss.py: focal_loss (:18-27), center_loss (:29-45), batch_hard_triplet_loss
-(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference), its K-centre form subcenter_margin_loss, its sampled-class form partial_fc_margin_loss and adaface_loss (the margin per row from the feature norms).  Same names, argument meaning and defaults.  There is no autograd here, so every function
+(:47-78) on libfte.so, plus additive_margin_loss (ArcFace / CosFace; not in the reference), its K-centre form subcenter_margin_loss, its sampled-class form partial_fc_margin_loss and adaface_loss (the margin per row from the feature norms), curricularface_loss and magface_loss (the margin a function of the feature norm AND part of the gradient).  Same names, argument meaning and defaults.  There is no autograd here, so every function
 also returns the gradient of ITS OWN loss value with respect to its first argument (what tf.gradients would have
 produced for that term); the graph nets wire them as heads (nets/graph.py), a caller can combine them freely.
 
@@ -205,6 +205,22 @@ def curricularface_loss(features, weights, labels, t, scale=64.0, margin=0.5, al
     dw = torch.empty_like(weights)
     head = ('curricularface', float(scale), float(margin), float(alpha), int(bool(update)))
     return _head_run(b, features, weights, dw, labels, head, n, d, c, ld) + (dw,)
+
+
+def magface_loss(features, weights, labels, scale=64.0, l_a=10.0, u_a=110.0, l_m=0.45, u_m=0.8, lambda_g=35.0, num_classes=None):
+    """MagFace (Meng et al., CVPR 2021): ArcFace's target logit with the margin of each row a linear function of the clamped norm a
+    of its feature vector, mu = l_m + (u_m - l_m) (a - l_a) / (u_a - l_a), plus the regulariser g(a) = a / u_a^2 + 1 / a with weight
+    lambda_g; the contract is fte.h's fte_magface_softmax_fwd_bwd.  The margin and g are part of the gradient: dfeatures carries the
+    derivative through the norm.  The other arguments and the shapes are additive_margin_loss's.
+    -> (loss [0-d] = mean CE + lambda_g * mean g, dfeatures [N, D], dweights [D, ld], magnitude_loss [0-d] = lambda_g * mean g)."""
+    from .nets.net_base import magface_params
+    head = ('magface',) + magface_params(scale, l_a, u_a, l_m, u_m, lambda_g)
+    features, weights, labels, n, d, ld, c = _head_args(features, weights, labels, num_classes)
+    b = _head_scratch(features, n, d, ld, reg_rows=torch.empty(n, dtype=torch.float32, device=features.device))
+    dw = torch.empty_like(weights)
+    ce, dx = _head_run(b, features, weights, dw, labels, head, n, d, c, ld)
+    mag = _scaled_sum(b.reg_rows, head[6] / n)
+    return ce + mag, dx, dw, mag
 
 
 def sample_size(num_classes, sample_rate):

@@ -14,7 +14,7 @@ import torch
 from .. import _lib, heads
 from . import plan
 from .net_base import (MARGIN_PRESETS, NORMALISED_HEADS, Network, adaface_params, adaface_state, curricular_params, curricular_state,
-                       margin_params, side_stream)
+                       magface_params, margin_params, side_stream)
 from .plan import shuffle_perm, stem_kpad          # noqa: F401 (shuffle_perm: the tests import it from here)
 from .sphere import Variable
 
@@ -83,7 +83,9 @@ class GraphNet(Network):
     fte_margin_softmax_rows_fwd_bwd; (S, m) in margin_scale / margin, h / t_alpha in adaface_h / adaface_t_alpha; the scalars are
     state like the BN moving statistics and move under the same switch, update_moving_stats) and 'curricularface' (ArcFace's target
     logit with the hard negatives re-weighted by the running scalar t, fte.h fte_curricular_t / fte_curricular_softmax_fwd_bwd; (S, m)
-    in margin_scale / margin, alpha in curricular_alpha; t is state under the same switch)."""
+    in margin_scale / margin, alpha in curricular_alpha; t is state under the same switch) and 'magface' (ArcFace's target logit with
+    the margin a function of the norm of the classifier's input and a regulariser on that norm, both part of the gradient, fte.h
+    fte_magface_softmax_fwd_bwd; S in margin_scale, (l_a, u_a, l_m, u_m, lambda_g) in magface; no state; a third loss, magnitude_loss)."""
 
     head = 'softmax'
     channel_pad = 1
@@ -129,6 +131,12 @@ class GraphNet(Network):
                 raise ValueError('the curricularface head has no margin_cos')
             self.margin_scale, self.margin, self.curricular_alpha = curricular_params(scale, margin)
             self.margin_cos = 0.0
+        elif head == 'magface':
+            if margin is not None or margin_cos is not None:
+                raise ValueError('the magface head has no margin / margin_cos (set_magface sets its margin range)')
+            vals = magface_params(scale)
+            self.margin_scale, self.magface = vals[0], vals[1:]
+            self.margin, self.margin_cos = 0.0, 0.0
         elif (scale, margin, margin_cos) != (None, None, None):
             raise ValueError('scale / margin / margin_cos belong to the arcface / cosface heads, not %r' % head)
 
@@ -415,6 +423,8 @@ class GraphNet(Network):
             self.a_rows, self.b_rows = torch.empty(n, **f32), torch.empty(n, **f32)
         if self.head == 'curricularface':
             self.cf_t = torch.empty(1, **f32)
+        if self.head == 'magface':
+            self.reg_rows = torch.empty(n, **f32)
         need = max(w.need, 4 * n * fdim, 12 * n * n)
         self.ws = torch.empty((need + 3) // 4 + 1024, **f32)
         self.ws_bytes = self.ws.numel() * 4
@@ -1387,6 +1397,9 @@ class GraphNet(Network):
                      self.num_classes, self.cpad, self.tower_scale / n, st)
             call('fte_sum', self.loss_rows, n, self.tower_scale / n, slots[0:1], self.ws, self.ws_bytes, st)
             losses.append(slots[0]); names.append('focal_entropy' if self.head == 'focal' else 'cross_entropy')
+            if self.head == 'magface':                       # lambda_g * mean g; cross_entropy above stays the pure CE
+                call('fte_sum', self.reg_rows, n, self.magface[4] * self.tower_scale / n, slots[2:3], self.ws, self.ws_bytes, st)
+                losses.append(slots[2]); names.append('magnitude_loss')
             if self.head == 'softmax+center':
                 comm = self.center_comm if self.update_centers else None
                 call('fte_center_loss_fwd_bwd_update', feat, labels, self._centers(), self.loss_rows, self.dfeat, n, d, self.num_classes,

@@ -32,11 +32,15 @@ ADAFACE_PRESET = (64.0, 0.4, 0.333, 0.01)
 ADAFACE_STATS_INIT = (20.0, 100.0)
 ADAFACE_STATE = ('classifier/adaface/batch_mean', 'classifier/adaface/batch_std')
 # heads on the normalised embedding and classifier columns: xn / wn / rowcoef / colcoef buffers and the norm-correction backward
-NORMALISED_HEADS = tuple(MARGIN_PRESETS) + ('adaface', 'curricularface')
+NORMALISED_HEADS = tuple(MARGIN_PRESETS) + ('adaface', 'curricularface', 'magface')
 # CurricularFace (Huang et al. 2020: s = 64, m = 0.5, alpha = 0.01): ArcFace's target logit, and the negative columns above the
 # margined target cosine re-weighted by t, a running mean of the batch's target cosines -- one non-trainable variable, initially 0
 CURRICULAR_PRESET = (64.0, 0.5, 0.01)
 CURRICULAR_STATE = ('classifier/curricularface/t',)
+# MagFace (Meng et al. 2021, the MS1M-V2 values: s = 64, l_a = 10, u_a = 110, l_m = 0.45, u_m = 0.8, lambda_g = 35): the margin of each
+# image grows linearly with the clamped norm of its embedding and a regulariser rewards large norms; the margin is part of the
+# gradient, so the norms are trained.  No state variable: a MagFace net has the variable names of the ArcFace net of its backbone
+MAGFACE_PRESET = (64.0, 10.0, 110.0, 0.45, 0.8, 35.0)
 
 
 def adaface_params(scale=None, margin=None, h=None, t_alpha=None):
@@ -73,7 +77,25 @@ def curricular_state(device):
     return t, OrderedDict(((CURRICULAR_STATE[0], t),))
 
 
-IRESNET_NAMES = tuple('IResNet-%d%s' % (d, h) for d in (18, 34, 50, 100) for h in ('', '-arcface', '-cosface', '-adaface', '-curricularface'))
+def magface_params(scale=None, l_a=None, u_a=None, l_m=None, u_m=None, lambda_g=None):
+    """(S, l_a, u_a, l_m, u_m, lambda_g) of the MagFace head: the given values, the preset where an argument is None.  The ranges are
+    fte.h's fte_magface_softmax_fwd_bwd (a NaN fails every compare)."""
+    vals = [float(p if v is None else v) for p, v in zip(MAGFACE_PRESET, (scale, l_a, u_a, l_m, u_m, lambda_g))]
+    S, la, ua, lm, um, lg = vals
+    if not (S > 0.0 and la > 0.0 and ua > la and lm >= 0.0 and um >= lm and um < 1.5707963267948966 and lg >= 0.0):
+        raise ValueError('MagFace head needs scale > 0, 0 < l_a < u_a, 0 <= l_m <= u_m < pi/2 and lambda_g >= 0 '
+                         '(got %r, %r, %r, %r, %r, %r)' % tuple(vals))
+    return tuple(vals)
+
+
+def magface_lambda_bound(scale, l_a, u_a, l_m, u_m):
+    """S k_m u_a^2 l_a^2 / (u_a^2 - l_a^2): below it lambda_g does not give the loss a unique optimum in the norm (the paper's
+    condition; 22.6 for the preset)"""
+    k_m = (u_m - l_m) / (u_a - l_a)
+    return scale * k_m * u_a * u_a * l_a * l_a / (u_a * u_a - l_a * l_a)
+
+
+IRESNET_NAMES = tuple('IResNet-%d%s' % (d, h) for d in (18, 34, 50, 100) for h in ('', '-arcface', '-cosface', '-adaface', '-curricularface', '-magface'))
 SE_IRESNET_NAMES = tuple('SE-' + n for n in IRESNET_NAMES)      # "IR-SE": an SE gate behind every block's last BN
 SUB_CENTER_NETS = ('SphereNet-ArcFace', 'SphereNet-CosFace', 'ResNet-50-arcface', 'ResNet-50-cosface')
 
@@ -110,10 +132,13 @@ def net_select(name, data_format='NCHW', weight_decay=5e-4, sub_centers=1):
     elif name == 'SphereNet-CurricularFace':                      # hard-negative re-weighting head (fte.h fte_curricular_softmax_fwd_bwd)
         from .sphere import SphereNetCurricularFace
         network = SphereNetCurricularFace(data_format=data_format, weight_decay=weight_decay)
+    elif name == 'SphereNet-MagFace':                             # magnitude-aware margin head (fte.h fte_magface_softmax_fwd_bwd)
+        from .sphere import SphereNetMagFace
+        network = SphereNetMagFace(data_format=data_format, weight_decay=weight_decay)
     elif name == 'ResNet-50':
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay)
-    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface', 'ResNet-50-adaface', 'ResNet-50-curricularface'):
+    elif name in ('ResNet-50-arcface', 'ResNet-50-cosface', 'ResNet-50-adaface', 'ResNet-50-curricularface', 'ResNet-50-magface'):
         from .resnet import ResNet
         network = ResNet(num_layers=50, data_format=data_format, weight_decay=weight_decay, head=name.split('-')[2])
         network.set_sub_centers(sub_centers)
@@ -205,11 +230,25 @@ class Network(abc.ABC):
             self.margin_scale, self.margin, _ = curricular_params(self.margin_scale if scale is None else scale,
                                                                   self.margin if margin is None else margin, self.curricular_alpha)
             return
+        if head == 'magface':                            # S alone; the margin is (l_a, u_a, l_m, u_m) of set_magface
+            if margin is not None or margin_cos is not None:
+                raise ValueError('%s: the MagFace head has no margin / margin_cos; its margin range is set by --magface '
+                                 '(set_magface)' % self.name)
+            self.margin_scale = magface_params(self.margin_scale if scale is None else scale, *self.magface)[0]
+            return
         if head not in MARGIN_PRESETS:
             raise ValueError('%s has no additive-margin head' % self.name)
         self.margin_scale, self.margin, self.margin_cos = margin_params(
             head, self.margin_scale if scale is None else scale, self.margin if margin is None else margin,
             self.margin_cos if margin_cos is None else margin_cos)
+
+    def set_magface(self, l_a=None, u_a=None, l_m=None, u_m=None, lambda_g=None):
+        """MagFace nets only: replace (l_a, u_a, l_m, u_m, lambda_g) -- train.py --magface; None keeps a value.  Takes effect from
+        the next forward / loss_function."""
+        if getattr(self, 'head', None) != 'magface':
+            raise ValueError('%s has no MagFace head (--magface: SphereNet-MagFace, ResNet-50-magface, [SE-]IResNet-*-magface only)' % self.name)
+        given = (l_a, u_a, l_m, u_m, lambda_g)
+        self.magface = magface_params(self.margin_scale, *(old if v is None else v for old, v in zip(self.magface, given)))[1:]
 
     def set_sample_rate(self, rate, seed=0):
         """Nets with a sampled-class (Partial FC) head only -- SphereNet-ArcFace / -CosFace; train.py --sample_rate / --sample_seed.

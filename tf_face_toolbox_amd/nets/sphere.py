@@ -23,8 +23,8 @@ import torch
 
 from .. import _lib, heads
 from ..loss import sample_size
-from .net_base import (NORMALISED_HEADS, Network, adaface_params, adaface_state, curricular_params, curricular_state, margin_params,
-                       side_stream)
+from .net_base import (NORMALISED_HEADS, Network, adaface_params, adaface_state, curricular_params, curricular_state, magface_params,
+                       margin_params, side_stream)
 from .sphere_plan import StageRing, split_point, wino_plan
 
 NUM_BLOCKS = (1, 2, 4, 1)     # nets/sphere.py:58,62,66,70
@@ -1121,3 +1121,39 @@ class SphereNetCurricularFace(SphereNetMargin):
 
     def _others(self):
         return OrderedDict()
+
+
+class SphereNetMagFace(SphereNetMargin):
+    """SphereNet-20 + the MagFace head (Meng et al., CVPR 2021): ArcFace's target logit with the margin of each image a linear
+    function of the clamped norm of its embedding, mu = l_m + (u_m - l_m) (a - l_a) / (u_a - l_a), and the regulariser
+    g(a) = a / u_a^2 + 1 / a, weight lambda_g, which rewards large norms; fte.h fte_magface_softmax_fwd_bwd states the contract.
+    The margin is part of the gradient (the opposite of AdaFace): the norms are trained, and after training the norm of the raw
+    embedding is a quality score of the image (verification.feature_quality).  `scale` = S and `l_a` .. `lambda_g`, None = the
+    preset (nets/net_base.py MAGFACE_PRESET).  The call order and the norm-correction backward are SphereNetAdditiveMargin's; the
+    head's whole norm gradient is in rowcoef.  No state: the variable names are SphereNet-ArcFace's.  Three losses: cross_entropy
+    (the pure CE, comparable with ArcFace's), magnitude_loss = lambda_g * mean g, reg_loss."""
+    head = 'magface'
+
+    def __init__(self, weight_decay=0.0005, data_format='NCHW', name='SphereNet', seed=0, scale=None, l_a=None, u_a=None, l_m=None,
+                 u_m=None, lambda_g=None):
+        super(SphereNetMagFace, self).__init__(weight_decay, data_format, name, seed)
+        vals = magface_params(scale, l_a, u_a, l_m, u_m, lambda_g)
+        self.margin_scale, self.magface = vals[0], vals[1:]
+        self.margin, self.margin_cos = 0.0, 0.0
+
+    def _alloc_head(self, n):
+        self.reg_rows = torch.empty(n, dtype=torch.float32, device=self.device)
+
+    def _head_spec(self):
+        return heads.describe(self)
+
+    def _finish_losses(self, n):
+        super(SphereNetMagFace, self)._finish_losses(n)
+        # slot 2: lambda_g * mean g * tower_scale (the term G's rowcoef already carries the gradient of)
+        _lib.call('fte_sum', self.reg_rows, n, self.magface[4] * self.tower_scale / n, self.loss_slots[2:3], self.ws, self.ws_bytes, _stream())
+
+    def loss_function(self, scope, labels, **logits):
+        n = labels.shape[0]
+        self._finish_losses(n)
+        return ([self.loss_slots[0], self.loss_slots[2], self.loss_slots[1]], ['cross_entropy', 'magnitude_loss', 'reg_loss'],
+                OrderedDict())

@@ -41,6 +41,16 @@ def normalize(x, return_norms=False):
     return (y, norms) if return_norms else y
 
 
+def feature_quality(feats):
+    """The norm of every row of the raw features [n, d] (float32, CUDA; a numpy array is moved there) -> [n] on the device: the
+    norms normalize(..., return_norms=True) returns.  For a MagFace model this is the quality score of the image."""
+    import numpy as np
+    import torch
+    if not isinstance(feats, torch.Tensor):
+        feats = torch.from_numpy(np.ascontiguousarray(np.asarray(feats, np.float32))).cuda()
+    return normalize(feats, return_norms=True)[1]
+
+
 def pair_scores(feats, ia, ib):
     """out[p] = dot(feats[ia[p]], feats[ib[p]]) for normalised rows (the LFW protocol's listed pairs)."""
     import torch

@@ -64,11 +64,15 @@ def build_parser():
     parser.add_argument('--mfma_dtype', type=str, default='f32',
                         help='f32 (the reference arithmetic), bf16 (bf16 MFMA operands, fp32 accumulate and storage) or bf16s (bf16 operands and bf16 '
                              'storage of activations / inter-layer gradients; fp32 accumulate, sums and master weights: SphereNet).')
-    for flag, what in (('--margin_scale', 'scale S'), ('--margin', 'angular margin m (ArcFace, CurricularFace; AdaFace: the margin m its per-image margins scale)'),
-                       ('--margin_cos', 'cosine margin m3 (CosFace; not an AdaFace or CurricularFace parameter)')):
+    for flag, what in (('--margin_scale', 'scale S'), ('--margin', 'angular margin m (ArcFace, CurricularFace; AdaFace: the margin m its per-image margins scale; MagFace: refused, see --magface)'),
+                       ('--margin_cos', 'cosine margin m3 (CosFace; not an AdaFace, CurricularFace or MagFace parameter)')):
         parser.add_argument(flag, type=float, default=None,
                             help='additive-margin nets (SphereNet-ArcFace / -CosFace / -AdaFace / -CurricularFace, ResNet-50-arcface / -cosface / -adaface / -curricularface) only: the %s; '
-                                 "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35; AdaFace S = 64, m = 0.4; CurricularFace S = 64, m = 0.5)" % what)
+                                 "default: the net's preset (ArcFace S = 64, m = 0.5, m3 = 0; CosFace S = 64, m = 0, m3 = 0.35; AdaFace S = 64, m = 0.4; CurricularFace S = 64, m = 0.5; MagFace S = 64)" % what)
+    parser.add_argument('--magface', type=str, default=None,
+                        help='MagFace nets (SphereNet-MagFace, ResNet-50-magface, [SE-]IResNet-*-magface) only: l_a,u_a,l_m,u_m,lambda_g -- the norm '
+                             "range, the margin range and the regulariser's weight; default 10,110,0.45,0.8,35 (the paper's MS1M-V2 values). "
+                             '--margin_scale sets S.')
     parser.add_argument('--sample_rate', type=float, default=1.0,
                         help='SphereNet-ArcFace / SphereNet-CosFace (one GPU; --num_gpus > 1 with --sync_sample 1): the fraction of the classes the margin head runs over per '
                              "step (Partial FC: the batch's own classes plus a seeded random sample of the others; 0.1 is the usual value). "
@@ -132,6 +136,49 @@ def sub_centers_flags_check(FLAGS):
         sub_centers_check(FLAGS.net_name, FLAGS.sub_centers, FLAGS.sample_rate)
     except ValueError as e:
         raise SystemExit('--sub_centers %d: %s' % (FLAGS.sub_centers, e))
+
+
+def is_magface_net(name):
+    return name == 'SphereNet-MagFace' or name.endswith('-magface')
+
+
+def magface_notice(scale, l_a, u_a, l_m, u_m, lambda_g):
+    """the line train.py prints once when lambda_g is below the paper's bound for a unique optimum in the norm, else None"""
+    from tf_face_toolbox_amd.nets.net_base import magface_lambda_bound
+    bound = magface_lambda_bound(scale, l_a, u_a, l_m, u_m)
+    if lambda_g < bound:
+        return ('MagFace: lambda_g = %g is below S k_m u_a^2 l_a^2 / (u_a^2 - l_a^2) = %.4g: the loss has no unique optimum in the '
+                'feature norm (Meng et al. 2021, the condition of their Property 2)' % (lambda_g, bound))
+    return None
+
+
+def magface_flags_check(FLAGS):
+    """--magface and the margin flags of a MagFace net: refuse what does not belong, before anything is built.  Leaves the five
+    numbers (or None) in FLAGS.magface_values."""
+    FLAGS.magface_values = None
+    magnet = is_magface_net(FLAGS.net_name)
+    if FLAGS.magface is not None and not magnet:
+        raise SystemExit('--magface: only the MagFace nets (SphereNet-MagFace, ResNet-50-magface, [SE-]IResNet-*-magface) take it, not %s'
+                         % FLAGS.net_name)
+    if not magnet:
+        return
+    for flag in ('margin', 'margin_cos'):
+        if getattr(FLAGS, flag) is not None:
+            raise SystemExit('--%s: %s has no such parameter; its margin range is set by --magface l_a,u_a,l_m,u_m,lambda_g'
+                             % (flag, FLAGS.net_name))
+    from tf_face_toolbox_amd.nets.net_base import MAGFACE_PRESET, magface_params
+    vals = MAGFACE_PRESET[1:]
+    if FLAGS.magface is not None:
+        try:
+            vals = tuple(float(v) for v in FLAGS.magface.split(','))
+        except ValueError:
+            vals = ()
+        if len(vals) != 5:
+            raise SystemExit('--magface takes five numbers l_a,u_a,l_m,u_m,lambda_g: got %r' % FLAGS.magface)
+    try:
+        FLAGS.magface_values = magface_params(FLAGS.margin_scale, *vals)[1:]
+    except ValueError as e:
+        raise SystemExit('--magface: %s' % e)
 
 
 def FLAGS_assertion(FLAGS):
@@ -244,6 +291,11 @@ def train(FLAGS):
         margins = (FLAGS.margin_scale, FLAGS.margin, FLAGS.margin_cos)
         if getattr(network, 'margin_scale', None) is not None and margins != (None, None, None):
             network.set_margin(*margins)
+        if getattr(FLAGS, 'magface_values', None) is not None:
+            network.set_magface(*FLAGS.magface_values)
+            notice = magface_notice(network.margin_scale, *network.magface)
+            if notice and rank == 0:
+                print(notice)
         if FLAGS.sample_rate < 1.0:
             network.set_sample_rate(FLAGS.sample_rate, FLAGS.sample_seed)
         lr = lr_config(FLAGS, FLAGS.lr_decay_method, batches_per_epoch)                              # train.py:176
@@ -351,6 +403,7 @@ def main(argv=None):
     shard_flags_check(FLAGS)
     sample_flags_check(FLAGS)
     sub_centers_flags_check(FLAGS)
+    magface_flags_check(FLAGS)
     os.makedirs(os.path.join(FLAGS.train_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     os.makedirs(os.path.join(FLAGS.model_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     train(FLAGS)

@@ -48,6 +48,9 @@ def build_parser():
     parser.add_argument('--betas', type=str, default='0:20', help='templates --fusion softmax: betas, `a:b[:step]` (inclusive) or '
                         'a comma list; 1..32 values in [0, 40].')
     parser.add_argument('--weight_column', type=str, help='templates / template_search: metadata column of per-image pooling weights.')
+    parser.add_argument('--weight_by_norm', type=int, default=0, help='templates (--fusion pool) / template_search: 1 = pool the unit '
+                        'features with the norms of the raw features as the per-image weights (the quality score of a MagFace model: '
+                        'verification.feature_quality).  Not together with --weight_column.')
     parser.add_argument('--gallery_metadata', type=str, help='template_search: metadata CSV of the gallery templates.')
     parser.add_argument('--distractor_feature_path', type=str, help='megaface: .mat of the distractor features (wfea).')
     parser.add_argument('--distractor_list_path', type=str, help='megaface: the distractor list (paths only; row i = line i).')
@@ -119,9 +122,25 @@ def _template_set(meta_path, feature_path, list_path, weight_column):
     return meta, feats, V.build_templates(meta)
 
 
-def _pooled(feats, tpl, meta):
+def _pooled(feats, tpl, meta, weight_by_norm=False):
+    """the pooled template features; weight_by_norm: the norm of each raw row is its weight (else the metadata column, or 1)"""
+    import torch
     from tf_face_toolbox_amd import verification as V
-    return V.template_pool(_device_rows(feats), tpl['members'], tpl['media_off'], tpl['tmpl_off'], meta['weight'])
+    if weight_by_norm:
+        rows, weights = V.normalize(torch.from_numpy(np.ascontiguousarray(feats)).cuda(), return_norms=True)
+    else:
+        rows, weights = _device_rows(feats), meta['weight']
+    return V.template_pool(rows, tpl['members'], tpl['media_off'], tpl['tmpl_off'], weights)
+
+
+def weight_flags_check(FLAGS):
+    """--weight_by_norm: refuse it beside --weight_column and where nothing is pooled"""
+    if not getattr(FLAGS, 'weight_by_norm', 0):
+        return
+    if FLAGS.weight_column:
+        raise SystemExit('--weight_by_norm 1 and --weight_column both set the per-image pooling weights: give one of them')
+    if FLAGS.protocol not in ('templates', 'template_search') or (FLAGS.protocol == 'templates' and FLAGS.fusion != 'pool'):
+        raise SystemExit('--weight_by_norm 1 weights the pooled template features: --protocol templates (--fusion pool) or template_search')
 
 
 def run_templates(FLAGS, split):
@@ -135,7 +154,7 @@ def run_templates(FLAGS, split):
     t1, t2, genuine = V.read_template_pairs(sp(FLAGS.template_pairs), subj)
     ia, ib = V.template_index(tpl['template_ids'], t1), V.template_index(tpl['template_ids'], t2)
     if FLAGS.fusion == 'pool':
-        scores = V.pair_scores(_pooled(feats, tpl, meta), ia, ib).cpu().numpy()
+        scores = V.pair_scores(_pooled(feats, tpl, meta, bool(FLAGS.weight_by_norm)), ia, ib).cpu().numpy()
     else:
         scores = V.set_pair_scores(_device_rows(feats), tpl['members'], tpl['media_off'], tpl['tmpl_off'], ia, ib,
                                    parse_betas(FLAGS.betas)).cpu().numpy()
@@ -162,7 +181,8 @@ def run_template_search(FLAGS, split):
     pmeta, pfeats, ptpl = _template_set(sp(FLAGS.template_metadata), sp(FLAGS.feature_path), sp(FLAGS.data_list_path), FLAGS.weight_column)
     gmeta, gfeats, gtpl = _template_set(sp(FLAGS.gallery_metadata), sp(FLAGS.gallery_feature_path), sp(FLAGS.gallery_list_path),
                                         FLAGS.weight_column)
-    P, G = _pooled(pfeats, ptpl, pmeta), _pooled(gfeats, gtpl, gmeta)
+    by_norm = bool(FLAGS.weight_by_norm)
+    P, G = _pooled(pfeats, ptpl, pmeta, by_norm), _pooled(gfeats, gtpl, gmeta, by_norm)
     k = min(10, G.shape[0])
     s, i = V.topk_search(P, G, k, chunk_rows=FLAGS.chunk_rows or None)
     res = V.open_set_identification(s.cpu().numpy(), i.cpu().numpy(), ptpl['subjects'], gtpl['subjects'], ranks=tuple(range(1, k + 1)))
@@ -273,6 +293,7 @@ def run(FLAGS):
     from tf_face_toolbox_amd import verification as V
     from tf_face_toolbox_amd.data import get_image_paths
 
+    weight_flags_check(FLAGS)
     torch.cuda.set_device(0)
     t0 = time.time()
     chunk = FLAGS.chunk_rows or None
