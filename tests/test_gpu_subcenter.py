@@ -126,9 +126,9 @@ def _check_head(got, s, xn, wn, labels, K, c, ld, S, m, m3, gs, what, cc=None):
     return fr, Gr
 
 
-@pytest.mark.parametrize('K', [2, 3, 4])
-@pytest.mark.parametrize('c', [10, 1000, 4100])
-@pytest.mark.parametrize('n', [1, 7, 64])
+# K = 5 and 8 hold one chunk per trip: c = 1030 is their smallest shape with a second trip, its last chunk partly filled
+@pytest.mark.parametrize('n,c,K', [(n, c, K) for K in (2, 3, 4) for c in (10, 1000, 4100) for n in (1, 7, 64)] +
+                         [(n, c, K) for K in (5, 8) for n, c in ((1, 10), (7, 1030))])
 def test_kernel_against_the_restatement(n, c, K):
     s, xn, wn, labels, ld = _raw(n, c, K, seed=n * 7 + c + 100 * K)
     for S, m, m3 in (ARC, COS, MIX):

@@ -549,49 +549,46 @@ __global__ __launch_bounds__(256) void asoftmax_colcoef_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------
-// Additive-margin softmax (ArcFace m, CosFace m3; fte.h states the contract).  One block per row, s = raw x.W row.
-// Pass 1: one online max / sum-of-exp over the row (a thread rescales its partial sum only when its running max grows, so
-// the steady state costs one exp per element); the partials merge through block_max / block_sum in a fixed order.
-// Pass 2 re-reads s, writes G (and f) and sums G*s for rowcoef.  The target logit is computed once per row; the streams
-// select it with one compare.  VEC: s / G / f / wn 16-byte aligned and ld % 4 == 0 -- dwordx4 over columns 4q..4q+3
-// (a chunk starting below c lies wholly below ld; wn is read as a vector only where the chunk lies wholly below c).
+// Additive-margin softmax heads (fte.h states the contracts): ArcFace m / CosFace m3, the same head sharded over ranks, with a
+// margin per row (AdaFace), CurricularFace, MagFace and the sub-center head.  One block per row, s = raw x.W row.  Every kernel is
+//   prologue   the row's label, ix = 1 / max(xn, eps), the target cosine and from it the head's target logit zy and slope tp;
+//   pass 1     margin_pass1: one online max / sum-of-exp over the row (a thread rescales its partial sum only when its running
+//              max grows, so the steady state costs one exp per element); the partials merge through block_max / block_sum in a
+//              fixed order;
+//   pass 2     margin_pass2: re-reads s, writes G (and f) and block-sums G * s for rowcoef;
+//   epilogue   loss_rows, rowcoef and what the head adds.
+// The two passes are written once, for K planes of ld columns (K centres per class; K = 1 is the plain head) and a Logit policy
+// that turns the pooled cosine of a column into its logit; the target logit is computed once per row and the streams select it
+// with one compare.  VEC: s / G / f / wn 16-byte aligned and ld % 4 == 0 -- dwordx4 over columns 4q..4q+3 (a chunk starting below
+// c lies wholly below ld; wn is read as a vector only where the chunk lies wholly below c).  U chunks of K planes are in flight
+// per thread and trip: it shrinks as K grows so that a thread holds at most 8 s / wn chunk pairs, all in registers.
 // c = s * (1/max(xn, eps)) * rcp(wn): v_rcp_f32 (1 ulp) instead of a division; exp is __expf: its error, |x| * 2^-24
 // relative for exp(x), is below 1e-6 on every term that is more than 2e-9 of the row's sum.
+// profiles/margin_shared_body.md has the registers and the timings of the shared passes against the six copies they replaced.
 // ------------------------------------------------------------------------------------
+constexpr float MARGIN_EPS = 1e-12f;
+constexpr int margin_chunks(int K) { return K <= 2 ? 4 : (K <= 4 ? 2 : 1); }
 __device__ __forceinline__ float clamp1(float v) { return v > 1.f ? 1.f : (v < -1.f ? -1.f : v); }     // NaN stays NaN
-struct MarginRow {
-    float ix, S, zy;
-    int y;
-    __device__ __forceinline__ float z(float sv, float wv, int j, float& r) const {
-        r = ix * __builtin_amdgcn_rcpf(wv);
-        return j == y ? zy : S * clamp1(sv * r);
-    }
-};
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                             const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                             float S, float m, float m3, float* __restrict__ f,
-                                                             float* __restrict__ loss_rows, float* __restrict__ G,
-                                                             float* __restrict__ rowcoef, int c, int ld, float gscale) {
-    constexpr int U = 4;                                        // chunks in flight per thread and trip
-    constexpr float EPS = 1e-12f;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * ld;
-    float* gr = G + (long)row * ld;
-    float* fr = f ? f + (long)row * ld : nullptr;
-    const int yl = labels[row];
-    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
-    const int y = bad ? 0 : yl;
-    const float xr = xn[row];
-    MarginRow R;
-    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
-    R.S = S;
-    R.y = y;
-    // target term, once per row
-    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
-    float ty = cy - m3, tp = 1.f;
+// The row: an out-of-range label (or whatever else the head calls bad) makes ix NaN -- the NaN row -- and y 0: no out-of-bounds access
+struct MarginRowId {
+    bool bad;
+    int y;
+    float ix;
+};
+__device__ __forceinline__ float margin_ix(bool bad, float xr) { return bad ? NAN : 1.f / fmaxf(xr, MARGIN_EPS); }
+__device__ __forceinline__ MarginRowId margin_row_id(int yl, int c, float xr, bool bad_margin = false) {
+    const bool out = (unsigned)yl >= (unsigned)c;
+    return {out || bad_margin, out ? 0 : yl, margin_ix(out || bad_margin, xr)};
+}
+// the cosine of column y; curricular_t_kernel averages this very expression
+__device__ __forceinline__ float target_cos(const float* sr, const float* wn, int y, float ix) {
+    return clamp1(sr[y] * (ix * __builtin_amdgcn_rcpf(wn[y])));
+}
+// ArcFace / CosFace target term: ty = cos(theta + m) - m3 and tp = d ty / d cos(theta)
+__device__ __forceinline__ void arc_target(float cy, float m, float m3, float& ty, float& tp) {
+    ty = cy - m3;
+    tp = 1.f;
     if (m > 0.f) {
         const float cm = cosf(m), sm = sinf(m);
         if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
@@ -602,882 +599,94 @@ __global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __rest
             ty = cy - m * sm - m3;                              // easy_margin = False fallback
         }
     }
-    R.zy = S * ty;
-
-    // pass 1: online max / sum of exp
-    float mx = -INFINITY, se = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < c; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    float z[4], r;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
-                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
-                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < c; j += 256) {
-            float r;
-            const float z = R.z(sr[j], wn[j], j, r);
-            if (z > mx) { se *= __expf(mx - z); mx = z; }
-            se += __expf(z - mx);
-        }
-    }
-    const float M = block_max(mx, sh);
-    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
-    const float inv = 1.f / se;
-    const float gS = gscale * S, gT = gscale * S * tp;
-
-    // pass 2: G (and f), sum of G * s
-    float acc = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < ld; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < ld) {
-                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
-                    if (j < c) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (j + k < c) {
-                                float r;
-                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
-                                const float p = __expf(z - M) * inv;
-                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
-                                acc += g * sv[u][k];
-                                gv[k] = g;
-                                fv[k] = z;
-                            }
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(gr + j) = gv;
-                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < ld; j += 256) {
-            float g = 0.f, fv = 0.f;
-            if (j < c) {
-                float r;
-                const float sv = sr[j];
-                const float z = R.z(sv, wn[j], j, r);
-                const float p = __expf(z - M) * inv;
-                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
-                acc += g * sv;
-                fv = z;
-            }
-            gr[j] = g;
-            if (fr) fr[j] = fv;
-        }
-    }
-    acc = block_sum(acc, sh);
-    if (t == 0) {
-        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
-        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
-    }
+}
+__device__ __forceinline__ float margin_loss(bool bad, float M, float se, float zy) { return bad ? NAN : (M + logf(se)) - zy; }
+__device__ __forceinline__ float margin_rowcoef(bool bad, float xr, float acc, float ix) {
+    return bad ? NAN : (xr > MARGIN_EPS ? -acc * ix * ix : 0.f);
 }
 
-// ------------------------------------------------------------------------------------
-// The same head with the classes split over R ranks (fte.h "Sharded margin head"): this rank holds columns class_lo .. class_lo + c
-// of the classifier, the labels are global.  Two kernels, each margin_softmax_kernel's pass with the same block per row, the same
-// chunking and the same target term (a row whose label another shard owns has no target column here: R.y = -1 matches none):
-//   margin_shard_stats_kernel   pass 1 alone -> (max, sum of exp against that max, target logit or 0) per row;
-//   margin_shard_fwd_bwd_kernel merges the R triples IN RANK ORDER (every rank gets the same M, Z, T and so the same loss bits),
-//                               then pass 2 with p = exp(z - M) / Z.
-// Kernels of their own for the reason given at margin_softmax_rows_kernel.
-// ------------------------------------------------------------------------------------
-struct ShardRow {
-    MarginRow R;
-    float tp;
-    bool bad, own;
-    // the row's label against this shard and, where the shard owns it, the target term as margin_softmax_kernel forms it
-    __device__ __forceinline__ void init(const float* sr, const float* wn, int yl, int lo, int c, int num_classes, float xr, float S, float m,
-                                         float m3) {
-        constexpr float EPS = 1e-12f;
-        bad = (unsigned)yl >= (unsigned)num_classes;          // out-of-range label: NaN row on every shard, no out-of-bounds access
-        own = !bad && yl >= lo && yl - lo < c;
-        R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
-        R.S = S;
-        R.y = own ? yl - lo : -1;
-        R.zy = 0.f;
-        tp = 1.f;
-        if (own) {
-            const float cy = clamp1(sr[R.y] * (R.ix * __builtin_amdgcn_rcpf(wn[R.y])));
-            float ty = cy - m3;
-            if (m > 0.f) {
-                const float cm = cosf(m), sm = sinf(m);
-                if (cy > -cm) {                                 // cos(pi - m) = -cos m: theta + m <= pi
-                    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
-                    ty = cy * cm - st * sm - m3;
-                    tp = cm + sm * cy / fmaxf(st, 1e-6f);
-                } else {
-                    ty = cy - m * sm - m3;                      // easy_margin = False fallback
-                }
-            }
-            R.zy = S * ty;
-        }
+// Logit policies: the logit of column j from its pooled cosine cb, and d = (dz/dc) / S of a negative column.
+struct PlainLogit {
+    float S, zy;
+    int y;                                                      // -1: the target column is not in this row (another shard owns it)
+    __device__ __forceinline__ float z(float cb, int j, float& d) const {
+        d = 1.f;
+        return j == y ? zy : S * cb;
     }
 };
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void margin_shard_stats_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                                 const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                                 int lo, int num_classes, float S, float m, float m3,
-                                                                 float* __restrict__ stats, int n, int c, int ld) {
-    constexpr int U = 4;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * ld;
-    ShardRow Q;
-    Q.init(sr, wn, labels[row], lo, c, num_classes, xn[row], S, m, m3);
-    const MarginRow R = Q.R;
-    float mx = -INFINITY, se = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < c; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    float z[4], r;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
-                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
-                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < c; j += 256) {
-            float r;
-            const float z = R.z(sr[j], wn[j], j, r);
-            if (z > mx) { se *= __expf(mx - z); mx = z; }
-            se += __expf(z - mx);
-        }
-    }
-    const float M = block_max(mx, sh);
-    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
-    if (t == 0) {
-        stats[row] = Q.bad ? NAN : M;
-        stats[(long)n + row] = Q.bad ? NAN : se;
-        stats[2 * (long)n + row] = Q.bad ? NAN : R.zy;       // 0 where another shard owns the label
-    }
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void margin_shard_fwd_bwd_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                                   const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                                   int lo, int num_classes, float S, float m, float m3,
-                                                                   const float* __restrict__ all_stats, int ranks, float* __restrict__ f,
-                                                                   float* __restrict__ loss_rows, float* __restrict__ G,
-                                                                   float* __restrict__ rowcoef, int n, int c, int ld, float gscale) {
-    constexpr int U = 4;
-    constexpr float EPS = 1e-12f;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * ld;
-    float* gr = G + (long)row * ld;
-    float* fr = f ? f + (long)row * ld : nullptr;
-    const float xr = xn[row];
-    ShardRow Q;
-    Q.init(sr, wn, labels[row], lo, c, num_classes, xr, S, m, m3);
-    // the R triples of the row, in rank order (every thread reads the same addresses: one broadcast load each)
-    float M = -INFINITY, Z = 0.f, T = 0.f;
-    bool bad = Q.bad;
-    for (int r = 0; r < ranks; ++r) {
-        const float mr = all_stats[((long)r * 3) * n + row];
-        bad = bad || mr != mr;                                  // fmaxf would drop a NaN
-        M = fmaxf(M, mr);
-    }
-    for (int r = 0; r < ranks; ++r) {
-        const float* a = all_stats + ((long)r * 3) * n + row;
-        const float er = a[n], tr = a[2 * (long)n];
-        bad = bad || er != er || tr != tr;
-        Z += er * expf(a[0] - M);
-        T += tr;
-    }
-    MarginRow R = Q.R;
-    if (bad) R.ix = R.zy = NAN;                                 // the NaN row of the dense contract: z, p and g below c are NaN
-    const int y = R.y;
-    const float inv = 1.f / Z;
-    const float gS = gscale * S, gT = gscale * S * Q.tp;
-
-    float acc = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < ld; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < ld) {
-                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
-                    if (j < c) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (j + k < c) {
-                                float r;
-                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
-                                const float p = __expf(z - M) * inv;
-                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
-                                acc += g * sv[u][k];
-                                gv[k] = g;
-                                fv[k] = z;
-                            }
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(gr + j) = gv;
-                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < ld; j += 256) {
-            float g = 0.f, fv = 0.f;
-            if (j < c) {
-                float r;
-                const float sv = sr[j];
-                const float z = R.z(sv, wn[j], j, r);
-                const float p = __expf(z - M) * inv;
-                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
-                acc += g * sv;
-                fv = z;
-            }
-            gr[j] = g;
-            if (fr) fr[j] = fv;
-        }
-    }
-    acc = block_sum(acc, sh);
-    if (t == 0) {
-        loss_rows[row] = bad ? NAN : (M + logf(Z)) - T;
-        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
-    }
-}
-
-// The same head with the margin of each row its own (AdaFace; fte.h fte_margin_softmax_rows_fwd_bwd): theta' = theta + a_i clipped
-// to [E, pi - E], t = cos(theta') - b_i.  Inside the clip cos(theta + a) and sin(theta + a) come from c, sin_t and one
-// sincos(a) -- no error of acos enters the logit; acos only decides whether the clip binds.  The per-row work is two scalar
-// loads and one acosf / sincosf; the two passes are margin_softmax_kernel's, statement for statement.  A kernel of its own and
-// not a shared body: with the passes in one inlined function the compiler allocated margin_softmax_kernel's registers
-// differently (2163 -> 2142 instructions for VEC), and that kernel's code is to stay as it is.
-template <bool VEC>
-__global__ __launch_bounds__(256) void margin_softmax_rows_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                                  const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                                  float S, const float* __restrict__ a_rows,
-                                                                  const float* __restrict__ b_rows, float* __restrict__ f,
-                                                                  float* __restrict__ loss_rows, float* __restrict__ G,
-                                                                  float* __restrict__ rowcoef, int c, int ld, float gscale) {
-    constexpr int U = 4;                                        // chunks in flight per thread and trip
-    constexpr float EPS = 1e-12f, E = 1e-3f, PI = 3.14159265358979323846f;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * ld;
-    float* gr = G + (long)row * ld;
-    float* fr = f ? f + (long)row * ld : nullptr;
-    const int yl = labels[row];
-    const float am = a_rows[row], bm = b_rows[row];
-    // out-of-range label or a NaN / infinite margin: NaN row, no out-of-bounds access
-    const bool bad = (unsigned)yl >= (unsigned)c || !(fabsf(am) <= 3.4028234664e38f) || !(fabsf(bm) <= 3.4028234664e38f);
-    const int y = (unsigned)yl >= (unsigned)c ? 0 : yl;
-    const float xr = xn[row];
-    MarginRow R;
-    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
-    R.S = S;
-    R.y = y;
-    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
-    const float th = acosf(cy) + am;
-    float ty, tp;
-    if (th < E) {                                               // the clip binds: constant logit, zero derivative
-        ty = cosf(E) - bm; tp = 0.f;
-    } else if (th > PI - E) {
-        ty = -cosf(E) - bm; tp = 0.f;
-    } else {
-        float sa, ca;
-        sincosf(am, &sa, &ca);
-        const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
-        ty = cy * ca - st * sa - bm;                            // cos(theta + a) - b
-        tp = (st * ca + cy * sa) / fmaxf(st, 1e-6f);            // sin(theta + a) / max(sin_t, 1e-6)
-    }
-    R.zy = S * ty;
-
-    // pass 1: online max / sum of exp
-    float mx = -INFINITY, se = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < c; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    float z[4], r;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
-                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
-                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < c; j += 256) {
-            float r;
-            const float z = R.z(sr[j], wn[j], j, r);
-            if (z > mx) { se *= __expf(mx - z); mx = z; }
-            se += __expf(z - mx);
-        }
-    }
-    const float M = block_max(mx, sh);
-    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
-    const float inv = 1.f / se;
-    const float gS = gscale * S, gT = gscale * S * tp;
-
-    // pass 2: G (and f), sum of G * s
-    float acc = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < ld; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < ld) {
-                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
-                    if (j < c) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (j + k < c) {
-                                float r;
-                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
-                                const float p = __expf(z - M) * inv;
-                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
-                                acc += g * sv[u][k];
-                                gv[k] = g;
-                                fv[k] = z;
-                            }
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(gr + j) = gv;
-                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < ld; j += 256) {
-            float g = 0.f, fv = 0.f;
-            if (j < c) {
-                float r;
-                const float sv = sr[j];
-                const float z = R.z(sv, wn[j], j, r);
-                const float p = __expf(z - M) * inv;
-                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
-                acc += g * sv;
-                fv = z;
-            }
-            gr[j] = g;
-            if (fr) fr[j] = fv;
-        }
-    }
-    acc = block_sum(acc, sh);
-    if (t == 0) {
-        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
-        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
-    }
-}
-
-// CurricularFace (fte.h fte_curricular_softmax_fwd_bwd): ArcFace's target column, and a negative column whose cosine exceeds the
-// margined target cosine u_i (a HARD negative) gets the logit S c (t + c) instead of S c, derivative S (t + 2 c); t and the mask
-// are constants of the gradient.  The per-element work over margin_softmax_kernel's is one compare against u and one fma; pass 2
-// carries the derivative factor beside z.  t is one scalar load per block.  The two passes are margin_softmax_kernel's, statement
-// for statement; a kernel of its own for the reason given at margin_softmax_rows_kernel.
-struct CurricularRow {
-    float ix, S, zy, u, t;
+// CurricularFace: a negative column whose cosine exceeds the margined target cosine u (a HARD negative; NaN is never hard) gets
+// the logit S c (t + c), derivative S (t + 2 c)
+struct CurricularLogit {
+    float S, zy, u, t;
     int y;
-    // the logit of column j and d = (dz/dc) / S of a negative column (1, or t + 2c where the column is hard; NaN is never hard)
-    __device__ __forceinline__ float z(float sv, float wv, int j, float& r, float& d) const {
-        r = ix * __builtin_amdgcn_rcpf(wv);
-        const float cv = clamp1(sv * r);
-        const bool hard = cv > u;
-        d = hard ? t + 2.f * cv : 1.f;
-        return j == y ? zy : S * (hard ? cv * (t + cv) : cv);
-    }
-    __device__ __forceinline__ float z(float sv, float wv, int j) const {
-        float r, d;
-        return z(sv, wv, j, r, d);
+    __device__ __forceinline__ float z(float cb, int j, float& d) const {
+        const bool hard = cb > u;
+        d = hard ? t + 2.f * cb : 1.f;
+        return j == y ? zy : S * (hard ? cb * (t + cb) : cb);
     }
 };
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void curricular_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                                 const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                                 float S, float m, const float* __restrict__ t_used,
-                                                                 float* __restrict__ f, float* __restrict__ loss_rows,
-                                                                 float* __restrict__ G, float* __restrict__ rowcoef, int c, int ld,
-                                                                 float gscale) {
-    constexpr int U = 4;                                        // chunks in flight per thread and trip
-    constexpr float EPS = 1e-12f;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * ld;
-    float* gr = G + (long)row * ld;
-    float* fr = f ? f + (long)row * ld : nullptr;
-    const int yl = labels[row];
-    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
-    const int y = bad ? 0 : yl;
-    const float xr = xn[row];
-    CurricularRow R;
-    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
-    R.S = S;
-    R.y = y;
-    R.t = t_used[0];
-    // target term and mask threshold, once per row; u = cos(theta + m) on both sides of the fallback
-    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
-    const float cm = cosf(m), sm = sinf(m);
-    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
-    R.u = cy * cm - st * sm;
-    float ty = cy, tp = 1.f;
-    if (m > 0.f) {
-        if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
-            ty = R.u;
-            tp = cm + sm * cy / fmaxf(st, 1e-6f);
-        } else {
-            ty = cy - m * sm;                                   // easy_margin = False fallback
-        }
-    }
-    R.zy = S * ty;
-
-    // pass 1: online max / sum of exp
-    float mx = -INFINITY, se = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < c; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    float z[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k) : -INFINITY;
-                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
-                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < c; j += 256) {
-            const float z = R.z(sr[j], wn[j], j);
-            if (z > mx) { se *= __expf(mx - z); mx = z; }
-            se += __expf(z - mx);
-        }
-    }
-    const float M = block_max(mx, sh);
-    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
-    const float inv = 1.f / se;
-    const float gS = gscale * S, gT = gscale * S * tp;
-
-    // pass 2: G (and f), sum of G * s
-    float acc = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < ld; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < ld) {
-                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
-                    if (j < c) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (j + k < c) {
-                                float r, d;
-                                const float z = R.z(sv[u][k], wv[u][k], j + k, r, d);
-                                const float p = __expf(z - M) * inv;
-                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS * d) * r;
-                                acc += g * sv[u][k];
-                                gv[k] = g;
-                                fv[k] = z;
-                            }
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(gr + j) = gv;
-                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < ld; j += 256) {
-            float g = 0.f, fv = 0.f;
-            if (j < c) {
-                float r, d;
-                const float sv = sr[j];
-                const float z = R.z(sv, wn[j], j, r, d);
-                const float p = __expf(z - M) * inv;
-                g = (j == y ? (p - 1.f) * gT : p * gS * d) * r;
-                acc += g * sv;
-                fv = z;
-            }
-            gr[j] = g;
-            if (fr) fr[j] = fv;
-        }
-    }
-    acc = block_sum(acc, sh);
-    if (t == 0) {
-        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
-        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
-    }
-}
-
-// CurricularFace's t (fte.h fte_curricular_t): the running mean of the batch's target cosines, blended before the logits are formed.
-// ONE block, built like adaface_margins_kernel: every thread gathers c_iy of its strided rows -- curricular_softmax_kernel's
-// expression, so both see the same bits -- and sums in index order; sum and count merge through block_sum in a fixed order (two
-// calls are bit-identical; the count is exact in fp32 below 2^24 rows).  Rows with an out-of-range label are left out of the mean.
-__global__ __launch_bounds__(256) void curricular_t_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                           const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                           float alpha, int update, float* __restrict__ t_state,
-                                                           float* __restrict__ t_used, int n, int c, int ld) {
-    constexpr float EPS = 1e-12f;
-    __shared__ float sh[4];
-    const int t = threadIdx.x;
-    float acc = 0.f, cnt = 0.f;
-    if (update) {
-        for (int i = t; i < n; i += 256) {
-            const int y = labels[i];
-            if ((unsigned)y < (unsigned)c) {
-                const float ix = 1.f / fmaxf(xn[i], EPS);
-                acc += clamp1(s[(long)i * ld + y] * (ix * __builtin_amdgcn_rcpf(wn[y])));
-                cnt += 1.f;
-            }
-        }
-    }
-    acc = block_sum(acc, sh);
-    cnt = block_sum(cnt, sh);
-    if (t == 0) {
-        const float t0 = t_state[0];
-        const float tn = update && cnt > 0.f ? alpha * (acc / cnt) + (1.f - alpha) * t0 : t0;
-        t_used[0] = tn;
-        if (update && cnt > 0.f) t_state[0] = tn;
-    }
-}
-
-// MagFace (fte.h fte_magface_softmax_fwd_bwd): ArcFace's target column with the margin of each row a linear function of its
-// clamped norm, mu = l_m + k_m (a - l_a), and the regulariser g = a / u_a^2 + 1 / a per row.  Unlike AdaFace's, the margin is NOT
-// a constant of the gradient: d loss / d a -- the target logit through mu, plus lambda_g g'(a) -- goes into rowcoef as one more
-// term, dLda / xn, where the clamp does not bind; G keeps ArcFace's form.  mu needs no batch statistic, so this is ONE launch.
-// The per-row work is one sincosf and p_iy once more at the end; the two passes are margin_softmax_kernel's, statement for
-// statement; a kernel of its own for the reason given at margin_softmax_rows_kernel.
-template <bool VEC>
-__global__ __launch_bounds__(256) void magface_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                              const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                              float S, float l_a, float u_a, float l_m, float k_m, float lambda_g,
-                                                              float* __restrict__ f, float* __restrict__ loss_rows,
-                                                              float* __restrict__ reg_rows, float* __restrict__ G,
-                                                              float* __restrict__ rowcoef, int c, int ld, float gscale) {
-    constexpr int U = 4;                                        // chunks in flight per thread and trip
-    constexpr float EPS = 1e-12f;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * ld;
-    float* gr = G + (long)row * ld;
-    float* fr = f ? f + (long)row * ld : nullptr;
-    const int yl = labels[row];
-    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
-    const int y = bad ? 0 : yl;
-    const float xr = xn[row];
-    MarginRow R;
-    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
-    R.S = S;
-    R.y = y;
-    // the row's margin from its clamped norm, then the target term and its derivative in mu, once per row
-    const float a = fminf(fmaxf(xr, l_a), u_a);
-    const float mu = l_m + k_m * (a - l_a);
-    float sm, cm;
-    sincosf(mu, &sm, &cm);
-    const float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
-    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
-    float ty, tp, tmu;
-    if (cy > -cm) {                                             // cos(pi - mu) = -cos mu: theta + mu <= pi
-        ty = cy * cm - st * sm;
-        tp = cm + sm * cy / fmaxf(st, 1e-6f);
-        tmu = -(st * cm + cy * sm);
-    } else {
-        ty = cy - mu * sm;                                      // easy_margin = False fallback
-        tp = 1.f;
-        tmu = -(sm + mu * cm);
-    }
-    R.zy = S * ty;
-
-    // pass 1: online max / sum of exp
-    float mx = -INFINITY, se = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < c; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    float z[4], r;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) z[k] = j + k < c ? R.z(sv[u][k], wv[u][k], j + k, r) : -INFINITY;
-                    const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-                    if (m4 > mx) { se *= __expf(mx - m4); mx = m4; }
-                    se += (__expf(z[0] - mx) + __expf(z[1] - mx)) + (__expf(z[2] - mx) + __expf(z[3] - mx));
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < c; j += 256) {
-            float r;
-            const float z = R.z(sr[j], wn[j], j, r);
-            if (z > mx) { se *= __expf(mx - z); mx = z; }
-            se += __expf(z - mx);
-        }
-    }
-    const float M = block_max(mx, sh);
-    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
-    const float inv = 1.f / se;
-    const float gS = gscale * S, gT = gscale * S * tp;
-
-    // pass 2: G (and f), sum of G * s
-    float acc = 0.f;
-    if (VEC) {
-        for (int b = 4 * t; b < ld; b += 1024 * U) {
-            f32x4 sv[U], wv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-                    sv[u] = *reinterpret_cast<const f32x4*>(sr + j);
-                    if (j + 4 <= c) wv[u] = *reinterpret_cast<const f32x4*>(wn + j);
-                    else for (int k = 0; k < 4; ++k) wv[u][k] = j + k < c ? wn[j + k] : 1.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < ld) {
-                    f32x4 gv = {0.f, 0.f, 0.f, 0.f}, fv = {0.f, 0.f, 0.f, 0.f};
-                    if (j < c) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (j + k < c) {
-                                float r;
-                                const float z = R.z(sv[u][k], wv[u][k], j + k, r);
-                                const float p = __expf(z - M) * inv;
-                                const float g = (j + k == y ? (p - 1.f) * gT : p * gS) * r;
-                                acc += g * sv[u][k];
-                                gv[k] = g;
-                                fv[k] = z;
-                            }
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(gr + j) = gv;
-                    if (fr) *reinterpret_cast<f32x4*>(fr + j) = fv;
-                }
-            }
-        }
-    } else {
-        for (int j = t; j < ld; j += 256) {
-            float g = 0.f, fv = 0.f;
-            if (j < c) {
-                float r;
-                const float sv = sr[j];
-                const float z = R.z(sv, wn[j], j, r);
-                const float p = __expf(z - M) * inv;
-                g = (j == y ? (p - 1.f) * gT : p * gS) * r;
-                acc += g * sv;
-                fv = z;
-            }
-            gr[j] = g;
-            if (fr) fr[j] = fv;
-        }
-    }
-    acc = block_sum(acc, sh);
-    if (t == 0) {
-        // d loss / d a: the target logit through mu, and the regulariser; zero where the clamp binds (torch's clamp: bounds included)
-        const float py = __expf(R.zy - M) * inv;
-        const float ia = 1.f / a;
-        const bool in = xr >= l_a && xr <= u_a;
-        const float da = in ? gscale * (S * (py - 1.f) * tmu * k_m + lambda_g * (1.f / (u_a * u_a) - ia * ia)) : 0.f;
-        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
-        reg_rows[row] = bad ? NAN : a / (u_a * u_a) + ia;
-        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix + da * R.ix : 0.f);
-    }
-}
-
-// Sub-center head (fte.h fte_subcenter_margin_softmax_fwd_bwd): K centres per class in K planes of ld columns, centre k of class j
-// at column k * ld + j; s / G rows are K * ld wide, f rows ld.  The class cosine is the max over the K planes, the LOWEST k winning
-// a tie (strict > from plane 0 up; a NaN in plane 0 stays), and the two passes are margin_softmax_kernel's on the pooled cosine,
-// statement for statement: with K = 1 the results are the same bits.  Pass 2 writes the winner's plane and 0.0f into the others.
-// K is a template parameter (the planes of a chunk sit in registers, no scratch); the chunks in flight shrink as K grows so that
-// a thread holds at most 8 s / wn chunk pairs.  A kernel of its own for the reason given at margin_softmax_rows_kernel.
-struct PoolRow {
-    float ix, S, zy;
-    int y;
-    // cosine to one centre, and the winner so far (c, its r = ix / wn and its s)
-    __device__ __forceinline__ void first(float sv, float wv, float& cb, float& rb, float& sb) const {
-        rb = ix * __builtin_amdgcn_rcpf(wv);
-        cb = clamp1(sv * rb);
-        sb = sv;
-    }
-    __device__ __forceinline__ bool next(float sv, float wv, float& cb, float& rb, float& sb) const {
-        const float r = ix * __builtin_amdgcn_rcpf(wv);
-        const float ck = clamp1(sv * r);
-        const bool win = ck > cb;
-        if (win) { cb = ck; rb = r; sb = sv; }
-        return win;
-    }
-    __device__ __forceinline__ float z(float cb, int j) const { return j == y ? zy : S * cb; }
-};
-
-template <int K, bool VEC>
-__global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
-                                                                       const float* __restrict__ wn, const int32_t* __restrict__ labels,
-                                                                       float S, float m, float m3, float* __restrict__ f,
-                                                                       float* __restrict__ loss_rows, float* __restrict__ G,
-                                                                       float* __restrict__ rowcoef, int c, int ld, float gscale) {
-    constexpr int U = K <= 2 ? 4 : (K <= 4 ? 2 : 1);            // chunks (of K planes) in flight per thread and trip
-    constexpr float EPS = 1e-12f;
-    __shared__ float sh[4];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* sr = s + (long)row * K * ld;
-    float* gr = G + (long)row * K * ld;
-    float* fr = f ? f + (long)row * ld : nullptr;
-    const int yl = labels[row];
-    const bool bad = (unsigned)yl >= (unsigned)c;              // out-of-range label: NaN row, no out-of-bounds access
-    const int y = bad ? 0 : yl;
-    const float xr = xn[row];
-    PoolRow R;
-    R.ix = bad ? NAN : 1.f / fmaxf(xr, EPS);
-    R.S = S;
-    R.y = y;
-    // target term, once per row, on the pooled target cosine
-    float cy = clamp1(sr[y] * (R.ix * __builtin_amdgcn_rcpf(wn[y])));
+// The class cosine of one column: the max over its K centres, the LOWEST k winning a tie (strict > from plane 0 up; a NaN in plane
+// 0 stays).  In: the column's s and wn of every plane; out: the winner's cosine, its r = ix / wn, its s and its plane.
+template <int K>
+__device__ __forceinline__ int pool_planes(float ix, const float (&sk)[K], const float (&wk)[K], float& cb, float& rb, float& sb) {
+    sb = sk[0];
+    rb = ix * __builtin_amdgcn_rcpf(wk[0]);
+    cb = clamp1(sb * rb);
+    int kw = 0;
 #pragma unroll
     for (int k = 1; k < K; ++k) {
-        const float ck = clamp1(sr[(long)k * ld + y] * (R.ix * __builtin_amdgcn_rcpf(wn[(long)k * ld + y])));
-        if (ck > cy) cy = ck;
+        const float r = ix * __builtin_amdgcn_rcpf(wk[k]);
+        const float ck = clamp1(sk[k] * r);
+        const bool win = ck > cb;
+        cb = win ? ck : cb;
+        rb = win ? r : rb;
+        sb = win ? sk[k] : sb;
+        kw = win ? k : kw;
     }
-    float ty = cy - m3, tp = 1.f;
-    if (m > 0.f) {
-        const float cm = cosf(m), sm = sinf(m);
-        if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
-            const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
-            ty = cy * cm - st * sm - m3;
-            tp = cm + sm * cy / fmaxf(st, 1e-6f);
-        } else {
-            ty = cy - m * sm - m3;                              // easy_margin = False fallback
+    return kw;
+}
+// one column's s and wn of the K planes, from a trip's chunks and from memory
+template <int K>
+__device__ __forceinline__ void column_of(const f32x4 (&sv)[K], const f32x4 (&wv)[K], int q, float (&sk)[K], float (&wk)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) { sk[k] = sv[k][q]; wk[k] = wv[k][q]; }
+}
+template <int K>
+__device__ __forceinline__ void column_of(const float* sr, const float* wn, int ld, int j, float (&sk)[K], float (&wk)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) { sk[k] = sr[(long)k * ld + j]; wk[k] = wn[(long)k * ld + j]; }
+}
+
+// the U chunks of a trip that start below c, all K planes of each (wn beyond c reads as 1)
+template <int K, int U>
+__device__ __forceinline__ void load_chunks(const float* sr, const float* wn, int b, int c, int ld, f32x4 (&sv)[U][K], f32x4 (&wv)[U][K]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int j = b + 1024 * u;
+        if (j < c) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                sv[u][k] = *reinterpret_cast<const f32x4*>(sr + (long)k * ld + j);
+                if (j + 4 <= c) wv[u][k] = *reinterpret_cast<const f32x4*>(wn + (long)k * ld + j);
+                else for (int q = 0; q < 4; ++q) wv[u][k][q] = j + q < c ? wn[(long)k * ld + j + q] : 1.f;
+            }
         }
     }
-    R.zy = S * ty;
-    const float off = bad ? NAN : 0.f;                          // the centres that did not win: 0, NaN in a NaN row
+}
 
-    // pass 1: online max / sum of exp over the pooled logits
+struct MaxSum {
+    float M, se;                                                // the row's max logit and its sum of exp against that max
+};
+template <int K, bool VEC, class Logit>
+__device__ __forceinline__ MaxSum margin_pass1(const float* sr, const float* wn, float ix, const Logit& L, int c, int ld, float* sh) {
+    constexpr int U = margin_chunks(K);
+    const int t = threadIdx.x;
     float mx = -INFINITY, se = 0.f;
     if (VEC) {
         for (int b = 4 * t; b < c; b += 1024 * U) {
             f32x4 sv[U][K], wv[U][K];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        sv[u][k] = *reinterpret_cast<const f32x4*>(sr + (long)k * ld + j);
-                        if (j + 4 <= c) wv[u][k] = *reinterpret_cast<const f32x4*>(wn + (long)k * ld + j);
-                        else for (int q = 0; q < 4; ++q) wv[u][k][q] = j + q < c ? wn[(long)k * ld + j + q] : 1.f;
-                    }
-                }
-            }
+            load_chunks<K, U>(sr, wn, b, c, ld, sv, wv);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int j = b + 1024 * u;
@@ -1487,11 +696,10 @@ __global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const flo
                     for (int q = 0; q < 4; ++q) {
                         z[q] = -INFINITY;
                         if (j + q < c) {
-                            float cb, rb, sb;
-                            R.first(sv[u][0][q], wv[u][0][q], cb, rb, sb);
-#pragma unroll
-                            for (int k = 1; k < K; ++k) R.next(sv[u][k][q], wv[u][k][q], cb, rb, sb);
-                            z[q] = R.z(cb, j + q);
+                            float sk[K], wk[K], cb, rb, sb, d;
+                            column_of<K>(sv[u], wv[u], q, sk, wk);
+                            pool_planes<K>(ix, sk, wk, cb, rb, sb);
+                            z[q] = L.z(cb, j + q, d);
                         }
                     }
                     const float m4 = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
@@ -1502,37 +710,41 @@ __global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const flo
         }
     } else {
         for (int j = t; j < c; j += 256) {
-            float cb, rb, sb;
-            R.first(sr[j], wn[j], cb, rb, sb);
-#pragma unroll
-            for (int k = 1; k < K; ++k) R.next(sr[(long)k * ld + j], wn[(long)k * ld + j], cb, rb, sb);
-            const float z = R.z(cb, j);
+            float sk[K], wk[K], cb, rb, sb, d;
+            column_of<K>(sr, wn, ld, j, sk, wk);
+            pool_planes<K>(ix, sk, wk, cb, rb, sb);
+            const float z = L.z(cb, j, d);
             if (z > mx) { se *= __expf(mx - z); mx = z; }
             se += __expf(z - mx);
         }
     }
     const float M = block_max(mx, sh);
-    se = block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh);
-    const float inv = 1.f / se;
-    const float gS = gscale * S, gT = gscale * S * tp;
+    return {M, block_sum(mx == -INFINITY ? 0.f : se * __expf(mx - M), sh)};
+}
 
-    // pass 2: G of the winning centre (0 in the others; and f), sum of G * s
+// G of one column (before it goes to the winner's plane) with p = exp(z - M) * inv; z comes back for f
+template <class Logit>
+__device__ __forceinline__ float margin_grad(const Logit& L, float cb, float rb, int j, float M, float inv, float gS, float gT, float& z) {
+    float d;
+    z = L.z(cb, j, d);
+    const float p = __expf(z - M) * inv;
+    return (j == L.y ? (p - 1.f) * gT : p * gS * d) * rb;
+}
+// Writes G -- the winner's plane, off (0, NaN in a NaN row) into the other planes, 0 from c up to ld -- and f where wanted;
+// returns the block's sum of G * s.  G and f come whole and the row's pointers are formed here: formed by the caller, K = 4 kept a
+// 64-bit address per plane and stream in VGPRs through the loop (144 instead of 120, a wave per SIMD less).
+template <int K, bool VEC, class Logit>
+__device__ __forceinline__ float margin_pass2(const float* sr, const float* wn, float ix, const Logit& L, float M, float inv, float gS,
+                                              float gT, float off, float* G, float* f, int row, int c, int ld, float* sh) {
+    constexpr int U = margin_chunks(K);
+    float* gr = G + (long)row * K * ld;
+    float* fr = f ? f + (long)row * ld : nullptr;
+    const int t = threadIdx.x;
     float acc = 0.f;
     if (VEC) {
         for (int b = 4 * t; b < ld; b += 1024 * U) {
             f32x4 sv[U][K], wv[U][K];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = b + 1024 * u;
-                if (j < c) {
-#pragma unroll
-                    for (int k = 0; k < K; ++k) {
-                        sv[u][k] = *reinterpret_cast<const f32x4*>(sr + (long)k * ld + j);
-                        if (j + 4 <= c) wv[u][k] = *reinterpret_cast<const f32x4*>(wn + (long)k * ld + j);
-                        else for (int q = 0; q < 4; ++q) wv[u][k][q] = j + q < c ? wn[(long)k * ld + j + q] : 1.f;
-                    }
-                }
-            }
+            load_chunks<K, U>(sr, wn, b, c, ld, sv, wv);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int j = b + 1024 * u;
@@ -1544,14 +756,10 @@ __global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const flo
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             if (j + q < c) {
-                                float cb, rb, sb;
-                                int kw = 0;
-                                R.first(sv[u][0][q], wv[u][0][q], cb, rb, sb);
-#pragma unroll
-                                for (int k = 1; k < K; ++k) if (R.next(sv[u][k][q], wv[u][k][q], cb, rb, sb)) kw = k;
-                                const float z = R.z(cb, j + q);
-                                const float p = __expf(z - M) * inv;
-                                const float g = (j + q == y ? (p - 1.f) * gT : p * gS) * rb;
+                                float sk[K], wk[K], cb, rb, sb, z;
+                                column_of<K>(sv[u], wv[u], q, sk, wk);
+                                const int kw = pool_planes<K>(ix, sk, wk, cb, rb, sb);
+                                const float g = margin_grad(L, cb, rb, j + q, M, inv, gS, gT, z);
                                 acc += g * sb;
 #pragma unroll
                                 for (int k = 0; k < K; ++k) gv[k][q] = k == kw ? g : off;
@@ -1570,25 +778,309 @@ __global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const flo
             float g = 0.f, fv = 0.f;
             int kw = 0;
             if (j < c) {
-                float cb, rb, sb;
-                R.first(sr[j], wn[j], cb, rb, sb);
-#pragma unroll
-                for (int k = 1; k < K; ++k) if (R.next(sr[(long)k * ld + j], wn[(long)k * ld + j], cb, rb, sb)) kw = k;
-                const float z = R.z(cb, j);
-                const float p = __expf(z - M) * inv;
-                g = (j == y ? (p - 1.f) * gT : p * gS) * rb;
+                float sk[K], wk[K], cb, rb, sb;
+                column_of<K>(sr, wn, ld, j, sk, wk);
+                kw = pool_planes<K>(ix, sk, wk, cb, rb, sb);
+                g = margin_grad(L, cb, rb, j, M, inv, gS, gT, fv);
                 acc += g * sb;
-                fv = z;
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) gr[(long)k * ld + j] = k == kw ? g : (j < c ? off : 0.f);
             if (fr) fr[j] = fv;
         }
     }
+    return block_sum(acc, sh);
+}
+
+// ArcFace / CosFace on K centres per class (fte.h fte_subcenter_margin_softmax_fwd_bwd): centre k of class j at column k * ld + j;
+// s / G rows are K * ld wide, f rows ld.  The target term is taken on the pooled target cosine.  K = 1 is the plain head.
+template <int K, bool VEC>
+__device__ __forceinline__ void margin_softmax_row(const float* s, const float* xn, const float* wn, const int32_t* labels, float S, float m,
+                                                   float m3, float* f, float* loss_rows, float* G, float* rowcoef, int c, int ld,
+                                                   float gscale) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x;
+    const float* sr = s + (long)row * K * ld;
+    const float xr = xn[row];
+    const MarginRowId I = margin_row_id(labels[row], c, xr);
+    float cy = target_cos(sr, wn, I.y, I.ix);
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        const float ck = target_cos(sr + (long)k * ld, wn + (long)k * ld, I.y, I.ix);
+        if (ck > cy) cy = ck;
+    }
+    float ty, tp;
+    arc_target(cy, m, m3, ty, tp);
+    const PlainLogit L = {S, S * ty, I.y};
+    const MaxSum P = margin_pass1<K, VEC>(sr, wn, I.ix, L, c, ld, sh);
+    const float acc = margin_pass2<K, VEC>(sr, wn, I.ix, L, P.M, 1.f / P.se, gscale * S, gscale * S * tp, I.bad ? NAN : 0.f,
+                                           G, f, row, c, ld, sh);
+    if (threadIdx.x == 0) {
+        loss_rows[row] = margin_loss(I.bad, P.M, P.se, L.zy);
+        rowcoef[row] = margin_rowcoef(I.bad, xr, acc, I.ix);
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                             const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                             float S, float m, float m3, float* __restrict__ f,
+                                                             float* __restrict__ loss_rows, float* __restrict__ G,
+                                                             float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    margin_softmax_row<1, VEC>(s, xn, wn, labels, S, m, m3, f, loss_rows, G, rowcoef, c, ld, gscale);
+}
+template <int K, bool VEC>
+__global__ __launch_bounds__(256) void subcenter_margin_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                       const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                       float S, float m, float m3, float* __restrict__ f,
+                                                                       float* __restrict__ loss_rows, float* __restrict__ G,
+                                                                       float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    margin_softmax_row<K, VEC>(s, xn, wn, labels, S, m, m3, f, loss_rows, G, rowcoef, c, ld, gscale);
+}
+
+// ------------------------------------------------------------------------------------
+// The plain head with the classes split over R ranks (fte.h "Sharded margin head"): this rank holds columns class_lo .. class_lo + c
+// of the classifier, the labels are global.  A row whose label another shard owns has no target column here (y = -1 matches none,
+// zy = 0).  Two kernels:
+//   margin_shard_stats_kernel   pass 1 alone -> (max, sum of exp against that max, target logit or 0) per row;
+//   margin_shard_fwd_bwd_kernel merges the R triples IN RANK ORDER (every rank gets the same M, Z, T and so the same loss bits),
+//                               then pass 2 with p = exp(z - M) / Z.
+// ------------------------------------------------------------------------------------
+struct ShardRow {
+    float ix, zy, tp;
+    int y;
+    bool bad;
+};
+__device__ __forceinline__ ShardRow shard_row(const float* sr, const float* wn, int yl, int lo, int c, int num_classes, float xr, float S,
+                                              float m, float m3) {
+    ShardRow Q;
+    Q.bad = (unsigned)yl >= (unsigned)num_classes;            // out-of-range label: NaN row on every shard, no out-of-bounds access
+    const bool own = !Q.bad && yl >= lo && yl - lo < c;
+    Q.ix = margin_ix(Q.bad, xr);
+    Q.y = own ? yl - lo : -1;
+    Q.zy = 0.f;
+    Q.tp = 1.f;
+    if (own) {
+        float ty;
+        arc_target(target_cos(sr, wn, Q.y, Q.ix), m, m3, ty, Q.tp);
+        Q.zy = S * ty;
+    }
+    return Q;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_shard_stats_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                 const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                 int lo, int num_classes, float S, float m, float m3,
+                                                                 float* __restrict__ stats, int n, int c, int ld) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x;
+    const float* sr = s + (long)row * ld;
+    const ShardRow Q = shard_row(sr, wn, labels[row], lo, c, num_classes, xn[row], S, m, m3);
+    const MaxSum P = margin_pass1<1, VEC>(sr, wn, Q.ix, PlainLogit{S, Q.zy, Q.y}, c, ld, sh);
+    if (threadIdx.x == 0) {
+        stats[row] = Q.bad ? NAN : P.M;
+        stats[(long)n + row] = Q.bad ? NAN : P.se;
+        stats[2 * (long)n + row] = Q.bad ? NAN : Q.zy;       // 0 where another shard owns the label
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_shard_fwd_bwd_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                   const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                   int lo, int num_classes, float S, float m, float m3,
+                                                                   const float* __restrict__ all_stats, int ranks, float* __restrict__ f,
+                                                                   float* __restrict__ loss_rows, float* __restrict__ G,
+                                                                   float* __restrict__ rowcoef, int n, int c, int ld, float gscale) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x;
+    const float* sr = s + (long)row * ld;
+    const float xr = xn[row];
+    const ShardRow Q = shard_row(sr, wn, labels[row], lo, c, num_classes, xr, S, m, m3);
+    // the R triples of the row, in rank order (every thread reads the same addresses: one broadcast load each)
+    float M = -INFINITY, Z = 0.f, T = 0.f;
+    bool bad = Q.bad;
+    for (int r = 0; r < ranks; ++r) {
+        const float mr = all_stats[((long)r * 3) * n + row];
+        bad = bad || mr != mr;                                  // fmaxf would drop a NaN
+        M = fmaxf(M, mr);
+    }
+    for (int r = 0; r < ranks; ++r) {
+        const float* a = all_stats + ((long)r * 3) * n + row;
+        const float er = a[n], tr = a[2 * (long)n];
+        bad = bad || er != er || tr != tr;
+        Z += er * expf(a[0] - M);
+        T += tr;
+    }
+    // the NaN row of the dense contract: z, p and g below c are NaN
+    const float ix = bad ? NAN : Q.ix;
+    const PlainLogit L = {S, bad ? NAN : Q.zy, Q.y};
+    const float acc = margin_pass2<1, VEC>(sr, wn, ix, L, M, 1.f / Z, gscale * S, gscale * S * Q.tp, 0.f, G, f, row,
+                                           c, ld, sh);
+    if (threadIdx.x == 0) {
+        loss_rows[row] = margin_loss(bad, M, Z, T);
+        rowcoef[row] = margin_rowcoef(bad, xr, acc, ix);
+    }
+}
+
+// The plain head with the margin of each row its own (AdaFace; fte.h fte_margin_softmax_rows_fwd_bwd): theta' = theta + a_i clipped
+// to [E, pi - E], t = cos(theta') - b_i.  Inside the clip cos(theta + a) and sin(theta + a) come from c, sin_t and one
+// sincos(a) -- no error of acos enters the logit; acos only decides whether the clip binds.  The per-row work is two scalar
+// loads and one acosf / sincosf.  A NaN or infinite margin makes the row a NaN row as an out-of-range label does.
+template <bool VEC>
+__global__ __launch_bounds__(256) void margin_softmax_rows_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                  const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                  float S, const float* __restrict__ a_rows,
+                                                                  const float* __restrict__ b_rows, float* __restrict__ f,
+                                                                  float* __restrict__ loss_rows, float* __restrict__ G,
+                                                                  float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    constexpr float E = 1e-3f, PI = 3.14159265358979323846f;
+    __shared__ float sh[4];
+    const int row = blockIdx.x;
+    const float* sr = s + (long)row * ld;
+    const float am = a_rows[row], bm = b_rows[row];
+    const float xr = xn[row];
+    const MarginRowId I = margin_row_id(labels[row], c, xr, !(fabsf(am) <= 3.4028234664e38f) || !(fabsf(bm) <= 3.4028234664e38f));
+    const float cy = target_cos(sr, wn, I.y, I.ix);
+    const float th = acosf(cy) + am;
+    float ty, tp;
+    if (th < E) {                                               // the clip binds: constant logit, zero derivative
+        ty = cosf(E) - bm; tp = 0.f;
+    } else if (th > PI - E) {
+        ty = -cosf(E) - bm; tp = 0.f;
+    } else {
+        float sa, ca;
+        sincosf(am, &sa, &ca);
+        const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+        ty = cy * ca - st * sa - bm;                            // cos(theta + a) - b
+        tp = (st * ca + cy * sa) / fmaxf(st, 1e-6f);            // sin(theta + a) / max(sin_t, 1e-6)
+    }
+    const PlainLogit L = {S, S * ty, I.y};
+    const MaxSum P = margin_pass1<1, VEC>(sr, wn, I.ix, L, c, ld, sh);
+    const float acc = margin_pass2<1, VEC>(sr, wn, I.ix, L, P.M, 1.f / P.se, gscale * S, gscale * S * tp, 0.f, G, f, row,
+                                           c, ld, sh);
+    if (threadIdx.x == 0) {
+        loss_rows[row] = margin_loss(I.bad, P.M, P.se, L.zy);
+        rowcoef[row] = margin_rowcoef(I.bad, xr, acc, I.ix);
+    }
+}
+
+// CurricularFace (fte.h fte_curricular_softmax_fwd_bwd): ArcFace's target column and CurricularLogit on the negatives; t and the
+// mask are constants of the gradient.  t is one scalar load per block.  cos m, sin m and sin_t are formed whatever m is: the mask
+// threshold u = cos(theta + m) holds on both sides of the fallback.
+template <bool VEC>
+__global__ __launch_bounds__(256) void curricular_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                                 const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                                 float S, float m, const float* __restrict__ t_used,
+                                                                 float* __restrict__ f, float* __restrict__ loss_rows,
+                                                                 float* __restrict__ G, float* __restrict__ rowcoef, int c, int ld,
+                                                                 float gscale) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x;
+    const float* sr = s + (long)row * ld;
+    const float xr = xn[row];
+    const MarginRowId I = margin_row_id(labels[row], c, xr);
+    const float cy = target_cos(sr, wn, I.y, I.ix);
+    const float cm = cosf(m), sm = sinf(m);
+    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+    const float u = cy * cm - st * sm;
+    float ty = cy, tp = 1.f;
+    if (m > 0.f) {
+        if (cy > -cm) {                                         // cos(pi - m) = -cos m: theta + m <= pi
+            ty = u;
+            tp = cm + sm * cy / fmaxf(st, 1e-6f);
+        } else {
+            ty = cy - m * sm;                                   // easy_margin = False fallback
+        }
+    }
+    const CurricularLogit L = {S, S * ty, u, t_used[0], I.y};
+    const MaxSum P = margin_pass1<1, VEC>(sr, wn, I.ix, L, c, ld, sh);
+    const float acc = margin_pass2<1, VEC>(sr, wn, I.ix, L, P.M, 1.f / P.se, gscale * S, gscale * S * tp, 0.f, G, f, row,
+                                           c, ld, sh);
+    if (threadIdx.x == 0) {
+        loss_rows[row] = margin_loss(I.bad, P.M, P.se, L.zy);
+        rowcoef[row] = margin_rowcoef(I.bad, xr, acc, I.ix);
+    }
+}
+
+// CurricularFace's t (fte.h fte_curricular_t): the running mean of the batch's target cosines, blended before the logits are formed.
+// ONE block, built like adaface_margins_kernel: every thread gathers c_iy of its strided rows -- target_cos, as
+// curricular_softmax_kernel takes it, so both see the same bits -- and sums in index order; sum and count merge through block_sum
+// in a fixed order (two calls are bit-identical; the count is exact in fp32 below 2^24 rows).  Rows with an out-of-range label are
+// left out of the mean.
+__global__ __launch_bounds__(256) void curricular_t_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                           const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                           float alpha, int update, float* __restrict__ t_state,
+                                                           float* __restrict__ t_used, int n, int c, int ld) {
+    __shared__ float sh[4];
+    const int t = threadIdx.x;
+    float acc = 0.f, cnt = 0.f;
+    if (update) {
+        for (int i = t; i < n; i += 256) {
+            const int y = labels[i];
+            if ((unsigned)y < (unsigned)c) {
+                acc += target_cos(s + (long)i * ld, wn, y, margin_ix(false, xn[i]));
+                cnt += 1.f;
+            }
+        }
+    }
     acc = block_sum(acc, sh);
+    cnt = block_sum(cnt, sh);
     if (t == 0) {
-        loss_rows[row] = bad ? NAN : (M + logf(se)) - R.zy;
-        rowcoef[row] = bad ? NAN : (xr > EPS ? -acc * R.ix * R.ix : 0.f);
+        const float t0 = t_state[0];
+        const float tn = update && cnt > 0.f ? alpha * (acc / cnt) + (1.f - alpha) * t0 : t0;
+        t_used[0] = tn;
+        if (update && cnt > 0.f) t_state[0] = tn;
+    }
+}
+
+// MagFace (fte.h fte_magface_softmax_fwd_bwd): ArcFace's target column with the margin of each row a linear function of its
+// clamped norm, mu = l_m + k_m (a - l_a), and the regulariser g = a / u_a^2 + 1 / a per row.  Unlike AdaFace's, the margin is NOT
+// a constant of the gradient: d loss / d a -- the target logit through mu, plus lambda_g g'(a) -- goes into rowcoef as one more
+// term, dLda / xn, where the clamp does not bind; G keeps ArcFace's form.  mu needs no batch statistic, so this is ONE launch.
+// The per-row work is one sincosf (no m > 0 guard: mu is the row's own) and p_iy once more at the end.
+template <bool VEC>
+__global__ __launch_bounds__(256) void magface_softmax_kernel(const float* __restrict__ s, const float* __restrict__ xn,
+                                                              const float* __restrict__ wn, const int32_t* __restrict__ labels,
+                                                              float S, float l_a, float u_a, float l_m, float k_m, float lambda_g,
+                                                              float* __restrict__ f, float* __restrict__ loss_rows,
+                                                              float* __restrict__ reg_rows, float* __restrict__ G,
+                                                              float* __restrict__ rowcoef, int c, int ld, float gscale) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x;
+    const float* sr = s + (long)row * ld;
+    const float xr = xn[row];
+    const MarginRowId I = margin_row_id(labels[row], c, xr);
+    // the row's margin from its clamped norm, then the target term and its derivative in mu, once per row
+    const float a = fminf(fmaxf(xr, l_a), u_a);
+    const float mu = l_m + k_m * (a - l_a);
+    float sm, cm;
+    sincosf(mu, &sm, &cm);
+    const float cy = target_cos(sr, wn, I.y, I.ix);
+    const float st = sqrtf(fmaxf((1.f - cy) * (1.f + cy), 0.f));
+    float ty, tp, tmu;
+    if (cy > -cm) {                                             // cos(pi - mu) = -cos mu: theta + mu <= pi
+        ty = cy * cm - st * sm;
+        tp = cm + sm * cy / fmaxf(st, 1e-6f);
+        tmu = -(st * cm + cy * sm);
+    } else {
+        ty = cy - mu * sm;                                      // easy_margin = False fallback
+        tp = 1.f;
+        tmu = -(sm + mu * cm);
+    }
+    const PlainLogit L = {S, S * ty, I.y};
+    const MaxSum P = margin_pass1<1, VEC>(sr, wn, I.ix, L, c, ld, sh);
+    const float inv = 1.f / P.se;
+    const float acc = margin_pass2<1, VEC>(sr, wn, I.ix, L, P.M, inv, gscale * S, gscale * S * tp, 0.f, G, f, row,
+                                           c, ld, sh);
+    if (threadIdx.x == 0) {
+        // d loss / d a: the target logit through mu, and the regulariser; zero where the clamp binds (torch's clamp: bounds included)
+        const float py = __expf(L.zy - P.M) * inv;
+        const float ia = 1.f / a;
+        const bool in = xr >= l_a && xr <= u_a;
+        const float da = in ? gscale * (S * (py - 1.f) * tmu * k_m + lambda_g * (1.f / (u_a * u_a) - ia * ia)) : 0.f;
+        loss_rows[row] = margin_loss(I.bad, P.M, P.se, L.zy);
+        reg_rows[row] = I.bad ? NAN : a / (u_a * u_a) + ia;
+        rowcoef[row] = I.bad ? NAN : (xr > MARGIN_EPS ? -acc * I.ix * I.ix + da * I.ix : 0.f);
     }
 }
 
@@ -2192,16 +1684,21 @@ hipError_t k_asoftmax(const float* s, const float* xn, const float* wn, const in
     hipLaunchKernelGGL(asoftmax_kernel, dim3(n), dim3(256), 0, st, s, xn, wn, labels, lam, f, loss_rows, G, rowcoef, c, ld, gs);
     return hipGetLastError();
 }
+// the margin heads' VEC kernels: ld % 4 == 0 and 16-byte bases (a null f or G counts as aligned) -- every row, and every plane
+// k * ld of the sub-center head's s / wn / G, then starts on 16 bytes
+static bool margin_vec(int ld, const float* s, const float* wn, const float* G, const float* f) {
+    return ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+}
 hipError_t k_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m, float m3,
                             float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs, hipStream_t st) {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, G, f);
     if (vec) hipLaunchKernelGGL(margin_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(margin_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, c, ld, gs);
     return hipGetLastError();
 }
 hipError_t k_margin_shard_stats(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes,
                                 float scale, float m, float m3, float* stats, int n, int c, int ld, hipStream_t st) {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, nullptr, nullptr);
     if (vec) hipLaunchKernelGGL(margin_shard_stats_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, stats, n, c, ld);
     else hipLaunchKernelGGL(margin_shard_stats_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, stats, n, c, ld);
     return hipGetLastError();
@@ -2209,7 +1706,7 @@ hipError_t k_margin_shard_stats(const float* s, const float* xn, const float* wn
 hipError_t k_margin_shard_fwd_bwd(const float* s, const float* xn, const float* wn, const int32_t* labels, int class_lo, int num_classes,
                                   float scale, float m, float m3, const float* all_stats, int R, float* f, float* loss_rows, float* G,
                                   float* rowcoef_part, int n, int c, int ld, float gs, hipStream_t st) {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, G, f);
     if (vec) hipLaunchKernelGGL(margin_shard_fwd_bwd_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, all_stats, R, f, loss_rows, G, rowcoef_part, n, c, ld, gs);
     else hipLaunchKernelGGL(margin_shard_fwd_bwd_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, class_lo, num_classes, scale, m, m3, all_stats, R, f, loss_rows, G, rowcoef_part, n, c, ld, gs);
     return hipGetLastError();
@@ -2217,7 +1714,7 @@ hipError_t k_margin_shard_fwd_bwd(const float* s, const float* xn, const float* 
 hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, const float* a_rows,
                                  const float* b_rows, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
                                  hipStream_t st) {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, G, f);
     if (vec) hipLaunchKernelGGL(margin_softmax_rows_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(margin_softmax_rows_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, a_rows, b_rows, f, loss_rows, G, rowcoef, c, ld, gs);
     return hipGetLastError();
@@ -2225,7 +1722,7 @@ hipError_t k_margin_softmax_rows(const float* s, const float* xn, const float* w
 hipError_t k_curricular_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float m,
                                 const float* t_used, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
                                 hipStream_t st) {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, G, f);
     if (vec) hipLaunchKernelGGL(curricular_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(curricular_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, m, t_used, f, loss_rows, G, rowcoef, c, ld, gs);
     return hipGetLastError();
@@ -2233,7 +1730,7 @@ hipError_t k_curricular_softmax(const float* s, const float* xn, const float* wn
 hipError_t k_magface_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, float scale, float l_a, float u_a,
                              float l_m, float u_m, float lambda_g, float* f, float* loss_rows, float* reg_rows, float* G, float* rowcoef,
                              int n, int c, int ld, float gs, hipStream_t st) {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, G, f);
     const float k_m = (u_m - l_m) / (u_a - l_a);
     if (vec) hipLaunchKernelGGL(magface_softmax_kernel<true>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, l_a, u_a, l_m, k_m, lambda_g, f, loss_rows, reg_rows, G, rowcoef, c, ld, gs);
     else hipLaunchKernelGGL(magface_softmax_kernel<false>, dim3(n), dim3(256), 0, st, s, xn, wn, labels, scale, l_a, u_a, l_m, k_m, lambda_g, f, loss_rows, reg_rows, G, rowcoef, c, ld, gs);
@@ -2253,8 +1750,7 @@ static void subcenter_launch(bool vec, const float* s, const float* xn, const fl
 hipError_t k_subcenter_margin_softmax(const float* s, const float* xn, const float* wn, const int32_t* labels, int K, float scale, float m,
                                       float m3, float* f, float* loss_rows, float* G, float* rowcoef, int n, int c, int ld, float gs,
                                       hipStream_t st) {
-    // ld % 4 == 0 and aligned bases: every plane k * ld of s / wn / G starts on 16 bytes, and so does every row (stride K * ld)
-    const bool vec = ld % 4 == 0 && ((uintptr_t)s | (uintptr_t)wn | (uintptr_t)G | (uintptr_t)f) % 16 == 0;
+    const bool vec = margin_vec(ld, s, wn, G, f);
 #define FTE_SUBCENTER_K(k) case k: subcenter_launch<k>(vec, s, xn, wn, labels, scale, m, m3, f, loss_rows, G, rowcoef, n, c, ld, gs, st); break;
     switch (K) {
         FTE_SUBCENTER_K(1) FTE_SUBCENTER_K(2) FTE_SUBCENTER_K(3) FTE_SUBCENTER_K(4)
