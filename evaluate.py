@@ -29,6 +29,9 @@ def build_parser():
     parser.add_argument('--flip_flag', type=bool, default=False, help='Unused in the reference as well.')
     parser.add_argument('--data_list_path', type=str, help='Path to the list of testing data.')
     parser.add_argument('--batch_size', type=int, default=256, help='Number of images to process in a batch.')
+    parser.add_argument('--landmark_list_path', type=str, default=None,
+                        help='`path x1 y1 ... x5 y5` per line for every image of --data_list_path: five-point alignment to --input_height x '
+                             '--input_width in place of the resize (train.py --landmark_list_path).')
     parser.add_argument('--data_format', type=str, default='NCHW', help='net_select default (evaluate.py:62).')
     return parser
 
@@ -42,7 +45,8 @@ def evaluate(FLAGS):
     device = torch.device('cuda', 0)
     torch.cuda.set_device(device)
     next_images, num_images = eval_inputs(FLAGS.data_list_path, batch_size=FLAGS.batch_size, input_height=FLAGS.input_height,
-                                          input_width=FLAGS.input_width, is_color=FLAGS.is_color, device=device)
+                                          input_width=FLAGS.input_width, is_color=FLAGS.is_color, device=device,
+                                          landmark_list_path=getattr(FLAGS, 'landmark_list_path', None))
     tag = FLAGS.net_name + '_' + FLAGS.model_name
     latest = saver.latest_checkpoint(os.path.join(FLAGS.model_dir, tag))
     if not latest:

@@ -240,6 +240,29 @@ int fte_preprocess_u8_aug(const uint8_t* slots, float* out, int n, long slot_str
 size_t fte_preprocess_u8_geo_ws_bytes(int n, int channels, int crop_h, int crop_w);
 int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
                           int crop_w, const float* affine_table, void* ws, size_t ws_bytes, void* stream);
+/* Five-point face alignment in place of the resize (train.py / evaluate.py --landmark_list_path): the aligned in_h x in_w image
+ * is a similarity warp of the decoded image, and the stages are warp over the crop window, flip, colour (words 6..9, as
+ * fte_preprocess_u8_aug; hd[6] == 0 is the identity, bits 8 and 16 are ignored), (x - 0.5) / 0.5.  Same arguments and refusals
+ * as fte_preprocess_u8_aug (FTE_EINVAL: channels not 1 / 3, a crop larger than the input, a slot stride that is not a multiple
+ * of 64 or smaller than the header).  An aligned slot has a 128-byte header:
+ *   hd[0..15]  as fte_preprocess_u8_aug, with h0, w0 = the shape of the WINDOW of the decoded image that the slot carries
+ *              (preprocessing.align_window: the bounding box of the aligned image's corners in the source, padded by 2 pixels
+ *              and clamped to the image); y0 / x0 = the crop's corner in the ALIGNED image
+ *   hd[16..21] float32 bits of m6 = (a0, a1, a2, b0, b1, b2): the inverse similarity, translation relative to the window's corner
+ *   hd[22..31] 0
+ * followed by the window's h0 x w0 x channels bytes (mode 0) or the finished float32 crop (mode 1: copied from byte 128; a crop
+ * that does not fit the slot reads 0).  Output pixel (x, y), coordinates of the aligned image BEFORE the flip, reads
+ *   sx = (a0 x + a1 y) + a2, sy = (b0 x + b1 y) + b2;  fx = floor(sx), fy = floor(sy), cx = fx + 1, cy = fy + 1;
+ *   top = (cx - sx) R(fy, fx) + (sx - fx) R(fy, cx);  bot = (cx - sx) R(cy, fx) + (sx - fx) R(cy, cx);
+ *   out = (cy - sy) top + (sy - fy) bot;  R = byte * (1 / 255) inside the window, 0 outside;
+ *   a pixel NONE of whose four taps lies inside the window is 0 (the formula's own value for finite coordinates).
+ * Every operation is float32 and rounds on its own.  Words 16..21, h0 and w0 steer addresses and are NOT trusted: whether a tap
+ * lies inside [0, w0 - 1] x [0, h0 - 1] is decided on the float coordinates before any conversion to int (a NaN, an infinity or
+ * an out-of-range value reads 0, so such a pixel is 0 and the output -1), the converted index is clamped into the window, and
+ * with h0 < 1, w0 < 1 or h0 * w0 * channels > slot_stride - 128 every tap reads 0.  y0, x0 and flip only enter arithmetic.
+ * Every value is bit-equal to the host aligned transform (tf_face_toolbox_amd/preprocessing.py: align_window, align_warp). */
+int fte_preprocess_u8_align(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
+                            int crop_w, void* stream);
 
 /* ---------------------------------------------------------------------------
  * layers.batch_norm(scale=True, center=True, fused=True, decay=0.999, epsilon=1e-3) in TRAINING mode

@@ -76,13 +76,39 @@ def _load(path, num_channels):
     return a.reshape(a.shape[0], a.shape[1], num_channels)
 
 
-def decode(path, num_channels, height, width):
-    """tf.read_file + decode_jpeg(channels) + convert_image_dtype(float32) + resize_images (data.py:208-213)."""
+def _aligned(raw, landmarks, path, height, width, y0=0, win_h=None, x0=0, win_w=None):
+    """the aligned height x width image (its window) in place of the resized one: preprocessing.aligned_image; a refusal
+    names the image"""
+    from .preprocessing import aligned_image
+    try:
+        return aligned_image(raw, landmarks, height, width, y0, win_h, x0, win_w)
+    except ValueError as e:
+        raise ValueError('%s: %s' % (path, e))
+
+
+def decode(path, num_channels, height, width, landmarks=None):
+    """tf.read_file + decode_jpeg(channels) + convert_image_dtype(float32) + resize_images (data.py:208-213).  landmarks (10
+    numbers): five-point alignment to height x width in place of the resize."""
+    if landmarks is not None:
+        return _aligned(_load(path, num_channels), landmarks, path, height, width)
     return resize_window(_load(path, num_channels), height, width)
 
 
-def _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng):
-    if crop_height != -1 and crop_width != -1:                      # tf.random_crop: only the cropped window is resized
+GEO_WITH_LANDMARKS = ('the geometric augmentation (augmentation & 2) is not available together with landmarks: the aligned '
+                      'transform supports augmentation 0 and 1')
+
+
+def _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks=None, path=None):
+    if landmarks is not None:                                       # alignment replaces the resize; the draws are the same
+        if augmentation & 2:
+            raise ValueError(GEO_WITH_LANDMARKS)
+        if crop_height != -1 and crop_width != -1:
+            y0 = rng.integers(0, input_height - crop_height + 1)
+            x0 = rng.integers(0, input_width - crop_width + 1)
+            image = _aligned(raw, landmarks, path, input_height, input_width, int(y0), crop_height, int(x0), crop_width)
+        else:
+            image = _aligned(raw, landmarks, path, input_height, input_width)
+    elif crop_height != -1 and crop_width != -1:                    # tf.random_crop: only the cropped window is resized
         y0 = rng.integers(0, input_height - crop_height + 1)
         x0 = rng.integers(0, input_width - crop_width + 1)
         image = resize_window(raw, input_height, input_width, y0, crop_height, x0, crop_width)
@@ -99,8 +125,8 @@ def _finish(raw, input_height, input_width, crop_height, crop_width, augmentatio
     return (np.ascontiguousarray(image, dtype=np.float32) - 0.5) / 0.5
 
 
-def train_example(path, num_channels, input_height, input_width, crop_height, crop_width, augmentation, rng):
-    return _finish(_load(path, num_channels), input_height, input_width, crop_height, crop_width, augmentation, rng)
+def train_example(path, num_channels, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks=None):
+    return _finish(_load(path, num_channels), input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
 
 
 HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip}, the augmentation's {flags, float32 brightness,
@@ -108,14 +134,62 @@ HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip},
 #                              fte_preprocess_u8_aug, fte_preprocess_u8_geo)
 
 
-def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0):
+ALIGN_HEADER_BYTES = 128     # per ALIGNED raw slot: the 16 words above with h0, w0 = the shape of the source window, words 16..21 =
+#                              float32 bits of the inverse similarity m6, words 22..31 = 0 (include/fte.h: fte_preprocess_u8_align)
+
+
+def _raw_aligned(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, landmarks):
+    """raw_example() with landmarks: the WINDOW of the decoded image that the aligned image reads (preprocessing.align_window),
+    the draws and the inverse similarity into an aligned slot; fte_preprocess_u8_align warps, flips, colours and normalises."""
+    from .preprocessing import align_window
+    if augmentation & 2:
+        raise ValueError(GEO_WITH_LANDMARKS)
+    raw = _load(path, num_channels)
+    cropped = crop_height != -1 and crop_width != -1
+    out_h, out_w = (crop_height, crop_width) if cropped else (input_height, input_width)
+    hd = slot[:ALIGN_HEADER_BYTES].view(np.int32)
+    hd[:] = 0
+    try:
+        wy0, wx0, wh, ww, m6 = align_window(landmarks, raw.shape[0], raw.shape[1], input_height, input_width)
+    except ValueError as e:
+        raise ValueError('%s: %s' % (path, e))
+    if wh * ww * num_channels > slot.size - ALIGN_HEADER_BYTES:
+        if rng is None:
+            image = (_aligned(raw, landmarks, path, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
+        else:
+            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
+        slot[ALIGN_HEADER_BYTES:ALIGN_HEADER_BYTES + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
+        hd[:6] = (1, out_h, out_w, 0, 0, 0)
+        return
+    y0 = x0 = flip = 0
+    if rng is not None:
+        if cropped:
+            y0 = int(rng.integers(0, input_height - crop_height + 1))
+            x0 = int(rng.integers(0, input_width - crop_width + 1))
+        if augmentation & 1:
+            from .preprocessing import augmentation_draws
+            flip, flags, brightness, hue, saturation = augmentation_draws(rng, num_channels)
+            hd[6] = flags
+            hd[7:10].view(np.float32)[:] = (brightness, hue, saturation)
+        else:
+            flip = int(rng.random() < 0.5)
+    window = raw[wy0:wy0 + wh, wx0:wx0 + ww]
+    slot[ALIGN_HEADER_BYTES:ALIGN_HEADER_BYTES + window.size] = window.reshape(-1)
+    hd[:6] = (0, wh, ww, y0, x0, flip)
+    hd[16:22].view(np.float32)[:] = m6
+
+
+def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0, landmarks=None):
     """The DECODED image and the draws of train_example() (seeded the same way, drawn in the same order) into one slot of a raw
     batch buffer -- resize / crop / flip / normalise then run on the GPU (fte_preprocess_u8) and give the bits train_example()
     gives.  rng None: the evaluation transform (full window, no flip).  An image too large for its slot is transformed here
     and stored finished (mode 1).  augmentation: the draws of preprocessing.data_augmentation as well (header words 6..9: flag
     bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug.
     augmentation & 2: the geometric pair's draws too (word 6 bits 8 = zoom applied, 16 = affine; words 10..12 = the zoom's target
-    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo."""
+    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo.  landmarks (10 numbers): an ALIGNED slot instead
+    (_raw_aligned: 128-byte header, the source window, fte_preprocess_u8_align); None: everything above, unchanged."""
+    if landmarks is not None:
+        return _raw_aligned(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, landmarks)
     raw = _load(path, num_channels)
     h0, w0 = raw.shape[:2]
     cropped = crop_height != -1 and crop_width != -1
@@ -171,21 +245,22 @@ def fill_rows(task):
     """(buffer, batch shape, [(row, path, seed), ...], num_channels, in_h, in_w, crop_h, crop_w, augmentation[, raw]): decode the
     listed images (seed None: the evaluation transform) into rows of the shared batch buffer -- a float32 array of finished
     examples, or with raw = 1 a uint8 array [rows, slot bytes] of decoded images + draws (the colour augmentation's included) for
-    the GPU transform.  Returns the number of rows written (errors propagate)."""
+    the GPU transform.  A row may carry a fourth item, the image's 10 landmark numbers: it is aligned instead of resized (an
+    aligned raw slot has the 128-byte header).  Returns the number of rows written (errors propagate)."""
     name, shape, rows, num_channels, in_h, in_w, crop_h, crop_w, augmentation = task[:9]
     raw = len(task) > 9 and task[9]
     if raw:
         batch = _buffer(name, shape, np.uint8)
-        for row, path, seed in rows:
+        for row, path, seed, *lm in rows:
             raw_example(batch[row], path, num_channels, in_h, in_w, crop_h, crop_w, None if seed is None else np.random.default_rng(seed),
-                        augmentation)
+                        augmentation, *lm)
         return len(rows)
     batch = _buffer(name, shape, np.float32)
-    for row, path, seed in rows:
+    for row, path, seed, *lm in rows:
         if seed is None:                          # evaluation: decode + resize + normalise, nothing random (data.py:153-191)
-            batch[row] = (decode(path, num_channels, in_h, in_w) - np.float32(0.5)) / np.float32(0.5)
+            batch[row] = (decode(path, num_channels, in_h, in_w, *lm) - np.float32(0.5)) / np.float32(0.5)
         else:
-            batch[row] = train_example(path, num_channels, in_h, in_w, crop_h, crop_w, augmentation, np.random.default_rng(seed))
+            batch[row] = train_example(path, num_channels, in_h, in_w, crop_h, crop_w, augmentation, np.random.default_rng(seed), *lm)
     return len(rows)
 
 

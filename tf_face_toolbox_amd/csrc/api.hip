@@ -1306,6 +1306,13 @@ int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_str
     return rc(k_preprocess_u8_geo(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, affine_table, ws, (hipStream_t)stream));
 }
 
+int fte_preprocess_u8_align(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
+                            void* stream) {
+    if (!slots || !out || n <= 0 || (channels != 1 && channels != 3) || in_h <= 0 || in_w <= 0 || crop_h <= 0 || crop_w <= 0 ||
+        crop_h > in_h || crop_w > in_w || slot_stride < 128 || slot_stride % 64 || n > 65535) return FTE_EINVAL;
+    return rc(k_preprocess_u8_align(slots, out, n, slot_stride, channels, crop_h, crop_w, (hipStream_t)stream));
+}
+
 // ------------------------------------------------------------------------------------------------
 // grouped 3x3 conv, SE-gate pieces
 // fte.h: c / groups in {4, 8, 16, 32}; any other width is refused here, before a launcher sees it

@@ -77,3 +77,5 @@ hipError_t k_preprocess_u8_aug(const unsigned char* slots, float* out, int n, lo
 size_t k_preprocess_u8_geo_ws_bytes(int n, int channels, int crop_h, int crop_w);
 hipError_t k_preprocess_u8_geo(const unsigned char* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w,
                                int crop_h, int crop_w, const float* table, void* ws, hipStream_t st);
+hipError_t k_preprocess_u8_align(const unsigned char* slots, float* out, int n, long slot_stride, int channels, int crop_h, int crop_w,
+                                 hipStream_t st);

@@ -2338,3 +2338,85 @@ hipError_t k_preprocess_u8_geo(const unsigned char* slots, float* out, int n, lo
 #undef FTE_GEO
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// five-point alignment in place of the resize (tf_face_toolbox_amd/preprocessing.py: align_window, align_warp): the worker
+// hands over a WINDOW of the decoded image -- the part the aligned in_h x in_w image can read -- and the inverse similarity
+// relative to that window's corner; the crop of the aligned image is warped straight from the window's bytes, then flipped,
+// coloured (words 6..9, the tail of preprocess_u8_aug_kernel) and normalised.  Slot: a 128-byte header -- int32 words 0..15 as
+// above with h0, w0 = the window's shape, words 16..21 = float32 bits of (a0, a1, a2, b0, b1, b2) -- then h0 x w0 x C bytes
+// (mode 0) or the finished float32 crop (mode 1).  The warp is the AFFINE stage's formula on the window: output pixel (x, y) of
+// the aligned image reads (sx, sy) = ((a0 x + a1 y) + a2, (b0 x + b1 y) + b2), zero outside the window; a pixel none of whose
+// four taps lies inside is 0 (what the formula gives for finite coordinates; it settles the others).
+//
+// One thread per output pixel like preprocess_u8_kernel, not one workgroup per image like the geometric kernel: nothing is
+// staged and a pixel's 4 taps of C bytes are its only reads, so the simplest mapping was taken.  Neighbouring lanes' taps are
+// (a0, b0) source pixels apart: how many window rows, i.e. cache lines, a wave's 64 pixels touch grows with |b0| (rotation x
+// scale) -- two rows for an upright face, about 30 at (a0, b0) = (1.72, 0.46).  The launch measured 3x the plain resize's at that
+// matrix (profiles/align_loader.md); which part of the kernel carries the factor was not measured and the mapping is not tuned.
+// Words 16..21, h0 and w0 steer addresses and are not trusted: a tap is inside only if its FLOAT coordinates lie in
+// [0, w0 - 1] x [0, h0 - 1] (false for a NaN), decided before any conversion to int; the float is clamped to int's range before
+// it is converted and the index is clamped into the window after (floats above 2^24 round); a window with h0 < 1, w0 < 1 or
+// more than slot_stride - 128 bytes is not read at all.
+constexpr int ALIGN_HEADER = 128;
+
+template <int C>
+__global__ __launch_bounds__(256) void preprocess_u8_align_kernel(const unsigned char* __restrict__ slots, float* __restrict__ out, long slot_stride,
+                                                                   int crop_h, int crop_w) {
+#pragma clang fp contract(off)     // as in preprocess_u8_kernel: every operation rounds on its own, as numpy's do
+    const int img = blockIdx.y;
+    const unsigned char* slot = slots + (long)img * slot_stride;
+    const int* hd = reinterpret_cast<const int*>(slot);
+    const int mode = hd[0], h0 = hd[1], w0 = hd[2], y0 = hd[3], x0 = hd[4], flip = hd[5], flags = hd[6];
+    const int px = blockIdx.x * 256 + threadIdx.x;
+    if (px >= crop_h * crop_w) return;
+    float* o = out + ((long)img * crop_h * crop_w + px) * C;
+    if (mode == 1) {                              // finished by the worker, augmentation included
+        const float* f = reinterpret_cast<const float*>(slot + ALIGN_HEADER) + (long)px * C;
+        const bool fits = ((long)px + 1) * C * (long)sizeof(float) <= slot_stride - ALIGN_HEADER;      // a crop larger than the slot: zeros
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c] = fits ? f[c] : 0.f;
+        return;
+    }
+    const float delta_b = __int_as_float(hd[7]), delta_h = __int_as_float(hd[8]), factor = __int_as_float(hd[9]);
+    const float a0 = __int_as_float(hd[16]), a1 = __int_as_float(hd[17]), a2 = __int_as_float(hd[18]);
+    const float b0 = __int_as_float(hd[19]), b1 = __int_as_float(hd[20]), b2 = __int_as_float(hd[21]);
+    const bool window = h0 >= 1 && w0 >= 1 && (long)h0 * w0 <= (slot_stride - ALIGN_HEADER) / C;
+    const int r = px / crop_w, cc = px - r * crop_w;
+    const int col = flip ? crop_w - 1 - cc : cc;
+    const float x = (float)(x0 + col), y = (float)(y0 + r);
+    const float sx = (a0 * x + a1 * y) + a2, sy = (b0 * x + b1 * y) + b2;
+    const float fx = floorf(sx), fy = floorf(sy), cx = fx + 1.f, cy = fy + 1.f;
+    const float wl = cx - sx, wr = sx - fx, wt = cy - sy, wb = sy - fy;
+    const float xmax = (float)(w0 - 1), ymax = (float)(h0 - 1);
+    const bool xl = window && fx >= 0.f && fx <= xmax, xr = window && cx >= 0.f && cx <= xmax;          // false for a NaN
+    const bool yt = window && fy >= 0.f && fy <= ymax, yb = window && cy >= 0.f && cy <= ymax;
+    const float imax = 2147483520.f;              // the largest float an int holds: (float)(w0 - 1) is 2^31 for w0 near 2^31
+    const int ixl = xl ? min((int)fminf(fx, imax), w0 - 1) : 0, ixr = xr ? min((int)fminf(cx, imax), w0 - 1) : 0;
+    const int iyt = yt ? min((int)fminf(fy, imax), h0 - 1) : 0, iyb = yb ? min((int)fminf(cy, imax), h0 - 1) : 0;
+    const unsigned char* img0 = slot + ALIGN_HEADER;
+    const unsigned char* ptl = img0 + ((long)iyt * w0 + ixl) * C;
+    const unsigned char* ptr = img0 + ((long)iyt * w0 + ixr) * C;
+    const unsigned char* pbl = img0 + ((long)iyb * w0 + ixl) * C;
+    const unsigned char* pbr = img0 + ((long)iyb * w0 + ixr) * C;
+    const float s = (float)(1.0 / 255.0);
+    const bool any = (yt || yb) && (xl || xr);
+    float v[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float rtl = (yt && xl) ? (float)ptl[c] * s : 0.f, rtr = (yt && xr) ? (float)ptr[c] * s : 0.f;
+        const float rbl = (yb && xl) ? (float)pbl[c] * s : 0.f, rbr = (yb && xr) ? (float)pbr[c] * s : 0.f;
+        const float top = wl * rtl + wr * rtr;
+        const float bot = wl * rbl + wr * rbr;
+        v[c] = any ? wt * top + wb * bot : 0.f;
+    }
+    geo_colour_store<C>(v, flags, delta_b, delta_h, factor, o);
+}
+
+hipError_t k_preprocess_u8_align(const unsigned char* slots, float* out, int n, long slot_stride, int channels, int crop_h, int crop_w,
+                                 hipStream_t st) {
+    const dim3 grid((crop_h * crop_w + 255) / 256, n);
+    if (channels == 3) preprocess_u8_align_kernel<3><<<grid, 256, 0, st>>>(slots, out, slot_stride, crop_h, crop_w);
+    else preprocess_u8_align_kernel<1><<<grid, 256, 0, st>>>(slots, out, slot_stride, crop_h, crop_w);
+    return hipGetLastError();
+}

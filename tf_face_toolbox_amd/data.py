@@ -47,42 +47,41 @@ def usable_cpus():
 
 
 # ------------------------------------------------------------------ list parsers (names kept)
+def _list_entries(list_path):
+    """The entries of a list file: the whitespace-separated tokens of every non-blank line, in order.  An entry's position in
+    this list is its ENTRY INDEX -- the row of the landmark table that belongs to it (preprocessing.read_landmarks is given the
+    paths in this order); the three parsers below all walk the file through here."""
+    with open(os.path.expanduser(list_path), 'r') as f:
+        return [part_line for part_line in (line.split() for line in f) if part_line]
+
+
 def get_image_paths(list_path):
     """data.py:30-41: first whitespace-separated token of every line."""
-    image_paths_flat = []
-    for line in open(os.path.expanduser(list_path), 'r'):
-        part_line = line.split()
-        if part_line:
-            image_paths_flat.append(part_line[0])
+    image_paths_flat = [part_line[0] for part_line in _list_entries(list_path)]
     return image_paths_flat, len(image_paths_flat)
 
 
-def get_image_paths_and_labels(list_path):
-    """data.py:44-58: `path label`, num_classes = max(label)+1."""
+def get_image_paths_and_labels(list_path, with_index=False):
+    """data.py:44-58: `path label`, num_classes = max(label)+1.  with_index: (path, entry index) in place of every path."""
     image_paths_flat, labels_flat = [], []
-    for line in open(os.path.expanduser(list_path), 'r'):
-        part_line = line.split()
-        if not part_line:
-            continue
-        image_paths_flat.append(part_line[0])
+    for k, part_line in enumerate(_list_entries(list_path)):
+        image_paths_flat.append((part_line[0], k) if with_index else part_line[0])
         labels_flat.append(int(part_line[1]))
     return image_paths_flat, labels_flat, len(labels_flat), max(labels_flat) + 1
 
 
-def get_image_paths_and_labels_dict(list_path, num_per_class):
+def get_image_paths_and_labels_dict(list_path, num_per_class, with_index=False):
     """data.py:77-96: per-class path lists for the PxK sampler; classes with fewer than
     num_per_class images are dropped and the survivors are RE-NUMBERED 0..P'-1.  (The reference
     appends a single list when a new label shows up, so labels must first appear in increasing
-    order there -- data.py:84-86; this version grows the table as far as needed instead.)"""
+    order there -- data.py:84-86; this version grows the table as far as needed instead.)
+    with_index: (path, entry index) in place of every path."""
     image_path_list_tmp = []
-    for line in open(os.path.expanduser(list_path), 'r'):
-        part_line = line.split()
-        if not part_line:
-            continue
+    for k, part_line in enumerate(_list_entries(list_path)):
         label_index = int(part_line[1])
         while len(image_path_list_tmp) <= label_index:
             image_path_list_tmp.append([])
-        image_path_list_tmp[label_index].append(part_line[0])
+        image_path_list_tmp[label_index].append((part_line[0], k) if with_index else part_line[0])
     image_path_list = [lst for lst in image_path_list_tmp if len(lst) >= num_per_class]
     return image_path_list, sum(len(lst) for lst in image_path_list), len(image_path_list)
 
@@ -393,7 +392,15 @@ class _BatchSource(object):
         return self.p._cur[1]
 
 
-def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmentation, device):
+def raw_slot_bytes(header_bytes, num_channels, out_h, out_w):
+    """bytes of one raw slot: the header, then room for a decoded image (or, aligned, a source window) of FTE_LOADER_RAW_SIDE^2
+    pixels and for the finished float32 crop; a multiple of 64"""
+    side = int(os.environ.get('FTE_LOADER_RAW_SIDE', '256'))
+    slot = header_bytes + max(side * side * num_channels, out_h * out_w * num_channels * 4)
+    return (slot + 63) // 64 * 64
+
+
+def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmentation, device, align=False):
     """(slot bytes, transform) when the decode workers hand over DECODED uint8 images and the resize / crop / flip / normalise
     runs on the GPU (fte_preprocess_u8: the same bits as the host transform, tests/test_gpu_loader.py), else (0, None).  The
     host transform is 0.6 of the 1.7 ms a 250 x 250 JPEG costs a worker; the decode stays.  With `augmentation` the colour
@@ -401,15 +408,18 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
     with `augmentation & 2` the geometric pair (zoom, affine warp) as well (fte_preprocess_u8_geo, tests/test_gpu_geo_augment.py:
     the affine table is uploaded and the workspace allocated once per loader; the slot size is the same).
     FTE_LOADER_GPU=0 keeps everything on the host.  A slot holds an image of FTE_LOADER_RAW_SIDE^2 pixels
-    (default 256; CASIA-WebFace crops are 250 x 250) -- a larger image is transformed by its worker and handed over finished."""
+    (default 256; CASIA-WebFace crops are 250 x 250) -- a larger image is transformed by its worker and handed over finished.
+    align: aligned slots (128-byte header, the source WINDOW of the face in place of the image) and fte_preprocess_u8_align,
+    which serves augmentation 0 and 1 (tests/test_gpu_align.py)."""
     if num_workers <= 0 or torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0':
         return 0, None
     entry = 'fte_preprocess_u8_geo' if augmentation & 2 else 'fte_preprocess_u8_aug' if augmentation else 'fte_preprocess_u8'
     from . import _lib
     from ._decode_worker import HEADER_BYTES
-    side = int(os.environ.get('FTE_LOADER_RAW_SIDE', '256'))
-    slot = HEADER_BYTES + max(side * side * num_channels, out_h * out_w * num_channels * 4)
-    slot = (slot + 63) // 64 * 64
+    if align:
+        from ._decode_worker import ALIGN_HEADER_BYTES as HEADER_BYTES
+        entry = 'fte_preprocess_u8_align'
+    slot = raw_slot_bytes(HEADER_BYTES, num_channels, out_h, out_w)
 
     extra = ()
     if augmentation & 2:
@@ -430,16 +440,26 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
 # ------------------------------------------------------------------ public input builders
 def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop_width=-1, is_color=1,
                  augmentation=0, batch_size=-1, num_classes=-1, num_per_class=-1, device='cuda', seed=None,
-                 rank=0, world_size=1, num_workers=None):
+                 rank=0, world_size=1, num_workers=None, landmark_list_path=None):
     """data.py:195-281.  Returns {'images', 'labels', 'num_classes', 'num_examples', 'batch_size'};
     images/labels are callables (next batch / its labels).  With world_size > 1 every rank draws the
-    same global batch order (shared seed) and decodes only its own rows [r*B/n, (r+1)*B/n)."""
+    same global batch order (shared seed) and decodes only its own rows [r*B/n, (r+1)*B/n).
+    landmark_list_path (`path x1 y1 ... x5 y5` per line): every image is five-point aligned to input_height x input_width in
+    place of the resize (preprocessing.align_window / align_warp); augmentation 0 and 1 only."""
     num_channels = 3 if is_color else 1
+    landmarks = None
+    if landmark_list_path is not None:
+        if augmentation & 2:
+            from ._decode_worker import GEO_WITH_LANDMARKS
+            raise ValueError(GEO_WITH_LANDMARKS)
+        from .preprocessing import read_landmarks
+        landmarks = read_landmarks(landmark_list_path, get_image_paths(data_list_path)[0])      # float32 [entries of the list, 10]
     rng = np.random.default_rng(seed)
     if batch_size == -1:
         assert num_classes != -1 and num_per_class != -1
         batch_size = num_classes * num_per_class
-        image_label_dict, num_examples_total, num_classes_total = get_image_paths_and_labels_dict(data_list_path, num_per_class)
+        image_label_dict, num_examples_total, num_classes_total = get_image_paths_and_labels_dict(   # with landmarks: (path, entry index)
+            data_list_path, num_per_class, with_index=landmarks is not None)
 
         def _gen():                                                  # data.py:230-242 (_gen_balance)
             work = copy.deepcopy(image_label_dict)
@@ -453,7 +473,8 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
                     for _ in range(num_per_class):
                         yield work[idx].pop(), idx
     else:
-        image_list, label_list, num_examples_total, num_classes_total = get_image_paths_and_labels(data_list_path)
+        image_list, label_list, num_examples_total, num_classes_total = get_image_paths_and_labels(  # with landmarks: (path, entry index)
+            data_list_path, with_index=landmarks is not None)
 
         def _gen():                                                  # data.py:225-228 (_gen_random) + repeat()
             while True:
@@ -474,7 +495,8 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
             # 32 workers 23.8 k, 48 workers 27.1 k images/s (through a staging copy: 24.5 k at 48)
             num_workers = min(max(1, cpu_count() // 2 // max(1, world_size)), 48, shard // 4) if shard >= 64 else 0
     on_gpu = torch.device(device).type == 'cuda'
-    slot, transform = _raw_slots(num_workers, shard, num_channels, input_height, input_width, out_h, out_w, augmentation, device)
+    slot, transform = _raw_slots(num_workers, shard, num_channels, input_height, input_width, out_h, out_w, augmentation, device,
+                                 align=landmarks is not None)
     if slot:
         procs = _WorkerPool(num_workers, (shard, slot), pin=on_gpu, dtype=np.uint8)
     else:
@@ -485,7 +507,10 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
     def draw():
         items = [next(gen) for _ in range(batch_size)][rank * shard:(rank + 1) * shard]
         seeds = rng.integers(0, 2 ** 31, size=batch_size)[rank * shard:(rank + 1) * shard]
-        return items, seeds, np.asarray([lab for _, lab in items], dtype=np.int32)
+        labels = np.asarray([lab for _, lab in items], dtype=np.int32)
+        if landmarks is not None:                        # (path, entry index) -> (path, that entry's 10 numbers)
+            return [(e[0], tuple(landmarks[e[1]].tolist())) for e, _ in items], seeds, labels
+        return [(e,) for e, _ in items], seeds, labels
 
     pending = []                                         # worker processes: batch k + 1 is being decoded while batch k is copied out
 
@@ -493,12 +518,12 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
         if procs is not None:
             while len(pending) < procs.DEPTH:
                 items, seeds, labels = draw()
-                pending.append((procs.submit([(i, it[0], int(sd)) for i, (it, sd) in enumerate(zip(items, seeds))], params), labels))
+                pending.append((procs.submit([(i, it[0], int(sd)) + it[1:] for i, (it, sd) in enumerate(zip(items, seeds))], params), labels))
             ticket, labels = pending.pop(0)
             return procs.wait(ticket), labels
         items, seeds, labels = draw()
         imgs = list(pool.map(lambda a: _train_example(a[0][0], num_channels, input_height, input_width, crop_height,
-                                                      crop_width, augmentation, np.random.default_rng(a[1])),
+                                                      crop_width, augmentation, np.random.default_rng(a[1]), *a[0][1:]),
                              zip(items, seeds)))
         x = np.stack(imgs).reshape(shard, out_h, out_w, num_channels)
         return x, labels
@@ -516,18 +541,24 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
             'pin_fallback': bool(procs is not None and procs.pin_failed), 'gpu_transform': bool(slot)}
 
 
-def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width, device='cuda', num_workers=None):
+def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width, device='cuda', num_workers=None, landmark_list_path=None):
     """data.py:153-191: repeating, in list order, resized, (x-0.5)/0.5.  Returns (next_batch, num_examples).  Batches of 64 or
-    more are decoded by the worker processes train_inputs uses (threads in this process manage ~0.3 k images/s)."""
+    more are decoded by the worker processes train_inputs uses (threads in this process manage ~0.3 k images/s).
+    landmark_list_path: five-point alignment in place of the resize, as in train_inputs."""
     num_channels = 3 if is_color else 1
     image_list, num_examples = get_image_paths(data_list_path)
+    landmarks = None
+    if landmark_list_path is not None:
+        from .preprocessing import read_landmarks
+        landmarks = read_landmarks(landmark_list_path, image_list)
     print('%d images loaded' % num_examples)
     if num_workers is None:
         num_workers = int(os.environ.get('FTE_LOADER_WORKERS', '-1'))
         if num_workers < 0:
             num_workers = min(max(1, cpu_count() // 2), 32, batch_size // 4) if batch_size >= 64 else 0
     on_gpu = torch.device(device).type == 'cuda'
-    slot, transform = _raw_slots(num_workers, batch_size, num_channels, input_height, input_width, input_height, input_width, 0, device)
+    slot, transform = _raw_slots(num_workers, batch_size, num_channels, input_height, input_width, input_height, input_width, 0, device,
+                                 align=landmarks is not None)
     if slot:
         procs = _WorkerPool(num_workers, (batch_size, slot), pin=on_gpu, dtype=np.uint8)
     else:
@@ -538,16 +569,18 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
     pending = []
 
     def draw():
-        paths = [image_list[(state['pos'] + i) % num_examples] for i in range(batch_size)]
+        ks = [(state['pos'] + i) % num_examples for i in range(batch_size)]
         state['pos'] = (state['pos'] + batch_size) % num_examples
-        return paths
+        if landmarks is not None:
+            return [(image_list[k], tuple(landmarks[k].tolist())) for k in ks]
+        return [(image_list[k],) for k in ks]
 
     def make_batch():
         if procs is not None:
             while len(pending) < procs.DEPTH:
-                pending.append(procs.submit([(i, q, None) for i, q in enumerate(draw())], params))
+                pending.append(procs.submit([(i, q[0], None) + q[1:] for i, q in enumerate(draw())], params))
             return procs.wait(pending.pop(0)), None
-        imgs = list(pool.map(lambda q: (_decode(q, num_channels, input_height, input_width) - 0.5) / 0.5, draw()))
+        imgs = list(pool.map(lambda q: (_decode(q[0], num_channels, input_height, input_width, *q[1:]) - 0.5) / 0.5, draw()))
         return np.stack(imgs).astype(np.float32), None
 
     pf = _Prefetcher(make_batch, torch.device(device), pool=procs, transform=transform)

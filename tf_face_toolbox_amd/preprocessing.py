@@ -159,3 +159,136 @@ def geometric_augmentation(image, rng):
     """zoom, then affine, from draws taken here (u, then rnd)"""
     th, tw, rnd = geometric_draws(rng, image.shape[0], image.shape[1])
     return affine_warp(zoom_in_out(np.ascontiguousarray(image, dtype=np.float32), th, tw), AFFINE_TABLE[rnd])
+
+
+# ------------------------------------------------------------------ five-point alignment (not in the reference; DESIGN.md 4.23)
+# The template of ArcFace's norm_crop for a 112 x 112 crop: (x, y) of left eye, right eye, nose, left and right mouth corner,
+# pixel centres at integer coordinates (the cv2.warpAffine convention).
+ALIGN_TEMPLATE_112 = np.array([[38.2946, 51.6963], [73.5318, 51.5014], [56.0252, 71.7366], [41.5493, 92.3655], [70.7299, 92.2041]],
+                              dtype=np.float64)
+
+
+def align_template(in_h, in_w):
+    """The template for an in_h x in_w crop: scaled by s = in_h / 112 and centred along x.  112 x 96: the SphereFace template
+    (x - 8); 112 x 112: ALIGN_TEMPLATE_112 itself."""
+    s = in_h / 112.0
+    t = ALIGN_TEMPLATE_112 * s
+    t[:, 0] += (in_w - 112.0 * s) / 2.0
+    return t
+
+
+def similarity_from_landmarks(src5, dst5):
+    """The least-squares non-reflective similarity that maps src to dst, as a float64 [2, 3] matrix [[a, -b, tx], [b, a, ty]]:
+    with centred points p (src) and q (dst), a = sum(p . q) / sum|p|^2, b = sum(p x q) / sum|p|^2, t = mean(q) - M mean(p).
+    Points that (nearly) coincide have no similarity: ValueError."""
+    src = np.asarray(src5, dtype=np.float64).reshape(-1, 2)
+    dst = np.asarray(dst5, dtype=np.float64).reshape(-1, 2)
+    ms, md = src.mean(0), dst.mean(0)
+    p, q = src - ms, dst - md
+    den = (p * p).sum()
+    if not den >= 1e-12 * max(1.0, (ms * ms).sum()):              # (a NaN landmark is refused here too)
+        raise ValueError('landmarks coincide (spread %g): no similarity maps them to the template' % den)
+    a = (p * q).sum() / den
+    b = (p[:, 0] * q[:, 1] - p[:, 1] * q[:, 0]).sum() / den
+    m = np.array([[a, -b], [b, a]])
+    return np.concatenate([m, (md - m @ ms)[:, None]], 1)
+
+
+def align_window(landmarks, h0, w0, in_h, in_w):
+    """(wy0, wx0, wh, ww, m6) for an h0 x w0 image with the given five landmarks (10 numbers, source pixels): the window of the
+    image that the aligned in_h x in_w crop can read -- the bounding box of the crop's four corners under the INVERSE similarity
+    (float64), padded by 2 pixels and clamped to the image -- and the float32 inverse (a0, a1, a2, b0, b1, b2), its translation
+    relative to the window's corner (subtracted in float64, then rounded): aligned pixel (x, y) reads the window at
+    (a0 x + a1 y + a2, b0 x + b1 y + b2).  No intersection: a 1 x 1 window at (0, 0), which the warp leaves nearly everywhere.
+    The window is part of the definition on the host and on the GPU: it is what lets a large frame with a small face fit a
+    raw slot."""
+    fwd = similarity_from_landmarks(landmarks, align_template(in_h, in_w))
+    a, b = fwd[0, 0], fwd[1, 0]
+    det = a * a + b * b
+    if not (det > 0.0 and np.isfinite(det)):
+        raise ValueError('the similarity from the landmarks to the template is singular (scale^2 = %g)' % det)
+    inv = np.array([[a, b], [-b, a]]) / det
+    t = -inv @ fwd[:, 2]
+    corners = np.array([[0, 0], [in_w - 1, 0], [0, in_h - 1], [in_w - 1, in_h - 1]], dtype=np.float64)
+    src = corners @ inv.T + t
+    if not np.isfinite(src).all():
+        raise ValueError('the similarity from the landmarks to the template is singular (scale^2 = %g)' % det)
+    x_lo, y_lo = np.floor(src.min(0)) - 2
+    x_hi, y_hi = np.ceil(src.max(0)) + 2
+    x_lo, y_lo, x_hi, y_hi = max(x_lo, 0), max(y_lo, 0), min(x_hi, w0 - 1), min(y_hi, h0 - 1)
+    if x_lo > x_hi or y_lo > y_hi:
+        wy0, wx0, wh, ww = 0, 0, 1, 1
+    else:
+        wy0, wx0, wh, ww = int(y_lo), int(x_lo), int(y_hi - y_lo) + 1, int(x_hi - x_lo) + 1
+    m6 = np.array([inv[0, 0], inv[0, 1], t[0] - wx0, inv[1, 0], inv[1, 1], t[1] - wy0]).astype(np.float32)
+    return wy0, wx0, wh, ww, m6
+
+
+def align_warp(window, m6, in_h, in_w, y0=0, win_h=None, x0=0, win_w=None):
+    """Rows [y0, y0 + win_h) x columns [x0, x0 + win_w) of the aligned in_h x in_w image, warped from `window` (float32 in [0, 1],
+    HWC: the source window of align_window, converted as _decode_worker._load's image is) by affine_warp's formula: aligned pixel
+    (x, y) reads (sx, sy) = ((a0 x + a1 y) + a2, (b0 x + b1 y) + b2); with f = floor, c = f + 1:
+    top = (cx - sx) R(fy, fx) + (sx - fx) R(fy, cx), bot the same on row cy, out = (cy - sy) top + (sy - fy) bot; R is 0 outside the
+    window.  Float32, every operation rounded on its own.  A pixel NONE of whose four taps lies inside the window is 0: what the
+    formula gives whenever the coordinates are finite, and the rule for the others (include/fte.h: fte_preprocess_u8_align)."""
+    h, w, _ = window.shape
+    win_h = in_h if win_h is None else win_h
+    win_w = in_w if win_w is None else win_w
+    a0, a1, a2, b0, b1, b2 = (np.float32(v) for v in m6)
+    x = np.arange(x0, x0 + win_w).astype(np.float32)[None, :]
+    y = np.arange(y0, y0 + win_h).astype(np.float32)[:, None]
+    with np.errstate(invalid='ignore', over='ignore'):
+        sx = (a0 * x + a1 * y) + a2
+        sy = (b0 * x + b1 * y) + b2
+        fx, fy = np.floor(sx), np.floor(sy)
+        cx, cy = fx + np.float32(1), fy + np.float32(1)
+        xl, xr = (fx >= 0) & (fx <= w - 1), (cx >= 0) & (cx <= w - 1)          # false for NaN as well
+        yt, yb = (fy >= 0) & (fy <= h - 1), (cy >= 0) & (cy <= h - 1)
+
+        def read(yy, xx, ok):
+            yi = np.where(ok, yy, 0).astype(np.int64)
+            xi = np.where(ok, xx, 0).astype(np.int64)
+            return np.where(ok[:, :, None], window[yi, xi], np.float32(0))
+        wl, wr = (cx - sx)[:, :, None], (sx - fx)[:, :, None]
+        top = wl * read(fy, fx, yt & xl) + wr * read(fy, cx, yt & xr)
+        bot = wl * read(cy, fx, yb & xl) + wr * read(cy, cx, yb & xr)
+        out = (cy - sy)[:, :, None] * top + (sy - fy)[:, :, None] * bot
+    out = np.where(((yt | yb) & (xl | xr))[:, :, None], out, np.float32(0))
+    assert out.dtype == np.float32
+    return out
+
+
+def aligned_image(raw, landmarks, in_h, in_w, y0=0, win_h=None, x0=0, win_w=None):
+    """The host aligned transform up to the flip: decoded uint8 HWC image + landmarks -> the float32 [0, 1] window
+    [y0, y0 + win_h) x [x0, x0 + win_w) of the aligned in_h x in_w image."""
+    wy0, wx0, wh, ww, m6 = align_window(landmarks, raw.shape[0], raw.shape[1], in_h, in_w)
+    window = raw[wy0:wy0 + wh, wx0:wx0 + ww].astype(np.float32) * np.float32(1.0 / 255.0)
+    return align_warp(window, m6, in_h, in_w, y0, win_h, x0, win_w)
+
+
+def read_landmarks(landmark_list_path, image_paths):
+    """The landmark file (`path x1 y1 ... x5 y5` per line: source pixels of left eye, right eye, nose, left and right mouth
+    corner) as a float32 [len(image_paths), 10] array in the order of image_paths.  ValueError for a malformed line (its number)
+    and for listed images without landmarks (the first one and how many)."""
+    import os
+    table = {}
+    with open(os.path.expanduser(landmark_list_path), 'r') as f:
+        for num, line in enumerate(f, 1):
+            part = line.split()
+            if not part:
+                continue
+            try:
+                vals = np.asarray([float(v) for v in part[1:]], dtype=np.float32)
+            except ValueError:
+                vals = None
+            if vals is None or vals.size != 10 or not np.isfinite(vals).all():
+                raise ValueError('%s, line %d: expected `path x1 y1 x2 y2 x3 y3 x4 y4 x5 y5`' % (landmark_list_path, num))
+            table[part[0]] = vals
+    missing = [p for p in image_paths if p not in table]
+    if missing:
+        raise ValueError('%s has no landmarks for %d of the %d listed images, the first being %s'
+                         % (landmark_list_path, len(missing), len(image_paths), missing[0]))
+    out = np.empty((len(image_paths), 10), dtype=np.float32)
+    for i, p in enumerate(image_paths):
+        out[i] = table[p]
+    return out

@@ -90,6 +90,10 @@ def build_parser():
                         help='SphereNet-ArcFace / -CosFace, ResNet-50-arcface / -cosface: K centres per class (sub-center ArcFace), 1..8; the class '
                              'logit is the max cosine over its centres.  1 (default) = one centre, the head as it always was.  Not with '
                              '--sample_rate < 1.  subcenter_clean.py reduces a trained K-centre model to K = 1 and cleans the list.')
+    parser.add_argument('--landmark_list_path', type=str, default=None,
+                        help='`path x1 y1 x2 y2 x3 y3 x4 y4 x5 y5` per line (source pixels of left eye, right eye, nose, left and right mouth '
+                             'corner) for every image of --train_list_path: the images are five-point aligned to --input_height x --input_width '
+                             '(the ArcFace template, scaled by height / 112 and centred) in place of the resize.  --augmentation 0 or 1.')
     parser.add_argument('--shard_classes', type=int, default=0,
                         help='SphereNet-ArcFace / SphereNet-CosFace under --num_gpus > 1: 1 = the classifier is split by class over the ranks '
                              '(model-parallel head): rank r holds C / num_gpus columns with their optimizer slots, the features of the global '
@@ -116,6 +120,17 @@ def shard_flags_check(FLAGS):
             heads.shard_range(FLAGS.synthetic_classes, FLAGS.num_gpus, 0)
     except ValueError as e:
         raise SystemExit('--shard_classes 1: %s' % e)
+
+
+def landmark_flags_check(FLAGS):
+    """--landmark_list_path: refuse what the aligned transform does not do, before anything is built"""
+    if getattr(FLAGS, 'landmark_list_path', None) is None:
+        return
+    if FLAGS.augmentation & 2:
+        raise SystemExit('--landmark_list_path: the geometric augmentation (--augmentation 2 | 3) is not available together with '
+                         'landmarks; use --augmentation 0 or 1 (got %d)' % FLAGS.augmentation)
+    if FLAGS.synthetic:
+        raise SystemExit('--landmark_list_path: --synthetic 1 reads no images')
 
 
 def sample_flags_check(FLAGS):
@@ -284,7 +299,8 @@ def train(FLAGS):
         inputs = train_inputs(FLAGS.train_list_path, input_height=FLAGS.input_height, input_width=FLAGS.input_width,
                               crop_height=FLAGS.crop_height, crop_width=FLAGS.crop_width, is_color=FLAGS.is_color,
                               augmentation=FLAGS.augmentation, batch_size=FLAGS.batch_size, num_classes=FLAGS.num_classes,
-                              num_per_class=FLAGS.num_per_class, device=device, seed=1234, rank=rank, world_size=world)
+                              num_per_class=FLAGS.num_per_class, device=device, seed=1234, rank=rank, world_size=world,
+                              landmark_list_path=getattr(FLAGS, 'landmark_list_path', None))
     try:
         batches_per_epoch = inputs['num_examples'] // batch_size + 1                                  # train.py:172
         network = net_select(FLAGS.net_name, FLAGS.data_format, FLAGS.weight_decay, sub_centers=FLAGS.sub_centers)      # train.py:174
@@ -404,6 +420,7 @@ def main(argv=None):
     sample_flags_check(FLAGS)
     sub_centers_flags_check(FLAGS)
     magface_flags_check(FLAGS)
+    landmark_flags_check(FLAGS)
     os.makedirs(os.path.join(FLAGS.train_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     os.makedirs(os.path.join(FLAGS.model_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     train(FLAGS)
