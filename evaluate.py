@@ -33,10 +33,17 @@ def build_parser():
                         help='`path x1 y1 ... x5 y5` per line for every image of --data_list_path: five-point alignment to --input_height x '
                              '--input_width in place of the resize (train.py --landmark_list_path).')
     parser.add_argument('--data_format', type=str, default='NCHW', help='net_select default (evaluate.py:62).')
+    parser.add_argument('--packed_data_path', type=str, default=None,
+                        help='An image pack made by pack_list.py, in place of --data_list_path (train.py --packed_data_path); not with '
+                             '--data_list_path or --landmark_list_path.')
+    parser.add_argument('--pack_on_gpu', type=int, default=0,
+                        help='--packed_data_path: 1 = the pack is uploaded once and read by the device alone (no decode workers).')
     return parser
 
 
 def evaluate(FLAGS):
+    from train import pack_flags_check
+    pack_flags_check(FLAGS, 'data_list_path')
     import torch
     from scipy.io import savemat
     from tf_face_toolbox_amd import net_select, saver
@@ -46,7 +53,11 @@ def evaluate(FLAGS):
     torch.cuda.set_device(device)
     next_images, num_images = eval_inputs(FLAGS.data_list_path, batch_size=FLAGS.batch_size, input_height=FLAGS.input_height,
                                           input_width=FLAGS.input_width, is_color=FLAGS.is_color, device=device,
-                                          landmark_list_path=getattr(FLAGS, 'landmark_list_path', None))
+                                          landmark_list_path=getattr(FLAGS, 'landmark_list_path', None),
+                                          packed_data_path=getattr(FLAGS, 'packed_data_path', None),
+                                          pack_on_gpu=bool(getattr(FLAGS, 'pack_on_gpu', 0)))
+    if next_images.packed is not None:
+        print('image pack %s, %s' % (FLAGS.packed_data_path, {'host': 'rows read from the host mapping', 'gpu': 'resident in device memory'}[next_images.packed]))
     tag = FLAGS.net_name + '_' + FLAGS.model_name
     latest = saver.latest_checkpoint(os.path.join(FLAGS.model_dir, tag))
     if not latest:

@@ -264,6 +264,21 @@ int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_str
 int fte_preprocess_u8_align(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
                             int crop_w, void* stream);
 
+/* Raw slots from a pre-decoded image pack that is RESIDENT in device memory (tf_face_toolbox_amd/packs.py; train.py / evaluate.py
+ * --packed_data_path P --pack_on_gpu 1).  `rows` holds num_rows rows of row_stride bytes (the pack's uint8 images, zero padded to
+ * a multiple of 64), `headers` n slot headers of 64 bytes (the workers' draws, mode 0, h0 x w0 = the pack's image shape),
+ * `index` n int64 pack rows.  For i < n:
+ *   slots[i * slot_stride .. + 64)              = headers[64 i .. + 64)
+ *   slots[i * slot_stride + 64 .. + row_stride) = rows[r * row_stride .. + row_stride),  r = clamp(index[i], 0, num_rows - 1)
+ * -- the slots fte_preprocess_u8 / _aug / _geo read.  The index is device data and is NOT trusted: it is clamped, never used raw
+ * (the loader validates its own indices on the host as well).  Bytes of a slot beyond 64 + row_stride are not written.  Every
+ * byte offset is 64-bit: r * row_stride passes 2^32 for real packs.  A plain copy in 16-byte chunks by a bounded grid; no
+ * workspace, no atomics, two calls write identical bytes.  FTE_EINVAL, with nothing launched: a null pointer, n < 1,
+ * num_rows < 1, row_stride < 64 or not a multiple of 64, slot_stride not a multiple of 64 or below 64 + row_stride, rows /
+ * headers / slots not 16-byte aligned (index: 8). */
+int fte_pack_gather_slots(const uint8_t* rows, long num_rows, long row_stride, const int64_t* index, const uint8_t* headers,
+                          uint8_t* slots, int n, long slot_stride, void* stream);
+
 /* ---------------------------------------------------------------------------
  * layers.batch_norm(scale=True, center=True, fused=True, decay=0.999, epsilon=1e-3) in TRAINING mode
  * (nets/resnet.py:97-99; FusedBatchNorm / FusedBatchNormGrad).  z is [rows, c] (NHWC flattened).

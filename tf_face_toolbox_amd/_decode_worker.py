@@ -1,5 +1,5 @@
-"""Worker-process side of the input pipeline (tf_face_toolbox_amd/data.py): decode + resize + crop + flip / augmentation +
-normalise of ONE image, written straight into a shared batch buffer.  Imports numpy and PIL only -- a worker process
+"""Worker-process side of the input pipeline (tf_face_toolbox_amd/data.py): decode (or the row of a pre-decoded image pack, packs.py)
++ resize + crop + flip / augmentation + normalise of ONE image, written straight into a shared batch buffer.  Imports numpy and PIL only -- a worker process
 (started as `python -m tf_face_toolbox_amd._decode_worker`) never loads torch or touches the GPU.  Mirrors data.py:206-223 of the reference (the tf.data map function)."""
 import numpy as np
 
@@ -76,6 +76,35 @@ def _load(path, num_channels):
     return a.reshape(a.shape[0], a.shape[1], num_channels)
 
 
+_PACKS = {}
+
+
+def _pack(pack):
+    """The ImagePack a task names by its file path, memory-mapped once per process and cached (as _SHM caches the batch
+    buffers); an ImagePack (the loader's own, in-process use) or None is passed through."""
+    if pack is None or not isinstance(pack, str):
+        return pack
+    p = _PACKS.get(pack)
+    if p is None:
+        from .packs import ImagePack
+        p = _PACKS[pack] = ImagePack(pack)
+    return p
+
+
+def _image(path, num_channels, pack=None):
+    """the decoded uint8 HWC image of an item: _load(path) of a file, or -- `path` an int -- that row of the pack"""
+    if isinstance(path, str):
+        return _load(path, num_channels)
+    pack = _pack(pack)
+    if pack is None:
+        raise ValueError('row index %r without a pack' % (path,))
+    if pack.shape[2] != num_channels:
+        raise ValueError('%s holds %d-channel images, the loader asks for %d' % (pack.path, pack.shape[2], num_channels))
+    if not 0 <= path < pack.num_rows:
+        raise ValueError('%s has no row %d' % (pack.path, path))
+    return pack.image(path)
+
+
 def _aligned(raw, landmarks, path, height, width, y0=0, win_h=None, x0=0, win_w=None):
     """the aligned height x width image (its window) in place of the resized one: preprocessing.aligned_image; a refusal
     names the image"""
@@ -86,12 +115,12 @@ def _aligned(raw, landmarks, path, height, width, y0=0, win_h=None, x0=0, win_w=
         raise ValueError('%s: %s' % (path, e))
 
 
-def decode(path, num_channels, height, width, landmarks=None):
+def decode(path, num_channels, height, width, landmarks=None, pack=None):
     """tf.read_file + decode_jpeg(channels) + convert_image_dtype(float32) + resize_images (data.py:208-213).  landmarks (10
-    numbers): five-point alignment to height x width in place of the resize."""
+    numbers): five-point alignment to height x width in place of the resize.  pack: `path` is a row of that image pack."""
     if landmarks is not None:
-        return _aligned(_load(path, num_channels), landmarks, path, height, width)
-    return resize_window(_load(path, num_channels), height, width)
+        return _aligned(_image(path, num_channels, pack), landmarks, path, height, width)
+    return resize_window(_image(path, num_channels, pack), height, width)
 
 
 GEO_WITH_LANDMARKS = ('the geometric augmentation (augmentation & 2) is not available together with landmarks: the aligned '
@@ -125,8 +154,8 @@ def _finish(raw, input_height, input_width, crop_height, crop_width, augmentatio
     return (np.ascontiguousarray(image, dtype=np.float32) - 0.5) / 0.5
 
 
-def train_example(path, num_channels, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks=None):
-    return _finish(_load(path, num_channels), input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
+def train_example(path, num_channels, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks=None, pack=None):
+    return _finish(_image(path, num_channels, pack), input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
 
 
 HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip}, the augmentation's {flags, float32 brightness,
@@ -179,30 +208,14 @@ def _raw_aligned(slot, path, num_channels, input_height, input_width, crop_heigh
     hd[16:22].view(np.float32)[:] = m6
 
 
-def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0, landmarks=None):
-    """The DECODED image and the draws of train_example() (seeded the same way, drawn in the same order) into one slot of a raw
-    batch buffer -- resize / crop / flip / normalise then run on the GPU (fte_preprocess_u8) and give the bits train_example()
-    gives.  rng None: the evaluation transform (full window, no flip).  An image too large for its slot is transformed here
-    and stored finished (mode 1).  augmentation: the draws of preprocessing.data_augmentation as well (header words 6..9: flag
-    bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug.
-    augmentation & 2: the geometric pair's draws too (word 6 bits 8 = zoom applied, 16 = affine; words 10..12 = the zoom's target
-    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo.  landmarks (10 numbers): an ALIGNED slot instead
-    (_raw_aligned: 128-byte header, the source window, fte_preprocess_u8_align); None: everything above, unchanged."""
-    if landmarks is not None:
-        return _raw_aligned(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, landmarks)
-    raw = _load(path, num_channels)
-    h0, w0 = raw.shape[:2]
+def slot_header(hd, h0, w0, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0):
+    """The 16 header words of a mode-0 raw slot into hd (int32 [16]): {0, h0, w0, y0, x0, flip}, then the draws of train_example()
+    for the seeded `rng`, taken in its order -- crop corner, the geometric pair (words 6, 10..12), the colour augmentation
+    (words 6..9) or the flip -- and zeros.  rng None: the evaluation transform (full window, no flip).  The ONE writer of the
+    draws: slots of decoded files, slots of pack rows and the header-only slots of a resident pack all come through here."""
     cropped = crop_height != -1 and crop_width != -1
     out_h, out_w = (crop_height, crop_width) if cropped else (input_height, input_width)
-    hd = slot[:HEADER_BYTES].view(np.int32)
-    if raw.size > slot.size - HEADER_BYTES:
-        if rng is None:
-            image = (resize_window(raw, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
-        else:
-            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng)
-        slot[HEADER_BYTES:HEADER_BYTES + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
-        hd[:6] = (1, out_h, out_w, 0, 0, 0)
-        return
+    hd[:] = 0
     y0 = x0 = flip = 0
     if rng is not None:
         if cropped:
@@ -222,8 +235,46 @@ def raw_example(slot, path, num_channels, input_height, input_width, crop_height
             hd[7:10].view(np.float32)[:] = (brightness, hue, saturation)
         else:
             flip = int(rng.random() < 0.5)
-    slot[HEADER_BYTES:HEADER_BYTES + raw.size] = raw.reshape(-1)
     hd[:6] = (0, h0, w0, y0, x0, flip)
+
+
+def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0, landmarks=None,
+                pack=None, header_only=False):
+    """The DECODED image and the draws of train_example() (seeded the same way, drawn in the same order) into one slot of a raw
+    batch buffer -- resize / crop / flip / normalise then run on the GPU (fte_preprocess_u8) and give the bits train_example()
+    gives.  rng None: the evaluation transform (full window, no flip).  An image too large for its slot is transformed here
+    and stored finished (mode 1).  augmentation: the draws of preprocessing.data_augmentation as well (header words 6..9: flag
+    bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug.
+    augmentation & 2: the geometric pair's draws too (word 6 bits 8 = zoom applied, 16 = affine; words 10..12 = the zoom's target
+    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo.  landmarks (10 numbers): an ALIGNED slot instead
+    (_raw_aligned: 128-byte header, the source window, fte_preprocess_u8_align); None: everything above, unchanged.
+    pack (an image pack or its file path): `path` is a row index and the slot gets that row, all row_stride bytes of it, where a
+    file's decoded pixels would go.  header_only: the 64 header bytes alone (h0, w0 = the pack's image shape) -- the rows of a
+    pack resident on the GPU are put behind them there (fte_pack_gather_slots)."""
+    if landmarks is not None:
+        return _raw_aligned(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, landmarks)
+    hd = slot[:HEADER_BYTES].view(np.int32)
+    if pack is not None:
+        pack = _pack(pack)
+        raw = _image(path, num_channels, pack)                      # checks the row and the channels; a view, nothing is read yet
+        body = None if header_only else pack.rows[path]
+    else:
+        raw = _load(path, num_channels)
+        body = raw.reshape(-1)
+    h0, w0 = raw.shape[:2]
+    if body is not None and body.size > slot.size - HEADER_BYTES:
+        cropped = crop_height != -1 and crop_width != -1
+        out_h, out_w = (crop_height, crop_width) if cropped else (input_height, input_width)
+        if rng is None:
+            image = (resize_window(raw, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
+        else:
+            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng)
+        slot[HEADER_BYTES:HEADER_BYTES + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
+        hd[:6] = (1, out_h, out_w, 0, 0, 0)
+        return
+    slot_header(hd, h0, w0, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation)
+    if body is not None:
+        slot[HEADER_BYTES:HEADER_BYTES + body.size] = body
 
 
 def _buffer(name, shape, dtype):
@@ -242,25 +293,32 @@ def _buffer(name, shape, dtype):
 
 
 def fill_rows(task):
-    """(buffer, batch shape, [(row, path, seed), ...], num_channels, in_h, in_w, crop_h, crop_w, augmentation[, raw]): decode the
-    listed images (seed None: the evaluation transform) into rows of the shared batch buffer -- a float32 array of finished
-    examples, or with raw = 1 a uint8 array [rows, slot bytes] of decoded images + draws (the colour augmentation's included) for
-    the GPU transform.  A row may carry a fourth item, the image's 10 landmark numbers: it is aligned instead of resized (an
-    aligned raw slot has the 128-byte header).  Returns the number of rows written (errors propagate)."""
+    """(buffer, batch shape, [(row, path, seed), ...], num_channels, in_h, in_w, crop_h, crop_w, augmentation[, raw[, pack path[,
+    header_only]]]): decode the listed images (seed None: the evaluation transform) into rows of the shared batch buffer -- a
+    float32 array of finished examples, or with raw = 1 a uint8 array [rows, slot bytes] of decoded images + draws (the colour
+    augmentation's included) for the GPU transform.  A row may carry a fourth item, the image's 10 landmark numbers: it is aligned
+    instead of resized (an aligned raw slot has the 128-byte header).  With a pack path (packs.py) a row's `path` is an int, the
+    row of that pack, read where a file would have been decoded; header_only: raw slots of 64 bytes, the draws alone.  Returns
+    the number of rows written (errors propagate)."""
     name, shape, rows, num_channels, in_h, in_w, crop_h, crop_w, augmentation = task[:9]
     raw = len(task) > 9 and task[9]
+    more = {}
+    if len(task) > 10 and task[10] is not None:
+        more['pack'] = _pack(task[10])
     if raw:
+        if len(task) > 11 and task[11]:
+            more['header_only'] = True
         batch = _buffer(name, shape, np.uint8)
         for row, path, seed, *lm in rows:
             raw_example(batch[row], path, num_channels, in_h, in_w, crop_h, crop_w, None if seed is None else np.random.default_rng(seed),
-                        augmentation, *lm)
+                        augmentation, *lm, **more)
         return len(rows)
     batch = _buffer(name, shape, np.float32)
     for row, path, seed, *lm in rows:
         if seed is None:                          # evaluation: decode + resize + normalise, nothing random (data.py:153-191)
-            batch[row] = (decode(path, num_channels, in_h, in_w, *lm) - np.float32(0.5)) / np.float32(0.5)
+            batch[row] = (decode(path, num_channels, in_h, in_w, *lm, **more) - np.float32(0.5)) / np.float32(0.5)
         else:
-            batch[row] = train_example(path, num_channels, in_h, in_w, crop_h, crop_w, augmentation, np.random.default_rng(seed), *lm)
+            batch[row] = train_example(path, num_channels, in_h, in_w, crop_h, crop_w, augmentation, np.random.default_rng(seed), *lm, **more)
     return len(rows)
 
 

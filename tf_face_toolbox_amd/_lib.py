@@ -40,6 +40,7 @@ _SIGS = {
     'fte_preprocess_u8_geo_ws_bytes': (c_size_t, [c_int] * 4),
     'fte_preprocess_u8_geo': (c_int, [_P] * 2 + [c_int, c_long] + [c_int] * 5 + [_P, _P, c_size_t, _P]),
     'fte_preprocess_u8_align': (c_int, [_P] * 2 + [c_int, c_long] + [c_int] * 5 + [_P]),
+    'fte_pack_gather_slots': (c_int, [_P, c_long, c_long, _P, _P, _P, c_int, c_long, _P]),
     'fte_bn_ws_bytes': (c_size_t, [c_int]),
     'fte_bn_train_fwd': (c_int, [_P] * 11 + [c_long, c_int, c_float, c_float, c_int, _P, c_size_t, _P]),
     'fte_bn_infer_fwd': (c_int, [_P] * 9 + [c_long, c_int, c_float, c_int, _P]),

@@ -1313,6 +1313,13 @@ int fte_preprocess_u8_align(const uint8_t* slots, float* out, int n, long slot_s
     return rc(k_preprocess_u8_align(slots, out, n, slot_stride, channels, crop_h, crop_w, (hipStream_t)stream));
 }
 
+int fte_pack_gather_slots(const uint8_t* rows, long num_rows, long row_stride, const int64_t* index, const uint8_t* headers, uint8_t* slots,
+                          int n, long slot_stride, void* stream) {
+    if (!rows || !index || !headers || !slots || n < 1 || num_rows < 1 || row_stride < 64 || row_stride % 64 || slot_stride % 64 ||
+        slot_stride < 64 + row_stride || ((uintptr_t)rows | (uintptr_t)headers | (uintptr_t)slots) % 16 || (uintptr_t)index % 8) return FTE_EINVAL;
+    return rc(k_pack_gather_slots(rows, num_rows, row_stride, index, headers, slots, n, slot_stride, igemm_num_cus(), (hipStream_t)stream));
+}
+
 // ------------------------------------------------------------------------------------------------
 // grouped 3x3 conv, SE-gate pieces
 // fte.h: c / groups in {4, 8, 16, 32}; any other width is refused here, before a launcher sees it

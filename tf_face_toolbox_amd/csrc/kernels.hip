@@ -2420,3 +2420,38 @@ hipError_t k_preprocess_u8_align(const unsigned char* slots, float* out, int n, 
     else preprocess_u8_align_kernel<1><<<grid, 256, 0, st>>>(slots, out, slot_stride, crop_h, crop_w);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Raw slots from a pre-decoded image pack resident in device memory (fte.h: fte_pack_gather_slots): slot i = the 64 header bytes
+// the worker wrote for image i, then row clamp(index[i]) of the pack.  A copy in 16-byte chunks -- rows, headers and slots are
+// 16-byte aligned and every stride is a multiple of 64 --; blockIdx.y strides over the images, blockIdx.x * 256 + threadIdx.x
+// over a slot's chunks, so no index is ever divided.  The index is device data: it is clamped before it forms an address.
+// Every byte offset is 64-bit (row * row_stride passes 2^32 for real packs).  No LDS, no atomics: a slot byte has one writer.
+__global__ void __launch_bounds__(256) pack_gather_slots_kernel(const uint4* __restrict__ rows, long num_rows, long row_chunks,
+                                                                const int64_t* __restrict__ index, const uint4* __restrict__ headers,
+                                                                uint4* __restrict__ slots, int n, long slot_chunks) {
+    const long chunks = 4 + row_chunks;                             // of one slot's written part: 64 header bytes + the row
+    for (int i = blockIdx.y; i < n; i += gridDim.y) {
+        long r = index[i];
+        r = r < 0 ? 0 : r >= num_rows ? num_rows - 1 : r;
+        const uint4* src = rows + (long)r * row_chunks;
+        const uint4* hd = headers + (long)i * 4;
+        uint4* dst = slots + (long)i * slot_chunks;
+        for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (long)gridDim.x * 256)
+            dst[c] = c < 4 ? hd[c] : src[c - 4];
+    }
+}
+
+hipError_t k_pack_gather_slots(const unsigned char* rows, long num_rows, long row_stride, const int64_t* index,
+                               const unsigned char* headers, unsigned char* slots, int n, long slot_stride, int cus, hipStream_t st) {
+    // memory-bound: at most ~8 blocks of 256 threads per CU, the loops stride over the rest
+    const long cap = 8L * (cus > 0 ? cus : 256);
+    const long per_slot = ((64 + row_stride) / 16 + 255) / 256;
+    const long gx = per_slot < cap ? per_slot : cap;
+    long gy = cap / gx < 1 ? 1 : cap / gx;
+    if (gy > n) gy = n;
+    if (gy > 65535) gy = 65535;
+    pack_gather_slots_kernel<<<dim3((unsigned)gx, (unsigned)gy), 256, 0, st>>>((const uint4*)rows, num_rows, row_stride / 16, index,
+                                                                             (const uint4*)headers, (uint4*)slots, n, slot_stride / 16);
+    return hipGetLastError();
+}

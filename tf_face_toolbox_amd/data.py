@@ -4,7 +4,8 @@ augmentation -> (x-0.5)/0.5, batches in NHWC).  This is the caller side of the h
 8f next-1): the JPEG decode and the random draws stay on the host (PIL + numpy workers); resize, crop, flip,
 colour augmentation and normalisation run on the GPU when worker processes feed one (_raw_slots), a prefetch
 thread keeps one batch ahead and hands over float32 NHWC CUDA tensors -- exactly the `inputs` dict
-data.py:275-279 returns, with tensors replaced by callables that yield the next batch.
+data.py:275-279 returns, with tensors replaced by callables that yield the next batch.  Not in the reference: packed_data_path feeds
+the same batches from a pre-decoded image pack (packs.py), on request from a copy of it in device memory (fte_pack_gather_slots).
 
 Reference: data.py:30-56 (list parsers), :77-96 (PxK dict), :153-191 (eval_inputs),
 :195-281 (train_inputs)."""
@@ -76,18 +77,25 @@ def get_image_paths_and_labels_dict(list_path, num_per_class, with_index=False):
     appends a single list when a new label shows up, so labels must first appear in increasing
     order there -- data.py:84-86; this version grows the table as far as needed instead.)
     with_index: (path, entry index) in place of every path."""
+    return _class_lists((((part_line[0], k) if with_index else part_line[0], int(part_line[1]))
+                         for k, part_line in enumerate(_list_entries(list_path))), num_per_class)
+
+
+def _class_lists(items_and_labels, num_per_class):
+    """(item, label) pairs in list order -> (per-class item lists with the classes below num_per_class dropped and the survivors
+    re-numbered, images kept, classes kept): the PxK table of a list file (items = paths) and of an image pack (items = rows)"""
     image_path_list_tmp = []
-    for k, part_line in enumerate(_list_entries(list_path)):
-        label_index = int(part_line[1])
+    for item, label_index in items_and_labels:
         while len(image_path_list_tmp) <= label_index:
             image_path_list_tmp.append([])
-        image_path_list_tmp[label_index].append((part_line[0], k) if with_index else part_line[0])
+        image_path_list_tmp[label_index].append(item)
     image_path_list = [lst for lst in image_path_list_tmp if len(lst) >= num_per_class]
     return image_path_list, sum(len(lst) for lst in image_path_list), len(image_path_list)
 
 
 # ------------------------------------------------------------------ decode / preprocess (host)
 from ._decode_worker import resize_bilinear_tf1, decode as _decode, train_example as _train_example, fill_rows as _fill_rows   # noqa: E402,F401
+from ._decode_worker import raw_example as _raw_example, HEADER_BYTES   # noqa: E402
 
 
 class _Prefetcher(object):
@@ -400,7 +408,7 @@ def raw_slot_bytes(header_bytes, num_channels, out_h, out_w):
     return (slot + 63) // 64 * 64
 
 
-def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmentation, device, align=False):
+def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmentation, device, align=False, slot_bytes=None):
     """(slot bytes, transform) when the decode workers hand over DECODED uint8 images and the resize / crop / flip / normalise
     runs on the GPU (fte_preprocess_u8: the same bits as the host transform, tests/test_gpu_loader.py), else (0, None).  The
     host transform is 0.6 of the 1.7 ms a 250 x 250 JPEG costs a worker; the decode stays.  With `augmentation` the colour
@@ -410,7 +418,8 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
     FTE_LOADER_GPU=0 keeps everything on the host.  A slot holds an image of FTE_LOADER_RAW_SIDE^2 pixels
     (default 256; CASIA-WebFace crops are 250 x 250) -- a larger image is transformed by its worker and handed over finished.
     align: aligned slots (128-byte header, the source WINDOW of the face in place of the image) and fte_preprocess_u8_align,
-    which serves augmentation 0 and 1 (tests/test_gpu_align.py)."""
+    which serves augmentation 0 and 1 (tests/test_gpu_align.py).  slot_bytes: the slot size when the images come from a pack
+    (64 + its row stride: every image fits, mode 1 cannot occur)."""
     if num_workers <= 0 or torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0':
         return 0, None
     entry = 'fte_preprocess_u8_geo' if augmentation & 2 else 'fte_preprocess_u8_aug' if augmentation else 'fte_preprocess_u8'
@@ -419,7 +428,7 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
     if align:
         from ._decode_worker import ALIGN_HEADER_BYTES as HEADER_BYTES
         entry = 'fte_preprocess_u8_align'
-    slot = raw_slot_bytes(HEADER_BYTES, num_channels, out_h, out_w)
+    slot = raw_slot_bytes(HEADER_BYTES, num_channels, out_h, out_w) if slot_bytes is None else slot_bytes
 
     extra = ()
     if augmentation & 2:
@@ -437,16 +446,96 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
     return slot, transform
 
 
+# ------------------------------------------------------------------ image packs (packs.py)
+UPLOAD_CHUNK_BYTES = 64 << 20       # the pinned staging buffers a resident pack is uploaded through (two, in turn)
+RESIDENT_HEADROOM_BYTES = 256 << 20  # left free next to a resident pack: the check below is about the pack, not the last byte
+
+
+def _open_pack(data_list_path, packed_data_path, landmark_list_path, num_channels, pack_on_gpu, device):
+    """the ImagePack of packed_data_path after the refusals that train_inputs and eval_inputs share"""
+    from .packs import ImagePack
+    if data_list_path is not None:
+        raise ValueError('packed_data_path replaces data_list_path: give one of them, not both')
+    if landmark_list_path is not None:
+        raise ValueError('landmark_list_path together with packed_data_path: a pack is aligned when it is made '
+                         '(pack_list.py --landmark_list_path), the loader does not align its rows again')
+    pack = ImagePack(packed_data_path)
+    if pack.shape[2] != num_channels:
+        raise ValueError('%s holds %d-channel images, is_color asks for %d' % (pack.path, pack.shape[2], num_channels))
+    if pack_on_gpu and (torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0'):
+        raise ValueError('pack_on_gpu needs the GPU transform: device %s, FTE_LOADER_GPU=%s'
+                         % (device, os.environ.get('FTE_LOADER_GPU', '1')))
+    return pack
+
+
+def _upload_pack(pack, device):
+    """The pack's rows as ONE uint8 device tensor [N * row_stride], uploaded in chunks through two page-locked staging buffers
+    (never one pageable copy of the whole file: the runtime would stage that through its own small buffer, and a 100 GB
+    pageable tensor would first have to exist on the host).  Refused, with both figures, when the device has not the room."""
+    need = pack.num_rows * pack.row_stride
+    free, total = torch.cuda.mem_get_info(device)
+    if need + RESIDENT_HEADROOM_BYTES > free:
+        raise ValueError('%s: a resident pack needs %d bytes of device memory (+ %d headroom), %d of %d are free -- use pack_on_gpu=False'
+                         % (pack.path, need, RESIDENT_HEADROOM_BYTES, free, total))
+    flat = np.memmap(pack.path, dtype=np.uint8, mode='r', offset=pack.data_offset, shape=(need,))
+    dev = torch.empty(need, dtype=torch.uint8, device=device)
+    chunk = min(UPLOAD_CHUNK_BYTES, need)
+    stage = [{'buf': torch.empty(chunk, dtype=torch.uint8).pin_memory(), 'ev': None} for _ in range(2 if need > chunk else 1)]
+    with torch.cuda.device(device):
+        for k, a in enumerate(range(0, need, chunk)):
+            b = min(a + chunk, need)
+            st = stage[k % len(stage)]
+            if st['ev'] is not None:
+                st['ev'].synchronize()
+            np.copyto(st['buf'].numpy()[:b - a], flat[a:b])
+            dev[a:b].copy_(st['buf'][:b - a], non_blocking=True)
+            st['ev'] = torch.cuda.Event()
+            st['ev'].record()
+        torch.cuda.synchronize()
+    return dev
+
+
+def _resident_transform(pack, pack_dev, rows, slot, transform):
+    """(headers [rows, 64] followed by the int64 pack rows, one uint8 device tensor) -> the float batch: fte_pack_gather_slots
+    builds the raw slots from the resident rows, the transform kernels consume them"""
+    from . import _lib
+
+    def gathered(raw):
+        slots = torch.empty((rows, slot), dtype=torch.uint8, device=raw.device)
+        _lib.call('fte_pack_gather_slots', pack_dev, pack.num_rows, pack.row_stride, raw.data_ptr() + rows * 64, raw, slots, rows, slot,
+                  torch.cuda.current_stream().cuda_stream)
+        return transform(slots)
+    return gathered
+
+
+def _resident_rows(rows):
+    """rows of 64 bytes of the host buffer a resident pack's loader hands over per batch: the headers, then the int64 indices"""
+    return rows + (rows * 8 + 63) // 64
+
+
 # ------------------------------------------------------------------ public input builders
 def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop_width=-1, is_color=1,
                  augmentation=0, batch_size=-1, num_classes=-1, num_per_class=-1, device='cuda', seed=None,
-                 rank=0, world_size=1, num_workers=None, landmark_list_path=None):
+                 rank=0, world_size=1, num_workers=None, landmark_list_path=None, packed_data_path=None, pack_on_gpu=False):
     """data.py:195-281.  Returns {'images', 'labels', 'num_classes', 'num_examples', 'batch_size'};
     images/labels are callables (next batch / its labels).  With world_size > 1 every rank draws the
     same global batch order (shared seed) and decodes only its own rows [r*B/n, (r+1)*B/n).
     landmark_list_path (`path x1 y1 ... x5 y5` per line): every image is five-point aligned to input_height x input_width in
-    place of the resize (preprocessing.align_window / align_warp); augmentation 0 and 1 only."""
+    place of the resize (preprocessing.align_window / align_warp); augmentation 0 and 1 only.
+    packed_data_path (data_list_path None): the images and labels come from a pre-decoded pack (packs.py, pack_list.py) -- an
+    item is a pack row where it was a path; the samplers, the sharding and the per-image seeds are the same code with the same
+    draws, so one seed gives the batches of the list the pack was made from.  pack_on_gpu: the pack's rows are uploaded once and
+    stay in device memory; the workers then write the 64-byte slot headers only.  The dict's 'packed' is None, 'host' or 'gpu'."""
     num_channels = 3 if is_color else 1
+    pack = None
+    if packed_data_path is not None:
+        pack = _open_pack(data_list_path, packed_data_path, landmark_list_path, num_channels, pack_on_gpu, device)
+        if not pack.has_labels:
+            raise ValueError('%s has no labels (it was made from a list of paths only): training needs them' % pack.path)
+    elif data_list_path is None:
+        raise ValueError('train_inputs needs data_list_path or packed_data_path')
+    elif pack_on_gpu:
+        raise ValueError('pack_on_gpu without packed_data_path')
     landmarks = None
     if landmark_list_path is not None:
         if augmentation & 2:
@@ -458,8 +547,11 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
     if batch_size == -1:
         assert num_classes != -1 and num_per_class != -1
         batch_size = num_classes * num_per_class
-        image_label_dict, num_examples_total, num_classes_total = get_image_paths_and_labels_dict(   # with landmarks: (path, entry index)
-            data_list_path, num_per_class, with_index=landmarks is not None)
+        if pack is not None:                                         # items are pack rows; dropped and renumbered like a list's
+            image_label_dict, num_examples_total, num_classes_total = _class_lists(enumerate(pack.labels.tolist()), num_per_class)
+        else:
+            image_label_dict, num_examples_total, num_classes_total = get_image_paths_and_labels_dict(   # with landmarks: (path, entry index)
+                data_list_path, num_per_class, with_index=landmarks is not None)
 
         def _gen():                                                  # data.py:230-242 (_gen_balance)
             work = copy.deepcopy(image_label_dict)
@@ -473,8 +565,12 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
                     for _ in range(num_per_class):
                         yield work[idx].pop(), idx
     else:
-        image_list, label_list, num_examples_total, num_classes_total = get_image_paths_and_labels(  # with landmarks: (path, entry index)
-            data_list_path, with_index=landmarks is not None)
+        if pack is not None:                                         # items are pack rows
+            image_list, label_list = list(range(pack.num_rows)), pack.labels.tolist()
+            num_examples_total, num_classes_total = pack.num_rows, max(label_list) + 1
+        else:
+            image_list, label_list, num_examples_total, num_classes_total = get_image_paths_and_labels(  # with landmarks: (path, entry index)
+                data_list_path, with_index=landmarks is not None)
 
         def _gen():                                                  # data.py:225-228 (_gen_random) + repeat()
             while True:
@@ -495,14 +591,22 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
             # 32 workers 23.8 k, 48 workers 27.1 k images/s (through a staging copy: 24.5 k at 48)
             num_workers = min(max(1, cpu_count() // 2 // max(1, world_size)), 48, shard // 4) if shard >= 64 else 0
     on_gpu = torch.device(device).type == 'cuda'
-    slot, transform = _raw_slots(num_workers, shard, num_channels, input_height, input_width, out_h, out_w, augmentation, device,
-                                 align=landmarks is not None)
-    if slot:
+    # a pack's slots are sized from the pack (every row fits: no mode-1 slots); a resident pack has its transform whatever the
+    # number of workers, which only write headers (none: this process writes them)
+    slot, transform = _raw_slots(max(num_workers, 1) if pack_on_gpu else num_workers, shard, num_channels, input_height, input_width, out_h,
+                                 out_w, augmentation, device, align=landmarks is not None,
+                                 slot_bytes=None if pack is None else HEADER_BYTES + pack.row_stride)
+    if pack_on_gpu:
+        transform = _resident_transform(pack, _upload_pack(pack, torch.device(device)), shard, slot, transform)
+        procs = _WorkerPool(num_workers, (_resident_rows(shard), HEADER_BYTES), pin=on_gpu, dtype=np.uint8) if num_workers > 0 else None
+    elif slot:
         procs = _WorkerPool(num_workers, (shard, slot), pin=on_gpu, dtype=np.uint8)
     else:
         procs = _WorkerPool(num_workers, (shard, out_h, out_w, num_channels), pin=on_gpu) if num_workers > 0 else None
-    pool = None if procs else ThreadPoolExecutor(max(1, cpu_count() // 2))
+    pool = None if procs or pack_on_gpu else ThreadPoolExecutor(max(1, cpu_count() // 2))
     params = (num_channels, input_height, input_width, crop_height, crop_width, augmentation) + ((1,) if slot else ())
+    if pack is not None:                                 # the task names the pack by its path; the workers map it once
+        params = params[:6] + (1 if slot else 0, pack.path, bool(pack_on_gpu))
 
     def draw():
         items = [next(gen) for _ in range(batch_size)][rank * shard:(rank + 1) * shard]
@@ -514,16 +618,32 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
 
     pending = []                                         # worker processes: batch k + 1 is being decoded while batch k is copied out
 
+    def with_index(buf, items):
+        """resident pack: the int64 pack rows behind the headers, validated here (the kernel clamps what it is given)"""
+        idx = np.asarray([it[0] for it in items], dtype=np.int64)
+        if idx.min() < 0 or idx.max() >= pack.num_rows:
+            raise ValueError('%s has no row %d' % (pack.path, int(idx.min() if idx.min() < 0 else idx.max())))
+        buf[shard:].reshape(-1).view(np.int64)[:shard] = idx
+        return buf
+
     def make_batch():
         if procs is not None:
             while len(pending) < procs.DEPTH:
                 items, seeds, labels = draw()
-                pending.append((procs.submit([(i, it[0], int(sd)) + it[1:] for i, (it, sd) in enumerate(zip(items, seeds))], params), labels))
-            ticket, labels = pending.pop(0)
-            return procs.wait(ticket), labels
+                pending.append((procs.submit([(i, it[0], int(sd)) + it[1:] for i, (it, sd) in enumerate(zip(items, seeds))], params),
+                                labels, items if pack_on_gpu else None))
+            ticket, labels, items = pending.pop(0)
+            return (with_index(procs.wait(ticket), items) if pack_on_gpu else procs.wait(ticket)), labels
         items, seeds, labels = draw()
+        if pack_on_gpu:                                  # no workers: the headers are a few draws per image, written here
+            buf = np.zeros((_resident_rows(shard), HEADER_BYTES), dtype=np.uint8)
+            for i, (it, sd) in enumerate(zip(items, seeds)):
+                _raw_example(buf[i], it[0], num_channels, input_height, input_width, crop_height, crop_width, np.random.default_rng(sd),
+                             augmentation, pack=pack, header_only=True)
+            return with_index(buf, items), labels
+        more = {} if pack is None else {'pack': pack}
         imgs = list(pool.map(lambda a: _train_example(a[0][0], num_channels, input_height, input_width, crop_height,
-                                                      crop_width, augmentation, np.random.default_rng(a[1]), *a[0][1:]),
+                                                      crop_width, augmentation, np.random.default_rng(a[1]), *a[0][1:], **more),
                              zip(items, seeds)))
         x = np.stack(imgs).reshape(shard, out_h, out_w, num_channels)
         return x, labels
@@ -538,15 +658,28 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
         return ended
     return {'images': src.images, 'labels': src.labels, 'num_classes': num_classes_total,
             'num_examples': num_examples_total, 'batch_size': batch_size, 'close': close,
-            'pin_fallback': bool(procs is not None and procs.pin_failed), 'gpu_transform': bool(slot)}
+            'pin_fallback': bool(procs is not None and procs.pin_failed), 'gpu_transform': bool(slot),
+            'packed': None if pack is None else 'gpu' if pack_on_gpu else 'host', 'pack': None if pack is None else pack.describe()}
 
 
-def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width, device='cuda', num_workers=None, landmark_list_path=None):
+def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width, device='cuda', num_workers=None, landmark_list_path=None,
+                packed_data_path=None, pack_on_gpu=False):
     """data.py:153-191: repeating, in list order, resized, (x-0.5)/0.5.  Returns (next_batch, num_examples).  Batches of 64 or
     more are decoded by the worker processes train_inputs uses (threads in this process manage ~0.3 k images/s).
-    landmark_list_path: five-point alignment in place of the resize, as in train_inputs."""
+    landmark_list_path: five-point alignment in place of the resize, as in train_inputs.
+    packed_data_path / pack_on_gpu: as in train_inputs; a resident pack is read by the device alone (constant headers, a running
+    range of rows) and no worker is started.  next_batch.packed is None, 'host' or 'gpu'."""
     num_channels = 3 if is_color else 1
-    image_list, num_examples = get_image_paths(data_list_path)
+    pack = None
+    if packed_data_path is not None:
+        pack = _open_pack(data_list_path, packed_data_path, landmark_list_path, num_channels, pack_on_gpu, device)
+        image_list, num_examples = list(range(pack.num_rows)), pack.num_rows
+    elif data_list_path is None:
+        raise ValueError('eval_inputs needs data_list_path or packed_data_path')
+    elif pack_on_gpu:
+        raise ValueError('pack_on_gpu without packed_data_path')
+    else:
+        image_list, num_examples = get_image_paths(data_list_path)
     landmarks = None
     if landmark_list_path is not None:
         from .preprocessing import read_landmarks
@@ -557,8 +690,10 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
         if num_workers < 0:
             num_workers = min(max(1, cpu_count() // 2), 32, batch_size // 4) if batch_size >= 64 else 0
     on_gpu = torch.device(device).type == 'cuda'
+    if pack_on_gpu:
+        return _resident_eval(pack, batch_size, num_channels, input_height, input_width, torch.device(device)), num_examples
     slot, transform = _raw_slots(num_workers, batch_size, num_channels, input_height, input_width, input_height, input_width, 0, device,
-                                 align=landmarks is not None)
+                                 align=landmarks is not None, slot_bytes=None if pack is None else HEADER_BYTES + pack.row_stride)
     if slot:
         procs = _WorkerPool(num_workers, (batch_size, slot), pin=on_gpu, dtype=np.uint8)
     else:
@@ -566,6 +701,10 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
     pool = None if procs else ThreadPoolExecutor(8)
     state = {'pos': 0}
     params = (num_channels, input_height, input_width, -1, -1, 0) + ((1,) if slot else ())
+    more = {}
+    if pack is not None:
+        params = params[:6] + (1 if slot else 0, pack.path, False)
+        more = {'pack': pack}
     pending = []
 
     def draw():
@@ -580,7 +719,7 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
             while len(pending) < procs.DEPTH:
                 pending.append(procs.submit([(i, q[0], None) + q[1:] for i, q in enumerate(draw())], params))
             return procs.wait(pending.pop(0)), None
-        imgs = list(pool.map(lambda q: (_decode(q[0], num_channels, input_height, input_width, *q[1:]) - 0.5) / 0.5, draw()))
+        imgs = list(pool.map(lambda q: (_decode(q[0], num_channels, input_height, input_width, *q[1:], **more) - 0.5) / 0.5, draw()))
         return np.stack(imgs).astype(np.float32), None
 
     pf = _Prefetcher(make_batch, torch.device(device), pool=procs, transform=transform)
@@ -594,7 +733,33 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
             pool.shutdown(wait=True)
         return ended
     next_batch.close = close                     # orderly shutdown of the producer thread and the decode workers (evaluate.py)
+    next_batch.packed = None if pack is None else 'host'
     return next_batch, num_examples
+
+
+def _resident_eval(pack, batch_size, num_channels, input_height, input_width, device):
+    """eval_inputs' next_batch over a pack resident in device memory: the evaluation transform draws nothing, so the slot headers
+    are ONE constant device tensor and the rows a running range (wrapping at the end, like the list's) -- per batch the host
+    uploads nothing and decodes nothing, and there is neither a worker process nor a prefetch thread."""
+    slot, transform = _raw_slots(1, batch_size, num_channels, input_height, input_width, input_height, input_width, 0, device,
+                                 slot_bytes=HEADER_BYTES + pack.row_stride)
+    pack_dev = _upload_pack(pack, device)
+    head = np.zeros((_resident_rows(batch_size), HEADER_BYTES), dtype=np.uint8)
+    for i in range(batch_size):
+        _raw_example(head[i], 0, num_channels, input_height, input_width, -1, -1, None, 0, pack=pack, header_only=True)
+    raw = torch.from_numpy(head).to(device)
+    index = raw[batch_size:].reshape(-1).view(torch.int64)[:batch_size]
+    ramp = torch.arange(batch_size, dtype=torch.int64, device=device)
+    gathered = _resident_transform(pack, pack_dev, batch_size, slot, transform)
+    state = {'pos': 0}
+
+    def next_batch():
+        torch.remainder(ramp + state['pos'], pack.num_rows, out=index)
+        state['pos'] = (state['pos'] + batch_size) % pack.num_rows
+        return gathered(raw)
+    next_batch.close = lambda: True              # nothing was started
+    next_batch.packed = 'gpu'
+    return next_batch
 
 
 def synthetic_inputs(batch_size, height, width, is_color, num_classes, device='cuda', rank=0, world_size=1, seed=0):

@@ -99,6 +99,13 @@ def build_parser():
                              '(model-parallel head): rank r holds C / num_gpus columns with their optimizer slots, the features of the global '
                              'batch are all-gathered, the classifier gradient is never all-reduced and the checkpoints stay dense.  Not with '
                              '--sample_rate < 1, --sync_sample 1 or --sub_centers > 1.  0 (default) = every rank holds the whole classifier.')
+    parser.add_argument('--packed_data_path', type=str, default=None,
+                        help='An image pack made by pack_list.py, in place of --train_list_path: the images were decoded once, the loader '
+                             'reads uint8 rows (same batches as the list the pack was made from, bit for bit).  Not with --train_list_path, '
+                             '--synthetic 1 or --landmark_list_path (a pack is aligned when it is made); the pack must carry labels.')
+    parser.add_argument('--pack_on_gpu', type=int, default=0,
+                        help='--packed_data_path: 1 = the whole pack is uploaded once and stays in device memory (every rank holds it); the '
+                             'host then only draws.  0 (default) = the workers copy rows out of the memory-mapped file.')
     return parser
 
 
@@ -131,6 +138,31 @@ def landmark_flags_check(FLAGS):
                          'landmarks; use --augmentation 0 or 1 (got %d)' % FLAGS.augmentation)
     if FLAGS.synthetic:
         raise SystemExit('--landmark_list_path: --synthetic 1 reads no images')
+
+
+def pack_flags_check(FLAGS, list_flag='train_list_path'):
+    """--packed_data_path / --pack_on_gpu: refuse the combinations a pack does not serve, before anything is built (evaluate.py
+    checks its flags here too, with list_flag='data_list_path')"""
+    packed = getattr(FLAGS, 'packed_data_path', None)
+    if packed is None:
+        if getattr(FLAGS, 'pack_on_gpu', 0):
+            raise SystemExit('--pack_on_gpu 1 needs --packed_data_path')
+        return
+    if getattr(FLAGS, list_flag, None) is not None:
+        raise SystemExit('--packed_data_path replaces --%s: give one of them, not both' % list_flag)
+    if getattr(FLAGS, 'synthetic', 0):
+        raise SystemExit('--packed_data_path: --synthetic 1 reads no images')
+    if getattr(FLAGS, 'landmark_list_path', None) is not None:
+        raise SystemExit('--packed_data_path together with --landmark_list_path: a pack is aligned when it is made '
+                         '(pack_list.py --landmark_list_path)')
+    if list_flag == 'train_list_path':
+        from tf_face_toolbox_amd.packs import ImagePack
+        try:
+            pack = ImagePack(packed)
+        except (OSError, ValueError) as e:
+            raise SystemExit('--packed_data_path: %s' % e)
+        if not pack.has_labels:
+            raise SystemExit('--packed_data_path: %s has no labels (it was made from a list of paths only): training needs them' % packed)
 
 
 def sample_flags_check(FLAGS):
@@ -300,7 +332,10 @@ def train(FLAGS):
                               crop_height=FLAGS.crop_height, crop_width=FLAGS.crop_width, is_color=FLAGS.is_color,
                               augmentation=FLAGS.augmentation, batch_size=FLAGS.batch_size, num_classes=FLAGS.num_classes,
                               num_per_class=FLAGS.num_per_class, device=device, seed=1234, rank=rank, world_size=world,
-                              landmark_list_path=getattr(FLAGS, 'landmark_list_path', None))
+                              landmark_list_path=getattr(FLAGS, 'landmark_list_path', None),
+                              packed_data_path=getattr(FLAGS, 'packed_data_path', None), pack_on_gpu=bool(getattr(FLAGS, 'pack_on_gpu', 0)))
+        if inputs['packed'] is not None and rank == 0:
+            print('image pack %s, %s' % (inputs['pack'], {'host': 'rows read from the host mapping', 'gpu': 'resident in device memory'}[inputs['packed']]))
     try:
         batches_per_epoch = inputs['num_examples'] // batch_size + 1                                  # train.py:172
         network = net_select(FLAGS.net_name, FLAGS.data_format, FLAGS.weight_decay, sub_centers=FLAGS.sub_centers)      # train.py:174
@@ -421,6 +456,7 @@ def main(argv=None):
     sub_centers_flags_check(FLAGS)
     magface_flags_check(FLAGS)
     landmark_flags_check(FLAGS)
+    pack_flags_check(FLAGS)
     os.makedirs(os.path.join(FLAGS.train_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     os.makedirs(os.path.join(FLAGS.model_dir, FLAGS.net_name + '_' + FLAGS.model_name), exist_ok=True)
     train(FLAGS)
