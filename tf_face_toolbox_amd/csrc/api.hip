@@ -144,6 +144,8 @@ inline bool aligned16(std::initializer_list<const void*> ptrs) {
     for (const void* q : ptrs) v |= (uintptr_t)q;
     return (v & 15) == 0;
 }
+// the first conv's kernels exist for SAME padding at stride 1 and 2 (same_pads divides by the stride)
+inline bool first_conv_shape_ok(int n, int h, int wd, int stride) { return n >= 1 && h >= 1 && wd >= 1 && (stride == 1 || stride == 2); }
 }  // namespace
 
 extern "C" {
@@ -652,25 +654,26 @@ int fte_conv3x3_wgrad_kept(const float* x, const float* dz, float* dw, int n, in
 // ------------------------------------------------------------------------------------------------
 int fte_conv3x3_first_fwd(const float* x, const float* w, const float* bias, const float* alpha, float* z, float* y,
                           int n, int h, int wd, int cin, int cout, int stride, void* stream) {
-    if (!x || !w || !y || (cout != 64 && cout != 32) || (cin != 1 && cin != 3)) return FTE_EINVAL;
+    if (!x || !w || !y || (cout != 64 && cout != 32) || (cin != 1 && cin != 3) || !first_conv_shape_ok(n, h, wd, stride)) return FTE_EINVAL;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     return rc(k_conv_first_fwd(x, w, bias, alpha, z, y, nullptr, nullptr, n, h, wd, cin, cout, ph.out, pw.out, stride, ph.before, pw.before, (hipStream_t)stream));
 }
 int fte_conv3x3_first_fwd_s16(const float* x, const float* w, const float* bias, const float* alpha, uint16_t* z16, uint16_t* y16,
                               int n, int h, int wd, int cin, int cout, int stride, void* stream) {
-    if (!x || !w || !y16 || (cout != 64 && cout != 32) || (cin != 1 && cin != 3)) return FTE_EINVAL;
+    if (!x || !w || !y16 || (cout != 64 && cout != 32) || (cin != 1 && cin != 3) || !first_conv_shape_ok(n, h, wd, stride)) return FTE_EINVAL;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     return rc(k_conv_first_fwd(x, w, bias, alpha, nullptr, nullptr, z16, y16, n, h, wd, cin, cout, ph.out, pw.out, stride, ph.before, pw.before, (hipStream_t)stream));
 }
 
 size_t fte_conv3x3_first_wgrad_ws_bytes(int n, int h, int wd, int cin, int cout, int stride) {
+    if ((cout != 64 && cout != 32) || (cin != 1 && cin != 3) || !first_conv_shape_ok(n, h, wd, stride)) return 0;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     return align_up((size_t)k_conv_first_wgrad_blocks((long)n * ph.out * pw.out) * 9 * cin * cout * sizeof(float)) + SCRATCH_BYTES;
 }
 
 static int conv_first_wgrad_impl(const float* x, const float* dz, const uint16_t* dz16, float* dw, int n, int h, int wd, int cin, int cout, int stride,
                                  void* ws, size_t ws_bytes, void* stream) {
-    if (!x || (!dz && !dz16) || !dw || (cout != 64 && cout != 32) || (cin != 1 && cin != 3)) return FTE_EINVAL;
+    if (!x || (!dz && !dz16) || !dw || (cout != 64 && cout != 32) || (cin != 1 && cin != 3) || !first_conv_shape_ok(n, h, wd, stride)) return FTE_EINVAL;
     const Pads ph = same_pads(h, 3, stride), pw = same_pads(wd, 3, stride);
     const int blocks = k_conv_first_wgrad_blocks((long)n * ph.out * pw.out);
     const size_t need = align_up((size_t)blocks * 9 * cin * cout * sizeof(float));
@@ -692,6 +695,7 @@ int fte_conv3x3_first_wgrad_s16(const float* x, const uint16_t* dz16, float* dw,
 // dense
 size_t fte_gemm_ws_bytes(int m, int n, int k) {
     // max over nn (m x n, red k), nt (m x k, red n; or its dalpha partials), tn (k x n, red m)
+    if (m <= 0 || n <= 0 || k <= 0) return 0;         // no product takes these (and dense_plan divides by the tile count)
     const PlanKnobs& kn = knobs();
     const bool b16 = igemm_get_bf16();
     size_t need = 0, v;
@@ -706,7 +710,7 @@ size_t fte_gemm_ws_bytes(int m, int n, int k) {
 
 static int gemm_nn_impl(const float* x, const float* w, const float* bias, float* y, int m, int n, int k, int act,
                         void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !y || m <= 0 || n % 64 || k % 32 || act < 0 || act > 2) return FTE_EINVAL;
+    if (!x || !w || !y || m <= 0 || n <= 0 || k <= 0 || n % 64 || k % 32 || act < 0 || act > 2) return FTE_EINVAL;
     IgemmParams p;
     zero_params(&p);
     p.M = m; p.N = n; p.K = k;
@@ -738,7 +742,7 @@ int fte_dense_small(const float* a, const float* w, const float* bias, const flo
 int fte_gemm_nt(const float* dy, const float* w, const float* zprev, const float* alpha_prev, int amod,
                 float* raw, float* dx, float* dalpha_prev, int m, int n, int k, void* ws, size_t ws_bytes, void* stream) {
     // dx[m,k] = dy[m,n] @ w[k,n]^T : GEMM with rows m, cols k, reduction n
-    if (!dy || !w || !dx || m <= 0 || k % 64 || n % 32) return FTE_EINVAL;
+    if (!dy || !w || !dx || m <= 0 || n <= 0 || k <= 0 || k % 64 || n % 32) return FTE_EINVAL;
     if (zprev && (!alpha_prev || amod <= 0 || k % amod)) return FTE_EINVAL;
     IgemmParams p;
     zero_params(&p);
@@ -767,7 +771,7 @@ int fte_gemm_nt(const float* dy, const float* w, const float* zprev, const float
 
 int fte_gemm_tn(const float* x, const float* dy, float* dw, int m, int n, int k, void* ws, size_t ws_bytes, void* stream) {
     // dw[k,n] = x[m,k]^T @ dy[m,n] : GEMM with rows k, cols n, reduction m
-    if (!x || !dy || !dw || m <= 0 || n % 64 || k % 4) return FTE_EINVAL;
+    if (!x || !dy || !dw || m <= 0 || n <= 0 || k <= 0 || n % 64 || k % 4) return FTE_EINVAL;
     IgemmParams p;
     zero_params(&p);
     p.M = k; p.N = n; p.K = m;
