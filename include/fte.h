@@ -201,8 +201,10 @@ int fte_im2col_first_s16(const float* x, uint16_t* cols16, int n, int h, int wd,
  * (x - 0.5) / 0.5; the evaluation transform of data.py:153-191 is the same with the full window and no flip).  `slots` holds
  * n slots of slot_stride bytes (a multiple of 64): a 64-byte header of int32 {mode, h0, w0, y0, x0, flip, 0...} followed by
  * the h0 x w0 x channels bytes of the image (mode 0; y0 / x0 = the crop's corner in the RESIZED image) or by the finished
- * float32 crop (mode 1).  out is [n, crop_h, crop_w, channels] float32; every value is bit-equal to the host transform
- * (tf_face_toolbox_amd/_decode_worker.py).  The random draws stay on the host (they are the workers' seeded draws). */
+ * float32 crop (mode 1: copied from byte 64; a crop that does not fit the slot reads 0).  out is [n, crop_h, crop_w, channels]
+ * float32; every value is bit-equal to the host transform (tf_face_toolbox_amd/_decode_worker.py).  The random draws stay on the
+ * host (they are the workers' seeded draws).  This entry and the three below are csrc/loader.hip: one header decode (SlotHeader),
+ * one bilinear tap, one colour tail and one mode-1 copy serve the 64-byte-header entries; the aligned entry shares the colour tail. */
 int fte_preprocess_u8(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
                       void* stream);
 /* The same transform followed by the colour augmentation of preprocessing.py:22-38 of the reference (train.py --augmentation 1)
@@ -270,7 +272,7 @@ int fte_preprocess_u8_align(const uint8_t* slots, float* out, int n, long slot_s
  * `index` n int64 pack rows.  For i < n:
  *   slots[i * slot_stride .. + 64)              = headers[64 i .. + 64)
  *   slots[i * slot_stride + 64 .. + row_stride) = rows[r * row_stride .. + row_stride),  r = clamp(index[i], 0, num_rows - 1)
- * -- the slots fte_preprocess_u8 / _aug / _geo read.  The index is device data and is NOT trusted: it is clamped, never used raw
+ * -- the slots fte_preprocess_u8 / _aug / _geo read (csrc/loader.hip: pack_gather_slots_kernel).  The index is device data and is NOT trusted: it is clamped, never used raw
  * (the loader validates its own indices on the host as well).  Bytes of a slot beyond 64 + row_stride are not written.  Every
  * byte offset is 64-bit: r * row_stride passes 2^32 for real packs.  A plain copy in 16-byte chunks by a bounded grid; no
  * workspace, no atomics, two calls write identical bytes.  FTE_EINVAL, with nothing launched: a null pointer, n < 1,

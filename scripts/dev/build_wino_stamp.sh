@@ -9,6 +9,6 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 $HIPCC $FLAGS ${STAMP--DFTE_WINO_STAMP} $EXTRA -c "$HERE/wino.hip" -o /tmp/fte_wstamp_obj/wino.o
 OBJS=""
 # (csrc/build.sh SRCS minus wino)
-for f in igemm igemm16 wgrad16 pw16 kernels layers search partial_fc cluster iresnet api; do OBJS="$OBJS $HERE/obj/$f.o"; done
+for f in igemm igemm16 wgrad16 pw16 kernels loader layers search partial_fc cluster iresnet api; do OBJS="$OBJS $HERE/obj/$f.o"; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libfte_wstamp.so" /tmp/fte_wstamp_obj/wino.o $OBJS
 echo "built $OUT/libfte_wstamp.so"

@@ -62,6 +62,44 @@ def test_eval_transform_is_bit_equal_to_the_host():
         assert np.array_equal(got[i].view(np.uint32), want.view(np.uint32))
 
 
+@pytest.mark.parametrize('ch', [3, 1])
+@pytest.mark.parametrize('entry,augmentation', [('fte_preprocess_u8', 0), ('fte_preprocess_u8_aug', 1), ('fte_preprocess_u8_geo', 3)])
+def test_finished_slots_are_copied(entry, augmentation, ch):
+    """mode 1 through the entries with the 64-byte header (the one copy the four transforms share): the float32 crop behind
+    the header comes back bit for bit, whatever words 6..12 say; the mode-0 slots on either side of it equal the host."""
+    import torch
+    from tf_face_toolbox_amd import _decode_worker as dw
+    from tf_face_toolbox_amd._lib import call, query
+    from tf_face_toolbox_amd.preprocessing import AFFINE_TABLE
+    in_h, in_w, out_h, out_w = 37, 29, 32, 24
+    nbytes = (dw.HEADER_BYTES + max(64 * 64 * ch, out_h * out_w * ch * 4) + 63) // 64 * 64
+    rng = np.random.default_rng(8 + ch)
+    crop = rng.standard_normal((out_h, out_w, ch)).astype(np.float32)
+    buf = np.zeros((3, nbytes), dtype=np.uint8)
+    paths = {0: os.path.join(IMG, 'a.png'), 2: os.path.join(IMG, 'c.png')}   # 29 x 37 and 60 x 60: both fit a 64 x 64 slot
+    for i in (0, 2):
+        dw.raw_example(buf[i], paths[i], ch, in_h, in_w, out_h, out_w, np.random.default_rng(40 + i), augmentation)
+    hd = buf[1, :dw.HEADER_BYTES].view(np.int32)
+    hd[:6] = (1, out_h, out_w, 5, 6, 1)
+    hd[6:13] = (31, -1, 0x7FC00000, 0x7F800000, -7, 10 ** 9, 5000)          # every flag bit, -NaN, NaN, +inf, th, tw, rnd out of range
+    buf[1, dw.HEADER_BYTES:dw.HEADER_BYTES + crop.size * 4] = crop.reshape(-1).view(np.uint8)
+    assert buf[[0, 2], :4].view(np.int32).tolist() == [[0], [0]]
+    raw = torch.from_numpy(buf).cuda()
+    out = torch.empty((3, out_h, out_w, ch), dtype=torch.float32, device='cuda')
+    extra = ()
+    if entry == 'fte_preprocess_u8_geo':
+        ws_bytes = query('fte_preprocess_u8_geo_ws_bytes', 3, ch, out_h, out_w)
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device='cuda')
+        extra = (torch.from_numpy(AFFINE_TABLE).cuda(), ws, ws_bytes)
+    call(entry, raw.data_ptr(), out.data_ptr(), 3, nbytes, ch, in_h, in_w, out_h, out_w, *extra, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert np.array_equal(got[1].view(np.uint32), crop.view(np.uint32))
+    for i in (0, 2):
+        want = dw.train_example(paths[i], ch, in_h, in_w, out_h, out_w, augmentation, np.random.default_rng(40 + i))
+        assert np.array_equal(got[i].view(np.uint32), want.view(np.uint32)), i
+
+
 def test_bad_arguments_are_refused():
     import torch
     from tf_face_toolbox_amd._lib import query

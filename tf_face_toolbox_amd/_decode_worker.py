@@ -1,6 +1,8 @@
 """Worker-process side of the input pipeline (tf_face_toolbox_amd/data.py): decode (or the row of a pre-decoded image pack, packs.py)
 + resize + crop + flip / augmentation + normalise of ONE image, written straight into a shared batch buffer.  Imports numpy and PIL only -- a worker process
 (started as `python -m tf_face_toolbox_amd._decode_worker`) never loads torch or touches the GPU.  Mirrors data.py:206-223 of the reference (the tf.data map function)."""
+from collections import namedtuple
+
 import numpy as np
 
 _RESIZE_TABLES = {}
@@ -105,9 +107,11 @@ def _image(path, num_channels, pack=None):
     return pack.image(path)
 
 
-def _aligned(raw, landmarks, path, height, width, y0=0, win_h=None, x0=0, win_w=None):
-    """the aligned height x width image (its window) in place of the resized one: preprocessing.aligned_image; a refusal
-    names the image"""
+def _window(raw, landmarks, path, height, width, y0=0, win_h=None, x0=0, win_w=None):
+    """The window of the resized height x width image (resize_window) or, with landmarks, of the aligned one in its place
+    (preprocessing.aligned_image; a refusal names the image)."""
+    if landmarks is None:
+        return resize_window(raw, height, width, y0, win_h, x0, win_w)
     from .preprocessing import aligned_image
     try:
         return aligned_image(raw, landmarks, height, width, y0, win_h, x0, win_w)
@@ -118,31 +122,28 @@ def _aligned(raw, landmarks, path, height, width, y0=0, win_h=None, x0=0, win_w=
 def decode(path, num_channels, height, width, landmarks=None, pack=None):
     """tf.read_file + decode_jpeg(channels) + convert_image_dtype(float32) + resize_images (data.py:208-213).  landmarks (10
     numbers): five-point alignment to height x width in place of the resize.  pack: `path` is a row of that image pack."""
-    if landmarks is not None:
-        return _aligned(_image(path, num_channels, pack), landmarks, path, height, width)
-    return resize_window(_image(path, num_channels, pack), height, width)
+    return _window(_image(path, num_channels, pack), landmarks, path, height, width)
 
 
 GEO_WITH_LANDMARKS = ('the geometric augmentation (augmentation & 2) is not available together with landmarks: the aligned '
                       'transform supports augmentation 0 and 1')
 
 
+def _crop_corner(rng, input_height, input_width, crop_height, crop_width):
+    """the first draws of an example: (y0, x0) of tf.random_crop, or (0, 0) and no draw without a crop"""
+    if crop_height == -1 or crop_width == -1:
+        return 0, 0
+    y0 = int(rng.integers(0, input_height - crop_height + 1))
+    return y0, int(rng.integers(0, input_width - crop_width + 1))
+
+
 def _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks=None, path=None):
-    if landmarks is not None:                                       # alignment replaces the resize; the draws are the same
-        if augmentation & 2:
-            raise ValueError(GEO_WITH_LANDMARKS)
-        if crop_height != -1 and crop_width != -1:
-            y0 = rng.integers(0, input_height - crop_height + 1)
-            x0 = rng.integers(0, input_width - crop_width + 1)
-            image = _aligned(raw, landmarks, path, input_height, input_width, int(y0), crop_height, int(x0), crop_width)
-        else:
-            image = _aligned(raw, landmarks, path, input_height, input_width)
-    elif crop_height != -1 and crop_width != -1:                    # tf.random_crop: only the cropped window is resized
-        y0 = rng.integers(0, input_height - crop_height + 1)
-        x0 = rng.integers(0, input_width - crop_width + 1)
-        image = resize_window(raw, input_height, input_width, y0, crop_height, x0, crop_width)
-    else:
-        image = resize_window(raw, input_height, input_width)
+    if landmarks is not None and augmentation & 2:                  # alignment replaces the resize; the draws are the same
+        raise ValueError(GEO_WITH_LANDMARKS)
+    cropped = crop_height != -1 and crop_width != -1
+    y0, x0 = _crop_corner(rng, input_height, input_width, crop_height, crop_width)
+    # tf.random_crop: only the cropped window is resized (aligned)
+    image = _window(raw, landmarks, path, input_height, input_width, y0, crop_height if cropped else None, x0, crop_width if cropped else None)
     if augmentation & 2:                                            # the geometric pair: zoom, then affine (draws u, rnd)
         from .preprocessing import geometric_augmentation
         image = geometric_augmentation(image, rng)
@@ -158,84 +159,42 @@ def train_example(path, num_channels, input_height, input_width, crop_height, cr
     return _finish(_image(path, num_channels, pack), input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
 
 
-HEADER_BYTES = 64            # per raw slot: int32 {mode, h0, w0, y0, x0, flip}, the augmentation's {flags, float32 brightness,
-#                              hue, saturation}, the geometric pair's {th, tw, rnd} + padding (include/fte.h: fte_preprocess_u8,
-#                              fte_preprocess_u8_aug, fte_preprocess_u8_geo)
+HEADER_BYTES = 64            # per raw slot: the 16 words below + padding (include/fte.h: fte_preprocess_u8, _aug, _geo)
+ALIGN_HEADER_BYTES = 128     # per ALIGNED raw slot: the same 16 words with h0, w0 = the shape of the source window, the inverse
+#                              similarity in words 16..21, words 22..31 = 0 (include/fte.h: fte_preprocess_u8_align)
+# The header's fields as words of its int32 view -- fte.h's layout, named here once:
+W_MODE, W_H0, W_W0, W_Y0, W_X0, W_FLIP, W_FLAGS = range(7)
+W_COLOUR = slice(7, 10)      # float32 bits: brightness delta, hue delta, saturation factor
+W_GEO = slice(10, 13)        # th, tw (the zoom's target shape), rnd (the affine index)
+W_M6 = slice(16, 22)         # float32 bits: (a0, a1, a2, b0, b1, b2) of an aligned slot
 
 
-ALIGN_HEADER_BYTES = 128     # per ALIGNED raw slot: the 16 words above with h0, w0 = the shape of the source window, words 16..21 =
-#                              float32 bits of the inverse similarity m6, words 22..31 = 0 (include/fte.h: fte_preprocess_u8_align)
-
-
-def _raw_aligned(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, landmarks):
-    """raw_example() with landmarks: the WINDOW of the decoded image that the aligned image reads (preprocessing.align_window),
-    the draws and the inverse similarity into an aligned slot; fte_preprocess_u8_align warps, flips, colours and normalises."""
-    from .preprocessing import align_window
-    if augmentation & 2:
-        raise ValueError(GEO_WITH_LANDMARKS)
-    raw = _load(path, num_channels)
-    cropped = crop_height != -1 and crop_width != -1
-    out_h, out_w = (crop_height, crop_width) if cropped else (input_height, input_width)
-    hd = slot[:ALIGN_HEADER_BYTES].view(np.int32)
-    hd[:] = 0
-    try:
-        wy0, wx0, wh, ww, m6 = align_window(landmarks, raw.shape[0], raw.shape[1], input_height, input_width)
-    except ValueError as e:
-        raise ValueError('%s: %s' % (path, e))
-    if wh * ww * num_channels > slot.size - ALIGN_HEADER_BYTES:
-        if rng is None:
-            image = (_aligned(raw, landmarks, path, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
-        else:
-            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
-        slot[ALIGN_HEADER_BYTES:ALIGN_HEADER_BYTES + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
-        hd[:6] = (1, out_h, out_w, 0, 0, 0)
-        return
-    y0 = x0 = flip = 0
-    if rng is not None:
-        if cropped:
-            y0 = int(rng.integers(0, input_height - crop_height + 1))
-            x0 = int(rng.integers(0, input_width - crop_width + 1))
-        if augmentation & 1:
-            from .preprocessing import augmentation_draws
-            flip, flags, brightness, hue, saturation = augmentation_draws(rng, num_channels)
-            hd[6] = flags
-            hd[7:10].view(np.float32)[:] = (brightness, hue, saturation)
-        else:
-            flip = int(rng.random() < 0.5)
-    window = raw[wy0:wy0 + wh, wx0:wx0 + ww]
-    slot[ALIGN_HEADER_BYTES:ALIGN_HEADER_BYTES + window.size] = window.reshape(-1)
-    hd[:6] = (0, wh, ww, y0, x0, flip)
-    hd[16:22].view(np.float32)[:] = m6
-
-
-def slot_header(hd, h0, w0, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0):
-    """The 16 header words of a mode-0 raw slot into hd (int32 [16]): {0, h0, w0, y0, x0, flip}, then the draws of train_example()
-    for the seeded `rng`, taken in its order -- crop corner, the geometric pair (words 6, 10..12), the colour augmentation
-    (words 6..9) or the flip -- and zeros.  rng None: the evaluation transform (full window, no flip).  The ONE writer of the
-    draws: slots of decoded files, slots of pack rows and the header-only slots of a resident pack all come through here."""
-    cropped = crop_height != -1 and crop_width != -1
-    out_h, out_w = (crop_height, crop_width) if cropped else (input_height, input_width)
+def slot_header(hd, h0, w0, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0, m6=None):
+    """The header words of a mode-0 raw slot into hd (int32 [16]; aligned: [32], with the inverse similarity m6 for words 16..21):
+    {0, h0, w0, y0, x0, flip}, then the draws of train_example() for the seeded `rng`, taken in its order -- crop corner, the
+    geometric pair (words 6, 10..12), the colour augmentation (words 6..9) or the flip -- and zeros.  rng None: the evaluation
+    transform (full window, no flip).  The ONE place that draws for a raw slot: slots of decoded files, aligned slots, slots of
+    pack rows and the header-only slots of a resident pack all come through here."""
     hd[:] = 0
     y0 = x0 = flip = 0
     if rng is not None:
-        if cropped:
-            y0 = int(rng.integers(0, input_height - crop_height + 1))
-            x0 = int(rng.integers(0, input_width - crop_width + 1))
-        geo = 0
+        y0, x0 = _crop_corner(rng, input_height, input_width, crop_height, crop_width)
         if augmentation & 2:
             from .preprocessing import AFFINE, ZOOM, geometric_draws
+            out_h, out_w = (crop_height, crop_width) if crop_height != -1 and crop_width != -1 else (input_height, input_width)
             th, tw, rnd = geometric_draws(rng, out_h, out_w)
-            geo = AFFINE | (ZOOM if (th, tw) != (out_h, out_w) else 0)
-            hd[6] = geo
-            hd[10:13] = (th, tw, rnd)
+            hd[W_FLAGS] = AFFINE | (ZOOM if (th, tw) != (out_h, out_w) else 0)
+            hd[W_GEO] = (th, tw, rnd)
         if augmentation & 1:
             from .preprocessing import augmentation_draws
             flip, flags, brightness, hue, saturation = augmentation_draws(rng, num_channels)
-            hd[6] = flags | geo
-            hd[7:10].view(np.float32)[:] = (brightness, hue, saturation)
+            hd[W_FLAGS] |= flags
+            hd[W_COLOUR].view(np.float32)[:] = (brightness, hue, saturation)
         else:
             flip = int(rng.random() < 0.5)
-    hd[:6] = (0, h0, w0, y0, x0, flip)
+    hd[:W_FLAGS] = (0, h0, w0, y0, x0, flip)
+    if m6 is not None:
+        hd[W_M6].view(np.float32)[:] = m6
 
 
 def raw_example(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation=0, landmarks=None,
@@ -246,35 +205,46 @@ def raw_example(slot, path, num_channels, input_height, input_width, crop_height
     and stored finished (mode 1).  augmentation: the draws of preprocessing.data_augmentation as well (header words 6..9: flag
     bits and the float32 brightness delta, hue delta and saturation factor), applied on the GPU by fte_preprocess_u8_aug.
     augmentation & 2: the geometric pair's draws too (word 6 bits 8 = zoom applied, 16 = affine; words 10..12 = the zoom's target
-    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo.  landmarks (10 numbers): an ALIGNED slot instead
-    (_raw_aligned: 128-byte header, the source window, fte_preprocess_u8_align); None: everything above, unchanged.
+    shape th, tw and the affine index rnd), applied by fte_preprocess_u8_geo.  landmarks (10 numbers): an ALIGNED slot instead --
+    a 128-byte header, then the WINDOW of the decoded image that the aligned image reads (preprocessing.align_window) with the
+    inverse similarity relative to it; fte_preprocess_u8_align warps, flips, colours and normalises.
     pack (an image pack or its file path): `path` is a row index and the slot gets that row, all row_stride bytes of it, where a
     file's decoded pixels would go.  header_only: the 64 header bytes alone (h0, w0 = the pack's image shape) -- the rows of a
     pack resident on the GPU are put behind them there (fte_pack_gather_slots)."""
-    if landmarks is not None:
-        return _raw_aligned(slot, path, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, landmarks)
-    hd = slot[:HEADER_BYTES].view(np.int32)
+    header, m6 = HEADER_BYTES, None
+    if pack is not None and landmarks is not None:
+        raise ValueError('landmarks together with a pack: a pack is aligned when it is made, its rows are not aligned again')
     if pack is not None:
         pack = _pack(pack)
         raw = _image(path, num_channels, pack)                      # checks the row and the channels; a view, nothing is read yet
         body = None if header_only else pack.rows[path]
+    elif landmarks is None:
+        body = raw = _load(path, num_channels)
     else:
-        raw = _load(path, num_channels)
-        body = raw.reshape(-1)
-    h0, w0 = raw.shape[:2]
-    if body is not None and body.size > slot.size - HEADER_BYTES:
-        cropped = crop_height != -1 and crop_width != -1
-        out_h, out_w = (crop_height, crop_width) if cropped else (input_height, input_width)
+        from .preprocessing import align_window
+        if augmentation & 2:
+            raise ValueError(GEO_WITH_LANDMARKS)
+        header, raw = ALIGN_HEADER_BYTES, _load(path, num_channels)
+        try:
+            wy0, wx0, wh, ww, m6 = align_window(landmarks, raw.shape[0], raw.shape[1], input_height, input_width)
+        except ValueError as e:
+            raise ValueError('%s: %s' % (path, e))
+        body = raw[wy0:wy0 + wh, wx0:wx0 + ww]
+    hd = slot[:header].view(np.int32)
+    if body is not None and body.size > slot.size - header:         # does not fit: finished on the host, mode 1
         if rng is None:
-            image = (resize_window(raw, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
+            image = (_window(raw, landmarks, path, input_height, input_width) - np.float32(0.5)) / np.float32(0.5)
         else:
-            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng)
-        slot[HEADER_BYTES:HEADER_BYTES + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
-        hd[:6] = (1, out_h, out_w, 0, 0, 0)
+            image = _finish(raw, input_height, input_width, crop_height, crop_width, augmentation, rng, landmarks, path)
+        slot[header:header + image.size * 4] = np.ascontiguousarray(image, dtype=np.float32).reshape(-1).view(np.uint8)
+        cropped = crop_height != -1 and crop_width != -1
+        hd[:] = 0
+        hd[:W_FLAGS] = (1,) + ((crop_height, crop_width) if cropped else (input_height, input_width)) + (0, 0, 0)
         return
-    slot_header(hd, h0, w0, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation)
+    h0, w0 = (raw if m6 is None else body).shape[:2]
+    slot_header(hd, h0, w0, num_channels, input_height, input_width, crop_height, crop_width, rng, augmentation, m6)
     if body is not None:
-        slot[HEADER_BYTES:HEADER_BYTES + body.size] = body
+        slot[header:header + body.size] = body.reshape(-1)
 
 
 def _buffer(name, shape, dtype):
@@ -292,34 +262,36 @@ def _buffer(name, shape, dtype):
     return batch
 
 
+Task = namedtuple('Task', 'buffer shape rows num_channels in_h in_w crop_h crop_w augmentation raw pack header_only',
+                  defaults=(0, None, False))
+
+
 def fill_rows(task):
-    """(buffer, batch shape, [(row, path, seed), ...], num_channels, in_h, in_w, crop_h, crop_w, augmentation[, raw[, pack path[,
-    header_only]]]): decode the listed images (seed None: the evaluation transform) into rows of the shared batch buffer -- a
+    """A Task, or the bare tuple of its fields in order (raw, pack, header_only may be left off): decode the listed images
+    rows = [(row, path, seed), ...] (seed None: the evaluation transform) into rows of the shared batch buffer -- a
     float32 array of finished examples, or with raw = 1 a uint8 array [rows, slot bytes] of decoded images + draws (the colour
     augmentation's included) for the GPU transform.  A row may carry a fourth item, the image's 10 landmark numbers: it is aligned
     instead of resized (an aligned raw slot has the 128-byte header).  With a pack path (packs.py) a row's `path` is an int, the
     row of that pack, read where a file would have been decoded; header_only: raw slots of 64 bytes, the draws alone.  Returns
     the number of rows written (errors propagate)."""
-    name, shape, rows, num_channels, in_h, in_w, crop_h, crop_w, augmentation = task[:9]
-    raw = len(task) > 9 and task[9]
-    more = {}
-    if len(task) > 10 and task[10] is not None:
-        more['pack'] = _pack(task[10])
-    if raw:
-        if len(task) > 11 and task[11]:
+    t = Task(*task)
+    more = {} if t.pack is None else {'pack': _pack(t.pack)}
+    size = (t.num_channels, t.in_h, t.in_w)
+    if t.raw:
+        if t.header_only:
             more['header_only'] = True
-        batch = _buffer(name, shape, np.uint8)
-        for row, path, seed, *lm in rows:
-            raw_example(batch[row], path, num_channels, in_h, in_w, crop_h, crop_w, None if seed is None else np.random.default_rng(seed),
-                        augmentation, *lm, **more)
-        return len(rows)
-    batch = _buffer(name, shape, np.float32)
-    for row, path, seed, *lm in rows:
+        batch = _buffer(t.buffer, t.shape, np.uint8)
+        for row, path, seed, *lm in t.rows:
+            raw_example(batch[row], path, *size, t.crop_h, t.crop_w, None if seed is None else np.random.default_rng(seed),
+                        t.augmentation, *lm, **more)
+        return len(t.rows)
+    batch = _buffer(t.buffer, t.shape, np.float32)
+    for row, path, seed, *lm in t.rows:
         if seed is None:                          # evaluation: decode + resize + normalise, nothing random (data.py:153-191)
-            batch[row] = (decode(path, num_channels, in_h, in_w, *lm, **more) - np.float32(0.5)) / np.float32(0.5)
+            batch[row] = (decode(path, *size, *lm, **more) - np.float32(0.5)) / np.float32(0.5)
         else:
-            batch[row] = train_example(path, num_channels, in_h, in_w, crop_h, crop_w, augmentation, np.random.default_rng(seed), *lm, **more)
-    return len(rows)
+            batch[row] = train_example(path, *size, t.crop_h, t.crop_w, t.augmentation, np.random.default_rng(seed), *lm, **more)
+    return len(t.rows)
 
 
 def main():

@@ -15,6 +15,7 @@
 #include "wgrad16.h"
 #include "pw16.h"
 #include "kernels.h"
+#include "loader.h"
 #include "layers.h"
 #include "wino.h"
 #include "search.h"
@@ -1281,17 +1282,22 @@ int fte_im2col_first_s16(const float* x, uint16_t* cols16, int n, int h, int wd,
     return rc(l_im2col_first(x, f32p(cols16), n, h, wd, cin, ksize, stride, ph.out, pw.out, ph.before, pw.before, kpad, (hipStream_t)stream, 1));
 }
 
+// the refusals the four transform entries share; min_stride: the header a slot must at least hold (64, aligned slots 128)
+static bool preprocess_args_ok(const uint8_t* slots, const float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h,
+                               int crop_w, long min_stride) {
+    return slots && out && n > 0 && (channels == 1 || channels == 3) && in_h > 0 && in_w > 0 && crop_h > 0 && crop_w > 0 &&
+           crop_h <= in_h && crop_w <= in_w && slot_stride >= min_stride && slot_stride % 64 == 0 && n <= 65535;
+}
+
 int fte_preprocess_u8(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
                       void* stream) {
-    if (!slots || !out || n <= 0 || (channels != 1 && channels != 3) || in_h <= 0 || in_w <= 0 || crop_h <= 0 || crop_w <= 0 ||
-        crop_h > in_h || crop_w > in_w || slot_stride < 64 || slot_stride % 64 || n > 65535) return FTE_EINVAL;
+    if (!preprocess_args_ok(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, 64)) return FTE_EINVAL;
     return rc(k_preprocess_u8(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, (hipStream_t)stream));
 }
 
 int fte_preprocess_u8_aug(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
                           void* stream) {
-    if (!slots || !out || n <= 0 || (channels != 1 && channels != 3) || in_h <= 0 || in_w <= 0 || crop_h <= 0 || crop_w <= 0 ||
-        crop_h > in_h || crop_w > in_w || slot_stride < 64 || slot_stride % 64 || n > 65535) return FTE_EINVAL;
+    if (!preprocess_args_ok(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, 64)) return FTE_EINVAL;
     return rc(k_preprocess_u8_aug(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, (hipStream_t)stream));
 }
 
@@ -1302,8 +1308,7 @@ size_t fte_preprocess_u8_geo_ws_bytes(int n, int channels, int crop_h, int crop_
 
 int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
                           const float* affine_table, void* ws, size_t ws_bytes, void* stream) {
-    if (!slots || !out || !affine_table || n <= 0 || (channels != 1 && channels != 3) || in_h <= 0 || in_w <= 0 || crop_h <= 0 ||
-        crop_w <= 0 || crop_h > in_h || crop_w > in_w || slot_stride < 64 || slot_stride % 64 || n > 65535 ||
+    if (!preprocess_args_ok(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, 64) || !affine_table ||
         (long)crop_h * crop_w * channels >= ((long)1 << 28)) return FTE_EINVAL;       // plane offsets are ints
     const size_t need = k_preprocess_u8_geo_ws_bytes(n, channels, crop_h, crop_w);
     if (need && (!ws || ws_bytes < need)) return FTE_EWORKSPACE;
@@ -1312,8 +1317,7 @@ int fte_preprocess_u8_geo(const uint8_t* slots, float* out, int n, long slot_str
 
 int fte_preprocess_u8_align(const uint8_t* slots, float* out, int n, long slot_stride, int channels, int in_h, int in_w, int crop_h, int crop_w,
                             void* stream) {
-    if (!slots || !out || n <= 0 || (channels != 1 && channels != 3) || in_h <= 0 || in_w <= 0 || crop_h <= 0 || crop_w <= 0 ||
-        crop_h > in_h || crop_w > in_w || slot_stride < 128 || slot_stride % 64 || n > 65535) return FTE_EINVAL;
+    if (!preprocess_args_ok(slots, out, n, slot_stride, channels, in_h, in_w, crop_h, crop_w, 128)) return FTE_EINVAL;
     return rc(k_preprocess_u8_align(slots, out, n, slot_stride, channels, crop_h, crop_w, (hipStream_t)stream));
 }
 

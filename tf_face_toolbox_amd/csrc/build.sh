@@ -14,7 +14,7 @@ mkdir -p "$HERE/obj"
 FTEH="$HERE/../../include/fte.h"
 SHA=$( (cd "$HERE" && cat $(ls *.hip *.h | LC_ALL=C sort)) | cat - "$FTEH" | sha256sum | cut -c1-16)
 HDR=$( (cd "$HERE" && cat $(ls *.h | LC_ALL=C sort)) | cat - "$FTEH" | sha256sum | cut -c1-16)
-SRCS="igemm igemm16 wgrad16 pw16 kernels layers wino search partial_fc cluster iresnet api"
+SRCS="igemm igemm16 wgrad16 pw16 kernels loader layers wino search partial_fc cluster iresnet api"
 pids=()
 for f in $SRCS; do
   KEY="$HDR-$(sha256sum < "$HERE/$f.hip" | cut -c1-16)-$FLAGS"

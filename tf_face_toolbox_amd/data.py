@@ -95,7 +95,7 @@ def _class_lists(items_and_labels, num_per_class):
 
 # ------------------------------------------------------------------ decode / preprocess (host)
 from ._decode_worker import resize_bilinear_tf1, decode as _decode, train_example as _train_example, fill_rows as _fill_rows   # noqa: E402,F401
-from ._decode_worker import raw_example as _raw_example, HEADER_BYTES   # noqa: E402
+from ._decode_worker import raw_example as _raw_example, Task as _Task, HEADER_BYTES, ALIGN_HEADER_BYTES   # noqa: E402
 
 
 class _Prefetcher(object):
@@ -408,6 +408,12 @@ def raw_slot_bytes(header_bytes, num_channels, out_h, out_w):
     return (slot + 63) // 64 * 64
 
 
+# (align, augmentation) -> the entry point of the GPU transform and the header bytes of its slots
+_RAW_ENTRIES = {(False, 0): ('fte_preprocess_u8', HEADER_BYTES), (False, 1): ('fte_preprocess_u8_aug', HEADER_BYTES),
+                (False, 2): ('fte_preprocess_u8_geo', HEADER_BYTES), (False, 3): ('fte_preprocess_u8_geo', HEADER_BYTES),
+                (True, 0): ('fte_preprocess_u8_align', ALIGN_HEADER_BYTES), (True, 1): ('fte_preprocess_u8_align', ALIGN_HEADER_BYTES)}
+
+
 def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmentation, device, align=False, slot_bytes=None):
     """(slot bytes, transform) when the decode workers hand over DECODED uint8 images and the resize / crop / flip / normalise
     runs on the GPU (fte_preprocess_u8: the same bits as the host transform, tests/test_gpu_loader.py), else (0, None).  The
@@ -422,13 +428,9 @@ def _raw_slots(num_workers, rows, num_channels, in_h, in_w, out_h, out_w, augmen
     (64 + its row stride: every image fits, mode 1 cannot occur)."""
     if num_workers <= 0 or torch.device(device).type != 'cuda' or os.environ.get('FTE_LOADER_GPU', '1') == '0':
         return 0, None
-    entry = 'fte_preprocess_u8_geo' if augmentation & 2 else 'fte_preprocess_u8_aug' if augmentation else 'fte_preprocess_u8'
     from . import _lib
-    from ._decode_worker import HEADER_BYTES
-    if align:
-        from ._decode_worker import ALIGN_HEADER_BYTES as HEADER_BYTES
-        entry = 'fte_preprocess_u8_align'
-    slot = raw_slot_bytes(HEADER_BYTES, num_channels, out_h, out_w) if slot_bytes is None else slot_bytes
+    entry, header_bytes = _RAW_ENTRIES[bool(align), augmentation]
+    slot = raw_slot_bytes(header_bytes, num_channels, out_h, out_w) if slot_bytes is None else slot_bytes
 
     extra = ()
     if augmentation & 2:
@@ -514,6 +516,52 @@ def _resident_rows(rows):
 
 
 # ------------------------------------------------------------------ public input builders
+def _feed(num_workers, rows, num_channels, in_h, in_w, crop_h, crop_w, augmentation, device, align, pack, pack_on_gpu, threads):
+    """What train_inputs and eval_inputs both build for batches of `rows` images: (slot bytes, transform, procs, pool, params).
+    procs: the _WorkerPool -- over raw slots when the GPU transform runs, over the header rows of a resident pack, else over
+    finished float rows -- or None without worker processes; pool: the thread pool that decodes in this process then (a resident
+    pack needs none: its headers are a few draws per image); params: the fields of a worker's Task after its rows.
+    A pack's slots are sized from the pack (every row fits: no mode-1 slots); a resident pack has its transform whatever the
+    number of workers, which only write headers."""
+    cropped = crop_h != -1 and crop_w != -1
+    out_h, out_w = (crop_h, crop_w) if cropped else (in_h, in_w)
+    slot, transform = _raw_slots(max(num_workers, 1) if pack_on_gpu else num_workers, rows, num_channels, in_h, in_w, out_h, out_w,
+                                 augmentation, device, align=align, slot_bytes=None if pack is None else HEADER_BYTES + pack.row_stride)
+    if pack_on_gpu:
+        transform = _resident_transform(pack, _upload_pack(pack, torch.device(device)), rows, slot, transform)
+        shape, dtype = (_resident_rows(rows), HEADER_BYTES), np.uint8
+    elif slot:
+        shape, dtype = (rows, slot), np.uint8
+    else:
+        shape, dtype = (rows, out_h, out_w, num_channels), np.float32
+    procs = _WorkerPool(num_workers, shape, pin=torch.device(device).type == 'cuda', dtype=dtype) if num_workers > 0 else None
+    pool = None if procs or pack_on_gpu else ThreadPoolExecutor(threads)
+    task = _Task(buffer=None, shape=None, rows=None, num_channels=num_channels, in_h=in_h, in_w=in_w, crop_h=crop_h, crop_w=crop_w,
+                 augmentation=augmentation, raw=1 if slot else 0, pack=None if pack is None else pack.path,   # the workers map the pack once
+                 header_only=bool(pack_on_gpu))
+    return slot, transform, procs, pool, tuple(task)[3:]
+
+
+def _pump(procs, params, pending, draw):
+    """Worker processes: batch k + 1 is being decoded while batch k is copied out.  Keeps procs.DEPTH tickets open -- draw()
+    gives the next batch's (rows for the workers, whatever travels with them) -- and returns (the oldest batch, what travelled)."""
+    while len(pending) < procs.DEPTH:
+        rows, extra = draw()
+        pending.append((procs.submit(rows, params), extra))
+    ticket, extra = pending.pop(0)
+    return procs.wait(ticket), extra
+
+
+def _closer(pf, pool):
+    """the close() of a loader: orderly shutdown of the producer thread, the decode workers and the thread pool"""
+    def close():
+        ended = pf.close()
+        if pool is not None:
+            pool.shutdown(wait=True)
+        return ended
+    return close
+
+
 def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop_width=-1, is_color=1,
                  augmentation=0, batch_size=-1, num_classes=-1, num_per_class=-1, device='cuda', seed=None,
                  rank=0, world_size=1, num_workers=None, landmark_list_path=None, packed_data_path=None, pack_on_gpu=False):
@@ -590,23 +638,10 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
             # measured on the MI355X host (to the GPU straight out of the page-locked worker buffers): 16 workers 18.7 k,
             # 32 workers 23.8 k, 48 workers 27.1 k images/s (through a staging copy: 24.5 k at 48)
             num_workers = min(max(1, cpu_count() // 2 // max(1, world_size)), 48, shard // 4) if shard >= 64 else 0
-    on_gpu = torch.device(device).type == 'cuda'
-    # a pack's slots are sized from the pack (every row fits: no mode-1 slots); a resident pack has its transform whatever the
-    # number of workers, which only write headers (none: this process writes them)
-    slot, transform = _raw_slots(max(num_workers, 1) if pack_on_gpu else num_workers, shard, num_channels, input_height, input_width, out_h,
-                                 out_w, augmentation, device, align=landmarks is not None,
-                                 slot_bytes=None if pack is None else HEADER_BYTES + pack.row_stride)
-    if pack_on_gpu:
-        transform = _resident_transform(pack, _upload_pack(pack, torch.device(device)), shard, slot, transform)
-        procs = _WorkerPool(num_workers, (_resident_rows(shard), HEADER_BYTES), pin=on_gpu, dtype=np.uint8) if num_workers > 0 else None
-    elif slot:
-        procs = _WorkerPool(num_workers, (shard, slot), pin=on_gpu, dtype=np.uint8)
-    else:
-        procs = _WorkerPool(num_workers, (shard, out_h, out_w, num_channels), pin=on_gpu) if num_workers > 0 else None
-    pool = None if procs or pack_on_gpu else ThreadPoolExecutor(max(1, cpu_count() // 2))
-    params = (num_channels, input_height, input_width, crop_height, crop_width, augmentation) + ((1,) if slot else ())
-    if pack is not None:                                 # the task names the pack by its path; the workers map it once
-        params = params[:6] + (1 if slot else 0, pack.path, bool(pack_on_gpu))
+    slot, transform, procs, pool, params = _feed(num_workers, rows=shard, num_channels=num_channels, in_h=input_height, in_w=input_width,
+                                                 crop_h=crop_height, crop_w=crop_width, augmentation=augmentation, device=device,
+                                                 align=landmarks is not None, pack=pack, pack_on_gpu=pack_on_gpu,
+                                                 threads=max(1, cpu_count() // 2))
 
     def draw():
         items = [next(gen) for _ in range(batch_size)][rank * shard:(rank + 1) * shard]
@@ -616,7 +651,11 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
             return [(e[0], tuple(landmarks[e[1]].tolist())) for e, _ in items], seeds, labels
         return [(e,) for e, _ in items], seeds, labels
 
-    pending = []                                         # worker processes: batch k + 1 is being decoded while batch k is copied out
+    pending = []
+
+    def worker_rows():
+        items, seeds, labels = draw()
+        return [(i, it[0], int(sd)) + it[1:] for i, (it, sd) in enumerate(zip(items, seeds))], (labels, items)
 
     def with_index(buf, items):
         """resident pack: the int64 pack rows behind the headers, validated here (the kernel clamps what it is given)"""
@@ -628,12 +667,8 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
 
     def make_batch():
         if procs is not None:
-            while len(pending) < procs.DEPTH:
-                items, seeds, labels = draw()
-                pending.append((procs.submit([(i, it[0], int(sd)) + it[1:] for i, (it, sd) in enumerate(zip(items, seeds))], params),
-                                labels, items if pack_on_gpu else None))
-            ticket, labels, items = pending.pop(0)
-            return (with_index(procs.wait(ticket), items) if pack_on_gpu else procs.wait(ticket)), labels
+            buf, (labels, items) = _pump(procs, params, pending, worker_rows)
+            return (with_index(buf, items) if pack_on_gpu else buf), labels
         items, seeds, labels = draw()
         if pack_on_gpu:                                  # no workers: the headers are a few draws per image, written here
             buf = np.zeros((_resident_rows(shard), HEADER_BYTES), dtype=np.uint8)
@@ -650,14 +685,8 @@ def train_inputs(data_list_path, input_height, input_width, crop_height=-1, crop
 
     pf = _Prefetcher(make_batch, torch.device(device), num_classes=num_classes_total, pool=procs, transform=transform)
     src = _BatchSource(pf)
-
-    def close():
-        ended = pf.close()
-        if pool is not None:
-            pool.shutdown(wait=True)
-        return ended
     return {'images': src.images, 'labels': src.labels, 'num_classes': num_classes_total,
-            'num_examples': num_examples_total, 'batch_size': batch_size, 'close': close,
+            'num_examples': num_examples_total, 'batch_size': batch_size, 'close': _closer(pf, pool),
             'pin_fallback': bool(procs is not None and procs.pin_failed), 'gpu_transform': bool(slot),
             'packed': None if pack is None else 'gpu' if pack_on_gpu else 'host', 'pack': None if pack is None else pack.describe()}
 
@@ -689,22 +718,13 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
         num_workers = int(os.environ.get('FTE_LOADER_WORKERS', '-1'))
         if num_workers < 0:
             num_workers = min(max(1, cpu_count() // 2), 32, batch_size // 4) if batch_size >= 64 else 0
-    on_gpu = torch.device(device).type == 'cuda'
     if pack_on_gpu:
         return _resident_eval(pack, batch_size, num_channels, input_height, input_width, torch.device(device)), num_examples
-    slot, transform = _raw_slots(num_workers, batch_size, num_channels, input_height, input_width, input_height, input_width, 0, device,
-                                 align=landmarks is not None, slot_bytes=None if pack is None else HEADER_BYTES + pack.row_stride)
-    if slot:
-        procs = _WorkerPool(num_workers, (batch_size, slot), pin=on_gpu, dtype=np.uint8)
-    else:
-        procs = _WorkerPool(num_workers, (batch_size, input_height, input_width, num_channels), pin=on_gpu) if num_workers > 0 else None
-    pool = None if procs else ThreadPoolExecutor(8)
+    slot, transform, procs, pool, params = _feed(num_workers, rows=batch_size, num_channels=num_channels, in_h=input_height,
+                                                 in_w=input_width, crop_h=-1, crop_w=-1, augmentation=0, device=device,
+                                                 align=landmarks is not None, pack=pack, pack_on_gpu=False, threads=8)
     state = {'pos': 0}
-    params = (num_channels, input_height, input_width, -1, -1, 0) + ((1,) if slot else ())
-    more = {}
-    if pack is not None:
-        params = params[:6] + (1 if slot else 0, pack.path, False)
-        more = {'pack': pack}
+    more = {} if pack is None else {'pack': pack}
     pending = []
 
     def draw():
@@ -716,9 +736,7 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
 
     def make_batch():
         if procs is not None:
-            while len(pending) < procs.DEPTH:
-                pending.append(procs.submit([(i, q[0], None) + q[1:] for i, q in enumerate(draw())], params))
-            return procs.wait(pending.pop(0)), None
+            return _pump(procs, params, pending, lambda: ([(i, q[0], None) + q[1:] for i, q in enumerate(draw())], None))
         imgs = list(pool.map(lambda q: (_decode(q[0], num_channels, input_height, input_width, *q[1:], **more) - 0.5) / 0.5, draw()))
         return np.stack(imgs).astype(np.float32), None
 
@@ -727,12 +745,7 @@ def eval_inputs(data_list_path, batch_size, is_color, input_height, input_width,
     def next_batch():
         return pf.advance()[0]
 
-    def close():
-        ended = pf.close()
-        if pool is not None:
-            pool.shutdown(wait=True)
-        return ended
-    next_batch.close = close                     # orderly shutdown of the producer thread and the decode workers (evaluate.py)
+    next_batch.close = _closer(pf, pool)         # orderly shutdown of the producer thread and the decode workers (evaluate.py)
     next_batch.packed = None if pack is None else 'host'
     return next_batch, num_examples
 

@@ -132,27 +132,9 @@ def affine_warp(image, coef):
     """tf.contrib.image.transform(image, coef + [0, 0], 'BILINEAR') as the TF-1.x kernel computes it, in float32 with every
     operation rounded on its own: output pixel (x, y) reads (sx, sy) = ((a0 x + a1 y) + a2, (b0 x + b1 y) + b2); with
     f = floor, c = f + 1:  top = (cx - sx) R(fy, fx) + (sx - fx) R(fy, cx), bot the same on row cy,
-    out = (cy - sy) top + (sy - fy) bot;  R is 0 outside the image."""
-    h, w, _ = image.shape
-    a0, a1, a2, b0, b1, b2 = (np.float32(v) for v in coef)
-    x = np.arange(w, dtype=np.float32)[None, :]
-    y = np.arange(h, dtype=np.float32)[:, None]
-    sx = (a0 * x + a1 * y) + a2
-    sy = (b0 * x + b1 * y) + b2
-    fx, fy = np.floor(sx), np.floor(sy)
-    cx, cy = fx + np.float32(1), fy + np.float32(1)
-
-    def read(yy, xx):
-        ok = (yy >= 0) & (yy <= h - 1) & (xx >= 0) & (xx <= w - 1)          # false for NaN as well
-        yi = np.where(ok, yy, 0).astype(np.int64)
-        xi = np.where(ok, xx, 0).astype(np.int64)
-        return np.where(ok[:, :, None], image[yi, xi], np.float32(0))
-    wl, wr = (cx - sx)[:, :, None], (sx - fx)[:, :, None]
-    top = wl * read(fy, fx) + wr * read(fy, cx)
-    bot = wl * read(cy, fx) + wr * read(cy, cx)
-    out = (cy - sy)[:, :, None] * top + (sy - fy)[:, :, None] * bot
-    assert out.dtype == np.float32
-    return out
+    out = (cy - sy) top + (sy - fy) bot;  R is 0 outside the image.  The host's one warp formula, over the whole image: align_warp
+    (its none-of-four-taps rule gives the +0 this formula gives for the table's finite coordinates)."""
+    return align_warp(image, coef, image.shape[0], image.shape[1])
 
 
 def geometric_augmentation(image, rng):
